@@ -21,7 +21,7 @@ each batch's scores before it proceeds (HypothesisSelection.cpp:248-257) sees.  
 communicator the exchange ran on.  The Python twin of the exchange (physimglobalpose_amd.sharding.BucketedExchange over
 torch.distributed) stays as the secondary row `rows.torch_twin`.  value = hypotheses all ranks scored / max-over-ranks wall time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode weighted|plain]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode weighted|plain] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     PGP_MULTI_EMULATE=2 python bench.py --gpus 2 --steps 6     # N logical members on ONE device: a smoke run of the
@@ -683,6 +683,34 @@ def _quantiles_ms(ts):
             "min_ms": float(a[0]), "calls": int(len(a))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, scores, counts, best_index, best_score):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step -- the score vector, the per-hypothesis
+    inlier counts (None where this form has no complete vector of them), the best index and its score -- as <name>.npy in
+    float32 / float64 (float64 holds every int32 exactly).  Past DUMP_LIMIT_BYTES, a fixed seeded sample of hypotheses is
+    written and its indices go to sample_index.npy, so two builds still compare entry for entry."""
+    scores = np.asarray(scores, np.float32).reshape(-1)
+    counts = None if counts is None else np.asarray(counts, np.float64).reshape(-1)
+    per_h = 4 + (0 if counts is None else 8)
+    arrays = {}
+    if scores.size * per_h > DUMP_LIMIT_BYTES - 4096:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (per_h + 8)
+        idx = np.sort(np.random.default_rng(0).choice(scores.size, keep, replace=False))
+        arrays["sample_index"] = idx.astype(np.float64)
+        scores = scores[idx]
+        counts = None if counts is None else counts[idx]
+    arrays["scores"] = scores
+    if counts is not None:
+        arrays["counts"] = counts
+    arrays["best_index"] = np.array([best_index], np.float64)
+    arrays["best_score"] = np.array([best_score], np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def per_call_one_device(sc, w, torch, mode, d_batches, calls=200):
     """SURVEY 8(d)'s metric as a caller meets it: the wall time of ONE synchronous call, clouds resident.  `host_pointers` =
     pgp_score_lcp (transforms in the caller's memory, scores / counts / best back in it: what base.cc:1885-1901's consumer
@@ -722,7 +750,8 @@ def per_call_one_device(sc, w, torch, mode, d_batches, calls=200):
     return out
 
 
-def group_headline(grp, args, w, mode, mode_name, n_h, world, barrier, max_over_ranks, check_device, torch=None):
+def group_headline(grp, args, w, mode, mode_name, n_h, world, barrier, max_over_ranks, check_device, torch=None,
+                   dump_dir=None):
     """The headline through the product's own device group (pgp_multi_*): N_BATCH resident batches of world * n_h
     hypotheses, K steps queued back to back (pgp_multi_enqueue_slot: no host wait per step), ONE pgp_multi_collect at the end;
     then the synchronous per-call forms.  The same function serves the single-process group (barrier = no-op) and the ranked
@@ -773,6 +802,8 @@ def group_headline(grp, args, w, mode, mode_name, n_h, world, barrier, max_over_
     launches, kern_ms = m0.kernel_timing(reset=True)
     m0.set_kernel_timing(False)
     lb = (state["k"] - 1) % N_BATCH
+    if dump_dir:
+        dump_outputs(dump_dir, *last)
     # ---- the synchronous forms, call by call (every rank makes the same calls: the collective needs them all)
     k_pc = max(40, min(args.steps, 200)) if not emulated else 6
     hs, rs = [], []
@@ -848,7 +879,8 @@ def group_process(args, real_stdout):
     grp = MultiGpuScorer([0] if emulate >= 2 else list(range(args.gpus)))
     world = grp.n_devices
     w = synth.make_workload(N_SCENE, N_MODEL, args.hyp * world * N_BATCH, config_id=2)
-    out = group_headline(grp, args, w, mode, args.mode, args.hyp, world, lambda: None, lambda x: x, 0)
+    out = group_headline(grp, args, w, mode, args.mode, args.hyp, world, lambda: None, lambda x: x, 0,
+                         dump_dir=args.dump_outputs)
     grp.close()
     os.write(real_stdout, (json.dumps(compact_line(out)) + "\n").encode())
     os.close(real_stdout)
@@ -883,7 +915,8 @@ def orchestrate(args):
         except ValueError as e:
             return None, f"unparsable line: {e!r}"
 
-    group, err_g = run([sys.executable, here] + common + ["--form", "group"], env)
+    dump = ["--dump-outputs", args.dump_outputs] if args.dump_outputs else []
+    group, err_g = run([sys.executable, here] + common + dump + ["--form", "group"], env)
     twin, err_t = None, "skipped"
     if os.environ.get("PGP_BENCH_TWIN", "1") != "0" and not (emulate and args.gpus > 4):   # (a 1-GPU box takes few processes)
         with socket.socket() as sk:
@@ -894,7 +927,8 @@ def orchestrate(args):
         if emulate:
             tenv["PGP_DIST_BACKEND"] = "gloo"     # ranks share the one device, the collective goes through the host: a smoke mode
         twin, err_t = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                           "--master-addr", "127.0.0.1", "--master-port", str(port), here] + common + ["--no-cpu-baseline"], tenv)
+                           "--master-addr", "127.0.0.1", "--master-port", str(port), here] + common + ["--no-cpu-baseline"]
+                          + (dump if group is None else []), tenv)   # (the twin's outputs only when its line is the headline)
 
     def twin_row():
         if twin is None:
@@ -962,7 +996,7 @@ def ranked_group_headline(args, torch, dist, rank, world, dev_index, w, mode):
 
     try:
         out = group_headline(grp, args, w, mode, args.mode, args.hyp, world, barrier, max_over_ranks,
-                             dev_index if rank == 0 else None, torch)
+                             dev_index if rank == 0 else None, torch, dump_dir=args.dump_outputs if rank == 0 else None)
         out["launch"] = "torch.distributed.run: one process per GPU, each holding one member of libpgp's group (ncclCommInitRank)"
         return out, None
     finally:
@@ -980,7 +1014,14 @@ def main():
     ap.add_argument("--form", choices=["group"], default=None,
                     help="group: ONE process drives libpgp's device group over --gpus devices (what the launcher-less "
                          "`python bench.py --gpus N` starts as its child)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (scores, counts, best index and "
+                         "score) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.form is None and args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("PGP_BENCH_FORCE_DIST") != "1":
         # no launcher: this process stays off the GPU (nothing below has been imported yet) and starts the children
         raise SystemExit(orchestrate(args))
@@ -1120,6 +1161,14 @@ def main():
 
     # sanity inside the bench: the device result of the last step matches a host-pointer call
     best = d_best.cpu().numpy()
+    if args.dump_outputs and rank == 0 and native is None:   # (a group headline has written its own)
+        if multi:   # the caller of the exchange receives the combined vector and its arg-max; counts stay per rank
+            s_all = ex.last_vector().cpu().numpy()
+            bi = int(ex.argmax[ex.last[1]])
+            dump_outputs(args.dump_outputs, s_all, None, bi, s_all[bi])
+        else:
+            dump_outputs(args.dump_outputs, ex.last_vector().cpu().numpy(), d_counts.cpu().numpy(), int(best[0]),
+                         best[1:2].view(np.float32)[0])
     lb = state["last_batch"]
     T_last = w.T.reshape(N_BATCH, world, n_h, 16)[lb, rank]
     s_host, _, bi_host, _ = sc.score(T_last, mode, w.gate_deg)

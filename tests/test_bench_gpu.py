@@ -176,3 +176,23 @@ def test_launcher_form_with_two_ranks_on_one_device_through_the_products_group()
     assert "ncclCommInitRank" in d["launch"] and "of 2 processes" in d["config"]["group"]
     assert d["per_call"]["host_pointers"]["median_ms"] > 0
     assert d["rows"]["torch_twin"]["value"] > 0
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the last timed step returned.  With --warmup 2 --steps 6 that step scored batch 7 of the
+    8 in rotation (the untimed pre-heat runs whole multiples of 8 steps): a host-pointer call on that batch must agree."""
+    from physimglobalpose_amd import LcpScorer, PGP_MODE_WEIGHTED, synth
+    import numpy as np
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+                          "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["best_index", "best_score", "counts", "scores"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    w = synth.make_workload(50000, 5000, 4096 * 8, config_id=2)
+    sc = LcpScorer(0)
+    sc.init(w.P_xyz, w.P_nrm, w.P_w, w.Q_xyz, w.Q_nrm, w.delta)
+    s, c, bi, bs = sc.score(w.T.reshape(8, 4096, 16)[7], PGP_MODE_WEIGHTED, w.gate_deg)
+    sc.close()
+    assert np.array_equal(got["scores"], s) and np.array_equal(got["counts"], c.astype(np.float64))
+    assert got["best_index"].tolist() == [bi] and got["best_score"].tolist() == [bs]

@@ -1,5 +1,5 @@
 import sys, os, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from physimglobalpose_amd import LcpScorer, PGP_MODE_WEIGHTED, synth
 w = synth.make_workload(50000, 5000, 16384, config_id=210)
