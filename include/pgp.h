@@ -577,6 +577,95 @@ int pgp_backproject_depth(pgp_ctx* ctx, const void* image, int raw16, const unsi
                           int cols, const float K[9], double z_min, double z_max, float* xyz_out, int cap,
                           int* n_out);
 
+/* ---- Table-plane removal (SceneCfg::removeTable / getTableParams, PPE/data_layer/SceneCfg.cpp:38-157) ----
+ * Replaces pcl::SACSegmentation with SACMODEL_PLANE, SAC_MSAC, setDistanceThreshold(0.005),
+ * setMaxIterations(1000), setOptimizeCoefficients(true), and the loop that zeroes the depth pixels near the
+ * plane.  PCL is not vendored and its sampler is seeded from the clock, so PCL's bits are NOT pinned; what is
+ * implemented, step by step (csrc/plane.hip):
+ *   candidates  the n_samples triples given (their order is the candidate order), or max_iterations + 1 drawn
+ *               slots (PCL's loop counts an iteration before it tests iterations > max_iterations, so it
+ *               evaluates up to max_iterations + 1 models).  Slot i draws three point indices as
+ *               variate % n from the counter-based splitmix64 stream keyed by (seed, i) -- attempt a uses
+ *               variates 3a, 3a + 1, 3a + 2 --; a draw with a repeated index or an exactly zero cross product
+ *               is redrawn, up to 64 attempts, after which the slot is invalid.  A given triple with a zero
+ *               cross product is an invalid slot.  Invalid slots are skipped and never counted.
+ *   coefficients  in float, in this order: n = (p1 - p0) x (p2 - p0); |n| = sqrt((nx^2 + ny^2) + nz^2)
+ *               (correctly rounded); (a, b, c) = n / |n|; d = -((a x0 + b y0) + c z0).
+ *   scoring     dist = |((a x + b y) + c z) + d| in float; MSAC penalty = sum of min(dist, threshold) in
+ *               DOUBLE (PCL's published rule: the truncated distance, not its square); inliers = dist <= threshold.
+ *   stop        PGP_PLANE_STOP_ADAPTIVE: PCL's sequential rule over the valid candidates in order -- a candidate
+ *               whose penalty is strictly below the best so far is a record; at a record
+ *               k = log(1 - probability) / log(clamp(1 - w^3, eps, 1 - eps)), w = inliers / n (double); the loop
+ *               ends after the e-th evaluated candidate when e >= k or e > max_iterations; the last record wins.
+ *               PGP_PLANE_STOP_ALL: the minimum penalty over every valid candidate, the lowest index on ties.
+ *   refit       (optimize != 0, setOptimizeCoefficients(true)): the points with dist < threshold (strict, as
+ *               PCL's selectWithinDistance) of the chosen sample; their centroid and the covariance about it,
+ *               double, fixed-order sums; normal = eigenvector of the smallest eigenvalue (pcl::eigen33, sign as it
+ *               comes), d = -n . centroid, rounded to float.  Fewer than 3 such points keep the sampled plane.
+ *   inliers     the final plane's points with dist < threshold (strict, selectWithinDistance): inliers[n] = 1/0.
+ * Every sum has a fixed order (no float atomics): the same call gives the same bits on every run.
+ * When every slot is invalid (collinear input, say) the call succeeds with all-zero coefficients and 0 inliers,
+ * as PCL returns an empty model.  n < 3, a non-finite coordinate, threshold <= 0, probability outside (0, 1),
+ * max_iterations < 1 (or above 65535 candidates), an unknown stop rule or a sample index outside [0, n) are
+ * PGP_EINVAL. */
+enum { PGP_PLANE_STOP_ADAPTIVE = 0, PGP_PLANE_STOP_ALL = 1 };
+
+typedef struct {
+  float threshold;            /* 0.005 (SceneCfg.cpp:61, :116) */
+  int max_iterations;         /* 1000 */
+  double probability;         /* 0.99, PCL's default */
+  int stop;                   /* PGP_PLANE_STOP_ADAPTIVE (default) | PGP_PLANE_STOP_ALL */
+  int optimize;               /* 1 = refit on the inliers + re-selection */
+  unsigned long long seed;    /* keys the drawn candidates (unused with explicit samples) */
+} pgp_plane_options;
+int pgp_plane_default_options(pgp_plane_options* opt);
+
+typedef struct {
+  int status;                 /* PGP_OK, or PGP_EINVAL when the device form met a non-finite point or a bad sample index
+                                 (the result is then empty: zero coefficients, 0 inliers) */
+  int chosen;                 /* candidate index of the winning sample; -1 when no slot is valid */
+  int n_evaluated;            /* valid candidates the stop rule evaluated */
+  int n_valid;                /* valid candidates in the list */
+  int n_candidates;           /* slots in the list: n_samples, or max_iterations + 1 */
+  int sampled_inliers;        /* the chosen sample's dist <= threshold count (the w of the stop rule) */
+  double penalty;             /* the chosen sample's MSAC penalty */
+  float sampled[4];           /* the chosen sample's coefficients, before the refit */
+} pgp_plane_info;
+
+/* The plane fit.  xyz: n x 3; samples (nullable): n_samples x 3 point indices replacing the draw; coeff[4] =
+ * (a, b, c, d) of a x + b y + c z + d = 0; inliers (nullable): n bytes; *n_inliers their number; info
+ * (nullable).  Host pointers, synchronous. */
+int pgp_fit_plane(pgp_ctx* ctx, const float* xyz, int n, const pgp_plane_options* opt, const int* samples, int n_samples,
+                  float coeff[4], unsigned char* inliers, int* n_inliers, pgp_plane_info* info);
+/* The same with DEVICE arrays, results written to device memory (d_coeff: 4 floats, d_inliers: n bytes or NULL,
+ * d_n_inliers: 1 int, d_info: one pgp_plane_info or NULL).  Enqueued on `stream` with no host synchronisation, so it
+ * chains behind pgp_voxel_grid_device; the workspace is sized once and kept in the context.  Finiteness and the sample
+ * indices are checked on the device (d_info->status). */
+int pgp_fit_plane_device(pgp_ctx* ctx, const float* d_xyz, int n, const pgp_plane_options* opt, const int* d_samples,
+                         int n_samples, float* d_coeff, unsigned char* d_inliers, int* d_n_inliers,
+                         pgp_plane_info* d_info, void* stream);
+
+/* The depth mask of SceneCfg::removeTable (SceneCfg.cpp:69-80), bit for bit: per pixel (u, v),
+ * x = (float)((v - cx) * depth / fx), y = (float)((u - cy) * depth / fy), z = depth (float operations);
+ * dist = |((a x + b y) + c z) + d| in DOUBLE from the float coefficients (pcl::pointToPlaneDistance);
+ * the pixel becomes 0 when dist < threshold (strict; 0.005 there).  image (in-out): rows x cols, float metres
+ * (raw16 == 0) or the raw 16-bit encoding pgp_backproject_depth reads (raw16 != 0; a masked pixel becomes raw
+ * 0); K: 3x3 row-major; *n_masked (nullable) = pixels zeroed.  Host pointers, synchronous; the _device form
+ * takes a device image, writes the count to d_n_masked (nullable) and does not synchronise `stream`. */
+int pgp_mask_plane_depth(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, const float K[9],
+                         const float coeff[4], double threshold, int* n_masked);
+int pgp_mask_plane_depth_device(pgp_ctx* ctx, void* d_image, int raw16, int rows, int cols, const float K[9],
+                                const float coeff[4], double threshold, int* d_n_masked, void* stream);
+
+/* SceneCfg::removeTable in one call: back-projection (0.1 < z < 2.0, as convert3dOrganizedRGB), the voxel grid
+ * (leaf; 0.005 there), pgp_fit_plane_device and the depth mask, all on the device: the image goes up once and
+ * comes back once, no cloud leaves the device.  The mask threshold is opt->threshold read as the double of its
+ * shortest decimal form (0.005f -> 0.005, the reference's literal).  coeff[4] (nullable) receives the plane,
+ * *n_masked (nullable) the pixels zeroed.  One deviation: the reference's organised cloud keeps out-of-range
+ * pixels as (0, 0, 0) points, which puts one voxel at the camera origin into the fit; they are dropped here. */
+int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, const float K[9], float leaf,
+                     const pgp_plane_options* opt, float coeff[4], int* n_masked);
+
 /* Replaces UCTState::computeCost (PPE/hypothesis_verification/mcts/UCTState.cpp:93-116) for n
  * rendered depth images against one observed image (all rows x cols float, row-major, metres):
  * render_score[i] = obScore + renScore - intScore with the pixel tests of the reference and

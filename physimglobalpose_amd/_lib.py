@@ -61,6 +61,21 @@ class ClusterParams(C.Structure):
     _fields_ = [("accept_fraction", C.c_float), ("rot_thresh_deg", C.c_float), ("trans_thresh", C.c_float)]
 
 
+PGP_PLANE_STOP_ADAPTIVE = 0
+PGP_PLANE_STOP_ALL = 1
+
+
+class PlaneOptions(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("max_iterations", C.c_int), ("probability", C.c_double), ("stop", C.c_int),
+                ("optimize", C.c_int), ("seed", C.c_ulonglong)]
+
+
+class PlaneInfo(C.Structure):
+    _fields_ = [("status", C.c_int), ("chosen", C.c_int), ("n_evaluated", C.c_int), ("n_valid", C.c_int),
+                ("n_candidates", C.c_int), ("sampled_inliers", C.c_int), ("penalty", C.c_double),
+                ("sampled", C.c_float * 4)]
+
+
 # every symbol include/pgp.h declares: (restype, argtypes)
 SIGNATURES = {
     "pgp_version": (C.c_int, []),
@@ -194,6 +209,16 @@ SIGNATURES = {
     "pgp_set_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "pgp_get_kernel_timing": (C.c_int, [C.c_void_p, _i, _f, C.c_int]),
     "pgp_get_index_info": (C.c_int, [C.c_void_p, C.POINTER(IndexInfo)]),
+    "pgp_plane_default_options": (C.c_int, [C.POINTER(PlaneOptions)]),
+    "pgp_fit_plane": (C.c_int, [C.c_void_p, _f, C.c_int, C.POINTER(PlaneOptions), _i, C.c_int, _f, C.POINTER(C.c_ubyte), _i,
+                                C.POINTER(PlaneInfo)]),
+    "pgp_fit_plane_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PlaneOptions), C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgp_mask_plane_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f, _f, C.c_double, _i]),
+    "pgp_mask_plane_depth_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f, _f, C.c_double,
+                                              C.c_void_p, C.c_void_p]),
+    "pgp_remove_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_float,
+                                   C.POINTER(PlaneOptions), _f, _i]),
 }
 
 _lib = None

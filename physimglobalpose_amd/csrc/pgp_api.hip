@@ -210,7 +210,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   if (ctx->h_pin) {
@@ -1586,16 +1586,7 @@ namespace {
 // come takes ~5 n draws when n is barely above cap), every subset equally likely; handed out in ascending order; a base with
 // fewer than `cap` quads hands out all of them.  The reference draws from the process's rand(), seeded from the clock: any
 // uniform sample of `cap` distinct quads is its behaviour.  sample_quads_kernel and pgp_sample_quads: bit for bit the same picks.
-__host__ __device__ inline unsigned long long sample_state(unsigned long long seed, int base) {
-  return (seed ^ 0xD1B54A32D192ED03ull) + (unsigned long long)(base + 1) * 0xBF58476D1CE4E5B9ull;
-}
-__host__ __device__ inline unsigned int sample_variate(unsigned long long state, int i) {
-  unsigned long long z = state + (unsigned long long)(i + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (unsigned int)(z >> 33);
-}
+// (sample_state / sample_variate: pgp_internal.h, shared with the plane fit's draw)
 constexpr int kSampleMax = 128;   // two slots per lane of the base's wave
 
 // one wave per base: where the base's picks start (the sum of the earlier bases' counts), then its draw
@@ -2727,6 +2718,204 @@ int pgp_get_index_info(pgp_ctx* ctx, pgp_index_info* info) {
     info->n_blocks = ctx->grid.sparse ? ctx->n_blocks : (long long)ctx->grid.nbx * ctx->grid.nby * ctx->grid.nbz;
     info->build_ms = ctx->build_ms;
   }
+  return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- table-plane removal (plane.hip) ----------------------------------------------------------------------------
+namespace {
+bool plane_options_ok(const pgp_plane_options* o, const char* who) {
+  if (!o || !(o->threshold > 0.f) || !std::isfinite(o->threshold) || o->max_iterations < 1 ||
+      o->max_iterations >= plane_max_candidates() || !(o->probability > 0.0 && o->probability < 1.0) ||
+      (o->stop != PGP_PLANE_STOP_ADAPTIVE && o->stop != PGP_PLANE_STOP_ALL)) {
+    set_error("%s: bad options (threshold > 0, 1 <= max_iterations < %d, 0 < probability < 1, stop 0 or 1)", who,
+              plane_max_candidates());
+    return false;
+  }
+  return true;
+}
+
+// the double of a float's shortest decimal form (0.005f -> 0.005): the literal a float option stands for
+double shortest_decimal(float f) {
+  char buf[48];
+  for (int p = 1; p <= 9; ++p) {
+    std::snprintf(buf, sizeof buf, "%.*g", p, (double)f);
+    if (std::strtof(buf, nullptr) == f) return std::strtod(buf, nullptr);
+  }
+  return (double)f;
+}
+}  // namespace
+
+extern "C" {
+
+int pgp_plane_default_options(pgp_plane_options* opt) {
+  if (!opt) {
+    set_error("pgp_plane_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->threshold = 0.005f;
+  opt->max_iterations = 1000;
+  opt->probability = 0.99;
+  opt->stop = PGP_PLANE_STOP_ADAPTIVE;
+  opt->optimize = 1;
+  opt->seed = 0;
+  return PGP_OK;
+}
+
+int pgp_fit_plane_device(pgp_ctx* ctx, const float* d_xyz, int n, const pgp_plane_options* opt, const int* d_samples,
+                         int n_samples, float* d_coeff, unsigned char* d_inliers, int* d_n_inliers,
+                         pgp_plane_info* d_info, void* stream) {
+  if (!ctx || n < 3 || !d_xyz || !d_coeff || !d_n_inliers || (d_samples && (n_samples < 1 || n_samples > plane_max_candidates()))) {
+    set_error("pgp_fit_plane_device: bad argument (n = %d >= 3, 1 <= n_samples <= %d)", n, plane_max_candidates());
+    return PGP_EINVAL;
+  }
+  if (!plane_options_ok(opt, "pgp_fit_plane_device")) return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_fit_plane(ctx, d_xyz, n, opt, d_samples, n_samples, d_coeff, d_inliers, d_n_inliers, d_info, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_fit_plane(pgp_ctx* ctx, const float* xyz, int n, const pgp_plane_options* opt, const int* samples, int n_samples,
+                  float coeff[4], unsigned char* inliers, int* n_inliers, pgp_plane_info* info) {
+  if (!ctx || n < 3 || !xyz || !coeff || !n_inliers || (samples && (n_samples < 1 || n_samples > plane_max_candidates()))) {
+    set_error("pgp_fit_plane: bad argument (n = %d >= 3, 1 <= n_samples <= %d)", n, plane_max_candidates());
+    return PGP_EINVAL;
+  }
+  if (!plane_options_ok(opt, "pgp_fit_plane")) return PGP_EINVAL;
+  for (size_t i = 0; i < (size_t)n * 3; ++i)
+    if (!std::isfinite(xyz[i])) {
+      set_error("pgp_fit_plane: point %zu is not finite", i / 3);
+      return PGP_EINVAL;
+    }
+  if (samples)
+    for (size_t i = 0; i < (size_t)n_samples * 3; ++i)
+      if (samples[i] < 0 || samples[i] >= n) {
+        set_error("pgp_fit_plane: sample %zu names point %d of %d", i / 3, samples[i], n);
+        return PGP_EINVAL;
+      }
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t b_xyz = ((size_t)n * 12 + 255) & ~(size_t)255, b_s = samples ? ((size_t)n_samples * 12 + 255) & ~(size_t)255 : 0,
+               b_m = ((size_t)n + 255) & ~(size_t)255;
+  int rc = ctx->d_plane_io.ensure(b_xyz + b_s + b_m + 512);
+  if (rc != PGP_OK) return rc;
+  unsigned char* base = ctx->d_plane_io.as<unsigned char>();
+  float* d_xyz = reinterpret_cast<float*>(base);
+  int* d_s = samples ? reinterpret_cast<int*>(base + b_xyz) : nullptr;
+  unsigned char* d_m = base + b_xyz + b_s;
+  float* d_c = reinterpret_cast<float*>(base + b_xyz + b_s + b_m);
+  int* d_n = reinterpret_cast<int*>(base + b_xyz + b_s + b_m + 64);
+  pgp_plane_info* d_i = reinterpret_cast<pgp_plane_info*>(base + b_xyz + b_s + b_m + 128);
+  PGP_HIP(hipMemcpyAsync(d_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  if (samples) PGP_HIP(hipMemcpyAsync(d_s, samples, (size_t)n_samples * 12, hipMemcpyHostToDevice, st));
+  if ((rc = launch_fit_plane(ctx, d_xyz, n, opt, d_s, n_samples, d_c, inliers ? d_m : nullptr, d_n, d_i, st)) != PGP_OK)
+    return rc;
+  pgp_plane_info h_info;
+  HostOut out(ctx, st);
+  if ((rc = out.to(coeff, d_c, 16)) != PGP_OK || (rc = out.to(n_inliers, d_n, 4)) != PGP_OK ||
+      (rc = out.to(&h_info, d_i, sizeof h_info)) != PGP_OK || (inliers && (rc = out.to(inliers, d_m, (size_t)n)) != PGP_OK) ||
+      (rc = out.sync()) != PGP_OK)
+    return rc;
+  if (info) *info = h_info;
+  return PGP_OK;
+}
+
+int pgp_mask_plane_depth_device(pgp_ctx* ctx, void* d_image, int raw16, int rows, int cols, const float K[9],
+                                const float coeff[4], double threshold, int* d_n_masked, void* stream) {
+  if (!ctx || rows < 0 || cols < 0 || !K || !coeff || ((size_t)rows * cols > 0 && !d_image) ||
+      (size_t)rows * cols > ((size_t)1 << 30) || !(threshold > 0.0) || !std::isfinite(threshold)) {
+    set_error("pgp_mask_plane_depth_device: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_mask_plane_depth(ctx, d_image, raw16 != 0, rows, cols, K, coeff, nullptr, threshold, d_n_masked, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_mask_plane_depth(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, const float K[9], const float coeff[4],
+                         double threshold, int* n_masked) {
+  if (!ctx || rows < 0 || cols < 0 || !K || !coeff || ((size_t)rows * cols > 0 && !image) ||
+      (size_t)rows * cols > ((size_t)1 << 30) || !(threshold > 0.0) || !std::isfinite(threshold)) {
+    set_error("pgp_mask_plane_depth: bad argument");
+    return PGP_EINVAL;
+  }
+  if (n_masked) *n_masked = 0;
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t px = raw16 ? 2 : 4, b_img = (n * px + 255) & ~(size_t)255;
+  int rc = ctx->d_plane_io.ensure(b_img + 256);
+  if (rc != PGP_OK) return rc;
+  unsigned char* d_img = ctx->d_plane_io.as<unsigned char>();
+  int* d_n = reinterpret_cast<int*>(d_img + b_img);
+  PGP_HIP(hipMemcpyAsync(d_img, image, n * px, hipMemcpyHostToDevice, st));
+  if ((rc = launch_mask_plane_depth(ctx, d_img, raw16 != 0, rows, cols, K, coeff, nullptr, threshold, d_n, st)) != PGP_OK)
+    return rc;
+  PGP_HIP(hipMemcpyAsync(image, d_img, n * px, hipMemcpyDeviceToHost, st));
+  int cnt = 0;
+  PGP_HIP(hipMemcpyAsync(&cnt, d_n, 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  if (n_masked) *n_masked = cnt;
+  return PGP_OK;
+}
+
+int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, const float K[9], float leaf,
+                     const pgp_plane_options* opt, float coeff[4], int* n_masked) {
+  if (!ctx || rows < 0 || cols < 0 || !K || ((size_t)rows * cols > 0 && !image) || (size_t)rows * cols > ((size_t)1 << 30) ||
+      !(leaf > 0.f) || !std::isfinite(leaf)) {
+    set_error("pgp_remove_table: bad argument");
+    return PGP_EINVAL;
+  }
+  if (!plane_options_ok(opt, "pgp_remove_table")) return PGP_EINVAL;
+  if (n_masked) *n_masked = 0;
+  if (coeff) coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.f;
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  // image | cloud (n x 3) | voxels (n x 3) | back-projection counters + scan scratch | coeff, counts, info
+  const size_t px = raw16 ? 2 : 4, b_img = (n * px + 255) & ~(size_t)255, b_xyz = (n * 12 + 255) & ~(size_t)255;
+  const size_t nb = (n + 255) / 256, b_ctr = ((nb + 1) * 4 + 255) & ~(size_t)255, b_scan = ((nb / 2048 + 4) * 4 + 255) & ~(size_t)255;
+  int rc = ctx->d_plane_io.ensure(b_img + 2 * b_xyz + b_ctr + b_scan + 512);
+  if (rc != PGP_OK) return rc;
+  unsigned char* base = ctx->d_plane_io.as<unsigned char>();
+  void* d_img = base;
+  float* d_cloud = reinterpret_cast<float*>(base + b_img);
+  float* d_vox = reinterpret_cast<float*>(base + b_img + b_xyz);
+  uint32_t* d_ctr = reinterpret_cast<uint32_t*>(base + b_img + 2 * b_xyz);
+  uint32_t* d_scan = reinterpret_cast<uint32_t*>(base + b_img + 2 * b_xyz + b_ctr);
+  unsigned char* tail = base + b_img + 2 * b_xyz + b_ctr + b_scan;
+  float* d_c = reinterpret_cast<float*>(tail);
+  int* d_cnt = reinterpret_cast<int*>(tail + 64);   // [0] inliers, [1] masked
+  pgp_plane_info* d_i = reinterpret_cast<pgp_plane_info*>(tail + 128);
+  PGP_HIP(hipMemcpyAsync(d_img, image, n * px, hipMemcpyHostToDevice, st));
+  int n_pts = 0, n_vox = 0;
+  if ((rc = launch_backproject(ctx, d_img, raw16 != 0, nullptr, rows, cols, K, 0.1, 2.0, d_ctr, d_scan, d_cloud, (int)n, &n_pts,
+                               st)) != PGP_OK)
+    return rc;
+  if ((rc = launch_voxel_grid(ctx, d_cloud, n_pts, leaf, d_vox, (int)n, &n_vox, st)) != PGP_OK) return rc;
+  if (n_vox < 3) {   // nothing to fit: the image stays as it is
+    PGP_HIP(hipStreamSynchronize(st));
+    return PGP_OK;
+  }
+  if ((rc = launch_fit_plane(ctx, d_vox, n_vox, opt, nullptr, 0, d_c, nullptr, d_cnt, d_i, st)) != PGP_OK) return rc;
+  if ((rc = launch_mask_plane_depth(ctx, d_img, raw16 != 0, rows, cols, K, nullptr, d_c, shortest_decimal(opt->threshold),
+                                    d_cnt + 1, st)) != PGP_OK)
+    return rc;
+  PGP_HIP(hipMemcpyAsync(image, d_img, n * px, hipMemcpyDeviceToHost, st));
+  float h_c[4];
+  int h_cnt[2];
+  PGP_HIP(hipMemcpyAsync(h_c, d_c, 16, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  if (coeff) std::memcpy(coeff, h_c, 16);
+  if (n_masked) *n_masked = h_cnt[1];
   return PGP_OK;
 }
 

@@ -56,6 +56,19 @@ __host__ __device__ inline uint32_t block_hash(const GridDesc& g, uint32_t key) 
   return (key * 2654435761u) >> g.tab_shift;
 }
 
+// The counter-based splitmix64 draw (pgp_api.hip sample_quads_kernel, plane.hip plane_candidates): variate i of a
+// stream is splitmix64's finaliser of state + (i + 1) * gamma, 31 bits, as rand() gives.
+__host__ __device__ inline unsigned long long sample_state(unsigned long long seed, int base) {
+  return (seed ^ 0xD1B54A32D192ED03ull) + (unsigned long long)(base + 1) * 0xBF58476D1CE4E5B9ull;
+}
+__host__ __device__ inline unsigned int sample_variate(unsigned long long state, int i) {
+  unsigned long long z = state + (unsigned long long)(i + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (unsigned int)(z >> 33);
+}
+
 // A growable device buffer (never shrinks; freed with the context).
 struct DevBuf {
   void* p = nullptr;
@@ -159,6 +172,7 @@ struct pgp_ctx {
 
   pgp::DevBuf d_pre_ws, d_vg_ws, d_pre_io;   // preprocess.hip: bbox partials, voxel-grid workspace, host-API staging
   pgp::DevBuf d_mls_ws;                      // mls.hip: sort keys, sorted cloud, per-point results
+  pgp::DevBuf d_plane_ws, d_plane_io;        // plane.hip: candidate / partial workspace; host-API staging
   bool hd_attr_set = false;
 
   pgp::DevBuf d_depth;   // depth-cost staging: observed | rendered[n] | counts
@@ -525,6 +539,14 @@ int launch_pose_error(pgp_ctx* ctx, const float* d_test, const float* d_gt, int 
 int launch_backproject(pgp_ctx* ctx, const void* d_img, bool raw16, const unsigned char* d_mask, int rows,
                        int cols, const float K[9], double z_min, double z_max, uint32_t* d_ctr,
                        uint32_t* d_scan_tmp, float* d_xyz, int cap, int* n_host, hipStream_t st);
+
+// plane.hip
+int plane_max_candidates();
+int launch_fit_plane(pgp_ctx* ctx, const float* d_xyz, int n, const pgp_plane_options* opt, const int* d_samples,
+                     int n_samples, float* d_coeff, unsigned char* d_inliers, int* d_n_inliers, pgp_plane_info* d_info,
+                     hipStream_t st);
+int launch_mask_plane_depth(pgp_ctx* ctx, void* d_img, bool raw16, int rows, int cols, const float K[9],
+                            const float* coeff, const float* d_coeff, double thr, int* d_n_masked, hipStream_t st);
 
 // rigid_fit.hip
 int launch_rigid(pgp_ctx* ctx, const int* d_base_ids, const int* d_quad_ids, int n, const float cP[3],

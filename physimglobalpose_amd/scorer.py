@@ -461,6 +461,109 @@ class LcpScorer:
             C.c_double(z_min), C.c_double(z_max), _fp(out), rows * cols, C.byref(n)))
         return out[: n.value].copy()
 
+    @staticmethod
+    def plane_options(threshold=0.005, max_iterations=1000, probability=0.99, stop="adaptive", optimize=True, seed=0):
+        """pgp_plane_options; stop: "adaptive" (PCL's MSAC stop rule) or "all" (the minimum over every candidate)."""
+        if stop not in ("adaptive", "all"):
+            raise ValueError(f"stop must be 'adaptive' or 'all', not {stop!r}")
+        return _lib.PlaneOptions(float(threshold), int(max_iterations), float(probability),
+                                 _lib.PGP_PLANE_STOP_ADAPTIVE if stop == "adaptive" else _lib.PGP_PLANE_STOP_ALL,
+                                 int(bool(optimize)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @staticmethod
+    def plane_info(info):
+        """pgp_plane_info (a ctypes struct, or its bytes as a numpy / torch uint8 array) -> dict."""
+        if not isinstance(info, _lib.PlaneInfo):
+            b = bytes(np.asarray(info.cpu() if hasattr(info, "cpu") else info, np.uint8).tobytes())
+            info = _lib.PlaneInfo.from_buffer_copy(b[: C.sizeof(_lib.PlaneInfo)])
+        return {"status": info.status, "chosen": info.chosen, "n_evaluated": info.n_evaluated, "n_valid": info.n_valid,
+                "n_candidates": info.n_candidates, "sampled_inliers": info.sampled_inliers, "penalty": info.penalty,
+                "sampled": np.array(info.sampled[:], np.float32)}
+
+    def fit_plane(self, xyz, threshold=0.005, max_iterations=1000, probability=0.99, stop="adaptive", optimize=True,
+                  seed=0, samples=None):
+        """pcl::SACSegmentation (SACMODEL_PLANE, SAC_MSAC; SceneCfg.cpp:55-64) -> (coeff (4,) float32 of
+        a x + b y + c z + d = 0, inlier mask (n,) bool, info dict).  samples: (m, 3) point indices replacing the draw."""
+        xyz = _f32(xyz, 3)
+        n = len(xyz)
+        opt = self.plane_options(threshold, max_iterations, probability, stop, optimize, seed)
+        smp = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+        coeff = np.zeros(4, np.float32)
+        mask = np.zeros(max(n, 1), np.uint8)
+        cnt = C.c_int(0)
+        info = _lib.PlaneInfo()
+        _lib.check(self._lib.pgp_fit_plane(self._h, _fp(xyz), n, C.byref(opt), None if smp is None else smp.ctypes.data_as(_i),
+                                           0 if smp is None else len(smp), _fp(coeff), mask.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                           C.byref(cnt), C.byref(info)))
+        out = self.plane_info(info)
+        out["n_inliers"] = cnt.value
+        return coeff, mask[:n].astype(bool), out
+
+    def fit_plane_device(self, d_xyz, n=None, threshold=0.005, max_iterations=1000, probability=0.99, stop="adaptive",
+                         optimize=True, seed=0, d_samples=None, d_coeff=None, d_inliers=None, d_n_inliers=None, d_info=None,
+                         stream=None):
+        """pgp_fit_plane_device on torch tensors, queued on `stream` (default: the current stream) with no host
+        synchronisation.  Returns (d_coeff (4,) float32, d_inliers (n,) uint8, d_n_inliers (1,) int32, d_info uint8 bytes
+        of pgp_plane_info: LcpScorer.plane_info(d_info) reads it)."""
+        import torch
+        n = int(d_xyz.shape[0]) if n is None else int(n)
+        dev = d_xyz.device
+        d_coeff = torch.empty(4, dtype=torch.float32, device=dev) if d_coeff is None else d_coeff
+        d_inliers = torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if d_inliers is None else d_inliers
+        d_n_inliers = torch.empty(1, dtype=torch.int32, device=dev) if d_n_inliers is None else d_n_inliers
+        d_info = torch.empty(C.sizeof(_lib.PlaneInfo), dtype=torch.uint8, device=dev) if d_info is None else d_info
+        opt = self.plane_options(threshold, max_iterations, probability, stop, optimize, seed)
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_fit_plane_device(self._h, p(d_xyz), n, C.byref(opt), p(d_samples),
+                                                  0 if d_samples is None else int(d_samples.shape[0]), p(d_coeff), p(d_inliers),
+                                                  p(d_n_inliers), p(d_info), C.c_void_p(st)))
+        return d_coeff, d_inliers, d_n_inliers, d_info
+
+    def mask_plane_depth(self, image, K, coeff, threshold=0.005):
+        """SceneCfg.cpp:69-80: a copy of image (uint16 raw or float32 metres) with the pixels within `threshold` of the
+        plane zeroed -> (image, number zeroed)."""
+        image = np.array(image, copy=True, order="C")
+        assert image.dtype in (np.uint16, np.float32) and image.ndim == 2
+        rows, cols = image.shape
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        c4 = np.ascontiguousarray(coeff, np.float32).reshape(4)
+        m = C.c_int(0)
+        _lib.check(self._lib.pgp_mask_plane_depth(self._h, image.ctypes.data_as(C.c_void_p), int(image.dtype == np.uint16),
+                                                  rows, cols, _fp(K9), _fp(c4), C.c_double(threshold), C.byref(m)))
+        return image, m.value
+
+    def mask_plane_depth_device(self, d_image, K, coeff, threshold=0.005, d_n_masked=None, stream=None):
+        """In place on a device image (torch uint16 / int16 raw or float32), queued on `stream` without a host
+        synchronisation; d_n_masked (1,) int32 receives the count.  Returns d_n_masked."""
+        import torch
+        rows, cols = d_image.shape
+        assert d_image.is_cuda and d_image.is_contiguous() and d_image.dtype in (torch.uint16, torch.int16, torch.float32)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        c4 = np.ascontiguousarray(coeff.cpu() if hasattr(coeff, "cpu") else coeff, np.float32).reshape(4)
+        d_n_masked = torch.empty(1, dtype=torch.int32, device=d_image.device) if d_n_masked is None else d_n_masked
+        st = (stream or torch.cuda.current_stream(d_image.device)).cuda_stream
+        _lib.check(self._lib.pgp_mask_plane_depth_device(self._h, C.c_void_p(d_image.data_ptr()),
+                                                         int(d_image.dtype != torch.float32), rows, cols, _fp(K9), _fp(c4),
+                                                         C.c_double(threshold), C.c_void_p(d_n_masked.data_ptr()),
+                                                         C.c_void_p(st)))
+        return d_n_masked
+
+    def remove_table(self, image, K, leaf=0.005, threshold=0.005, max_iterations=1000, probability=0.99, stop="adaptive",
+                     optimize=True, seed=0):
+        """SceneCfg::removeTable in one call (back-projection, voxel grid, plane fit, depth mask on the device) ->
+        (masked copy of image, coeff (4,), number of pixels zeroed)."""
+        image = np.array(image, copy=True, order="C")
+        assert image.dtype in (np.uint16, np.float32) and image.ndim == 2
+        rows, cols = image.shape
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        opt = self.plane_options(threshold, max_iterations, probability, stop, optimize, seed)
+        coeff = np.zeros(4, np.float32)
+        m = C.c_int(0)
+        _lib.check(self._lib.pgp_remove_table(self._h, image.ctypes.data_as(C.c_void_p), int(image.dtype == np.uint16), rows,
+                                              cols, _fp(K9), C.c_float(leaf), C.byref(opt), _fp(coeff), C.byref(m)))
+        return image, coeff, m.value
+
     def depth_cost(self, observed, rendered, threshold=0.01):
         """observed (rows,cols) f32, rendered (n,rows,cols) f32 -> (render_score (n,), counts (n,3))."""
         obs = np.ascontiguousarray(observed, np.float32)

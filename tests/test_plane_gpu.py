@@ -1,0 +1,438 @@
+"""Table-plane removal on the device (pgp_fit_plane, pgp_mask_plane_depth, pgp_remove_table): the batched MSAC plane fit
+and the depth mask of SceneCfg::removeTable, against an independent numpy restatement of the contract in include/pgp.h --
+float32 coefficients and distances in the documented order, float64 penalties, PCL's sequential stop rule, a float64
+PCA refit and the SceneCfg.cpp:69-80 pixel loop.  PCL itself is not on any machine here: its bits are not pinned."""
+import math
+import os
+
+import numpy as np
+import pytest
+
+from physimglobalpose_amd import LcpScorer
+from physimglobalpose_amd._lib import PgpError
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+F = np.float32
+
+# ---- the restatement ------------------------------------------------------------------------------------------------
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _variates(seed, slots, k):
+    """31-bit variate k of the splitmix64 streams of `slots` (include/pgp.h: keyed by (seed, slot))."""
+    s = np.asarray(slots, np.uint64)
+    with np.errstate(over="ignore"):
+        st = np.uint64((seed ^ 0xD1B54A32D192ED03) & _M64) + (s + np.uint64(1)) * np.uint64(0xBF58476D1CE4E5B9)
+        z = st + np.uint64(k + 1) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    return (z >> np.uint64(33)).astype(np.int64)
+
+
+def plane_coeffs(xyz, triples):
+    """float32 coefficients of the planes through the triples, in the header's order; (coeff (m, 4), valid (m,))."""
+    p0, p1, p2 = (xyz[triples[:, k]].astype(F) for k in range(3))
+    u, v = p1 - p0, p2 - p0
+    nx = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+    ny = u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2]
+    nz = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ln = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        ok = ~((nx == 0) & (ny == 0) & (nz == 0)) & (ln > 0) & np.isfinite(ln)
+        a, b, c = nx / ln, ny / ln, nz / ln
+        d = -((a * p0[:, 0] + b * p0[:, 1]) + c * p0[:, 2])
+    q = np.stack([a, b, c, d], 1).astype(F)
+    q[~ok] = 0
+    return q, ok
+
+
+def draw_triples(xyz, m, seed):
+    """The device's draw: slot i tries attempts a = 0..63 (variates 3a..3a+2 % n) until three distinct indices give a
+    non-zero cross product.  -> (triples (m, 3), coeff (m, 4), valid (m,))."""
+    n = len(xyz)
+    tri = np.zeros((m, 3), np.int64)
+    q = np.zeros((m, 4), F)
+    ok = np.zeros(m, bool)
+    todo = np.arange(m)
+    for a in range(64):
+        if len(todo) == 0:
+            break
+        t = np.stack([_variates(seed, todo, 3 * a + k) % n for k in range(3)], 1)
+        dist = (t[:, 0] != t[:, 1]) & (t[:, 0] != t[:, 2]) & (t[:, 1] != t[:, 2])
+        qq, good = plane_coeffs(xyz, t)
+        good &= dist
+        tri[todo[good]], q[todo[good]], ok[todo[good]] = t[good], qq[good], True
+        todo = todo[~good]
+    return tri, q, ok
+
+
+def plane_dist(xyz, q):
+    """float32 |((a x + b y) + c z) + d| for q (4,) or (m, 4) -> (n,) or (m, n)."""
+    q = np.atleast_2d(np.asarray(q, F))
+    x, y, z = (xyz[:, k].astype(F)[None, :] for k in range(3))
+    d = np.abs(((q[:, 0:1] * x + q[:, 1:2] * y) + q[:, 2:3] * z) + q[:, 3:4])
+    return d
+
+
+def score(xyz, q, thr, block=32):
+    """float64 MSAC penalties and dist <= thr counts of every candidate."""
+    thr = F(thr)
+    pen, cnt = np.zeros(len(q)), np.zeros(len(q), np.int64)
+    for s in range(0, len(q), block):
+        d = plane_dist(xyz, q[s:s + block])
+        pen[s:s + block] = np.minimum(d, thr).astype(np.float64).sum(1)
+        cnt[s:s + block] = (d <= thr).sum(1)
+    return pen, cnt
+
+
+def stop_rule(pen, cnt, valid, n, max_iterations=1000, probability=0.99, stop="adaptive"):
+    """PCL's MSAC loop (SampleConsensus MSAC::computeModel) over the valid candidates in order -> (chosen, n_evaluated)."""
+    if stop == "all":
+        idx = np.flatnonzero(valid)
+        if len(idx) == 0:
+            return -1, 0
+        return int(idx[np.argmin(pen[idx])]), len(idx)   # argmin: the first of equal minima
+    log_p = math.log(1.0 - probability)
+    best, k, it, chosen = math.inf, 1.0, 0, -1
+    for j in range(len(pen)):
+        if not valid[j]:
+            continue   # a skipped draw does not count as an iteration
+        if not it < k:
+            break
+        if pen[j] < best:
+            best, chosen = pen[j], j
+            w = cnt[j] / n
+            p_no = 1.0 - w ** 3.0
+            p_no = min(max(p_no, np.finfo(float).eps), 1.0 - np.finfo(float).eps)
+            k = log_p / math.log(p_no)
+        it += 1
+        if it > max_iterations:
+            break
+    return chosen, it
+
+
+def pca_plane(pts):
+    """float64 plane through the centroid with the normal of the smallest eigenvalue of the covariance."""
+    p = pts.astype(np.float64)
+    c = p.mean(0)
+    w, v = np.linalg.eigh((p - c).T @ (p - c))
+    nrm = v[:, 0]
+    return np.array([*nrm, -nrm @ c])
+
+
+def same_plane(q, ref, tol):
+    """q and ref are the same plane up to the sign of the normal, within tol per coefficient."""
+    q, ref = np.asarray(q, np.float64), np.asarray(ref, np.float64)
+    s = 1.0 if q[:3] @ ref[:3] >= 0 else -1.0
+    return np.max(np.abs(s * q - ref)) <= tol
+
+
+def angle_deg(a, b):
+    a, b = np.asarray(a[:3], np.float64), np.asarray(b[:3], np.float64)
+    c = abs(a @ b) / (np.linalg.norm(a) * np.linalg.norm(b))
+    return math.degrees(math.acos(min(1.0, c)))
+
+
+def decode_raw(raw):
+    s = ((raw.astype(np.uint32) << 13) | (raw.astype(np.uint32) >> 3)) & 0xFFFF
+    return s.astype(F) / F(10000.0)
+
+
+def mask_restated(depth, K, q, thr=0.005):
+    """SceneCfg.cpp:69-80: the pixels the reference zeroes (bool (rows, cols))."""
+    rows, cols = depth.shape
+    u, v = np.meshgrid(np.arange(rows, dtype=F), np.arange(cols, dtype=F), indexing="ij")
+    fx, fy, cx, cy = (F(K.reshape(9)[i]) for i in (0, 4, 2, 5))
+    x = ((v - cx) * depth) / fx
+    y = ((u - cy) * depth) / fy
+    a, b, c, d = (np.float64(t) for t in np.asarray(q, F))
+    dist = np.abs(((a * x.astype(np.float64) + b * y.astype(np.float64)) + c * depth.astype(np.float64)) + d)
+    return dist < thr
+
+
+# ---- scenes -----------------------------------------------------------------------------------------------------------
+def table_scene(n=50000, seed=0, noise=0.001):
+    """A tilted 0.8 x 0.6 m plane patch (1 mm noise) under three solids, plus uniform outliers: (xyz float32, (n, d))."""
+    rng = np.random.default_rng(seed)
+    from physimglobalpose_amd import synth
+    nrm = synth._unit(np.array([0.08, -0.12, 1.0]))
+    e1 = synth._unit(np.cross(nrm, [1.0, 0.0, 0.0]))
+    e2 = np.cross(nrm, e1)
+    origin = np.array([0.02, -0.01, 0.75])
+    n_pl, n_out = int(0.55 * n), int(0.10 * n)
+    n_obj = n - n_pl - n_out
+    uv = rng.uniform(-0.5, 0.5, (n_pl, 2)) * [0.8, 0.6]
+    pl = origin + uv[:, :1] * e1 + uv[:, 1:] * e2 + rng.normal(0, noise, (n_pl, 1)) * nrm
+    objs = []
+    for k, (cu, cv) in enumerate([(-0.2, 0.1), (0.15, -0.1), (0.2, 0.15)]):
+        m = n_obj // 3 + (n_obj % 3 if k == 0 else 0)
+        if k == 2:
+            p, _ = synth._sample_sphere(rng, m, 0.05, (0, 0, 0.06))
+        else:
+            p, _ = synth._sample_box(rng, m, (0.12, 0.08, 0.10), (0, 0, 0.055))
+        objs.append(origin + cu * e1 + cv * e2 + p[:, :1] * e1 + p[:, 1:2] * e2 + p[:, 2:] * nrm)
+    out = rng.uniform([-0.45, -0.35, 0.45], [0.45, 0.35, 1.05], (n_out, 3))
+    xyz = np.concatenate([pl, *objs, out])[rng.permutation(n)].astype(F)
+    return xyz, (nrm, -nrm @ origin)
+
+
+@pytest.fixture(scope="module")
+def sc():
+    s = LcpScorer()
+    yield s
+    s.close()
+
+
+@pytest.fixture(scope="module")
+def scene():
+    return table_scene()
+
+
+# ---- 1. explicit samples, candidate by candidate -------------------------------------------------------------------
+def test_explicit_samples_candidate_by_candidate(sc):
+    xyz, _ = table_scene(20000, seed=3)
+    line = np.array([[0.1, 0.2, 0.5], [0.2, 0.2, 0.5], [0.4, 0.2, 0.5]], F)   # exactly collinear in float
+    xyz = np.concatenate([xyz, line])
+    n = len(xyz)
+    rng = np.random.default_rng(11)
+    tri = rng.integers(0, n - 3, (1000, 3))
+    bad = [5, 17, 400, 401, 999]
+    tri[5] = [n - 3, n - 2, n - 1]
+    tri[17] = [n - 1, n - 3, n - 2]
+    tri[400] = [7, 7, 9]            # a repeated point: u = 0
+    tri[401] = [12, 30, 12]
+    tri[999] = [n - 2, n - 1, n - 3]
+    q_ref, ok = plane_coeffs(xyz, tri)
+    assert not ok[bad].any() and ok.sum() == 1000 - len(bad)
+    pen_ref, cnt_ref = score(xyz, q_ref, 0.005)
+    # every candidate alone: its coefficients, inlier count and penalty
+    for j in range(1000):
+        q, _, inf = sc.fit_plane(xyz, samples=tri[j:j + 1], optimize=False)
+        if not ok[j]:
+            assert inf["chosen"] == -1 and inf["n_valid"] == 0 and inf["n_evaluated"] == 0 and not q.any()
+            continue
+        assert inf["chosen"] == 0 and inf["n_evaluated"] == 1
+        assert np.array_equal(inf["sampled"].view(np.uint32), q_ref[j].view(np.uint32)), j
+        assert np.array_equal(q.view(np.uint32), q_ref[j].view(np.uint32)), j
+        assert inf["sampled_inliers"] == cnt_ref[j], j
+        assert abs(inf["penalty"] - pen_ref[j]) <= 1e-12 * pen_ref[j], j
+    # the whole list under both stop rules
+    for stop in ("adaptive", "all"):
+        ch, ev = stop_rule(pen_ref, cnt_ref, ok, n, stop=stop)
+        q, mask, inf = sc.fit_plane(xyz, samples=tri, stop=stop, optimize=False)
+        assert inf["chosen"] == ch and inf["n_evaluated"] == ev, (stop, inf, ch, ev)
+        assert inf["n_valid"] == 1000 - len(bad) and inf["n_candidates"] == 1000 and inf["status"] == 0
+        assert np.array_equal(q.view(np.uint32), q_ref[ch].view(np.uint32))
+        assert np.array_equal(mask, plane_dist(xyz, q)[0] < F(0.005)) and inf["n_inliers"] == mask.sum()
+
+
+# ---- 2. stop rule -----------------------------------------------------------------------------------------------------
+def _stop_scene():
+    xyz, (nrm, d0) = table_scene(20000, seed=5)
+    d = plane_dist(xyz, np.r_[nrm, d0].astype(F))[0]
+    on = np.flatnonzero(d < 0.0005)
+    off = np.flatnonzero(d > 0.1)
+    return xyz, on, off
+
+
+def test_stop_rule_records_at_known_positions(sc):
+    xyz, on, off = _stop_scene()
+    n = len(xyz)
+    rng = np.random.default_rng(2)
+    bad = off[rng.integers(0, len(off), (200, 3))]      # far off the table: high penalties, small w, large k
+    good = on[rng.integers(0, len(on), (3, 3))]         # on the table
+    tri = bad.copy()
+    tri[3] = [0, 0, 1]                                  # invalid: never counted
+    tri[10] = good[0]                                   # a record with w ~ 0.55 at list position 10
+    q, ok = plane_coeffs(xyz, tri)
+    pen, cnt = score(xyz, q, 0.005)
+    assert pen[10] < pen[ok].min() + 1e-9 and pen[10] == pen[ok].min()
+    ch, ev = stop_rule(pen, cnt, ok, n)
+    # by hand: ranks skip slot 3, so slot 10 is the 10th evaluated; k from its inlier fraction
+    w = cnt[10] / n
+    k = math.log(0.01) / math.log(1 - w ** 3)
+    assert ch == 10 and ev == max(10, math.ceil(k))
+    _, _, inf = sc.fit_plane(xyz, samples=tri, optimize=False)
+    assert (inf["chosen"], inf["n_evaluated"]) == (ch, ev)
+    # a better record before the stop moves it; one after the stop does not count
+    tri2 = tri.copy()
+    tri2[ev - 2] = good[1]
+    tri2[ev + 5] = good[2]
+    q2, ok2 = plane_coeffs(xyz, tri2)
+    pen2, cnt2 = score(xyz, q2, 0.005)
+    ch2, ev2 = stop_rule(pen2, cnt2, ok2, n)
+    _, _, inf2 = sc.fit_plane(xyz, samples=tri2, optimize=False)
+    assert (inf2["chosen"], inf2["n_evaluated"]) == (ch2, ev2)
+    assert ev2 < ev + 5 and ch2 == (ev - 2 if pen2[ev - 2] < pen2[10] else 10)
+    # ALL: the global minimum, the lowest index of equal minima (the same triple twice gives the same penalty)
+    tri3 = bad.copy()
+    tri3[150] = good[0]
+    tri3[40] = good[0]
+    q3, ok3 = plane_coeffs(xyz, tri3)
+    pen3, cnt3 = score(xyz, q3, 0.005)
+    _, _, inf3 = sc.fit_plane(xyz, samples=tri3, stop="all", optimize=False)
+    assert inf3["chosen"] == 40 == stop_rule(pen3, cnt3, ok3, n, stop="all")[0]
+    assert inf3["n_evaluated"] == ok3.sum()
+    # max_iterations: PCL counts the iteration before it tests it, so max_iterations + 1 are evaluated
+    _, _, inf4 = sc.fit_plane(xyz, samples=bad, max_iterations=5, optimize=False)
+    qb, okb = plane_coeffs(xyz, bad)
+    pb, cb = score(xyz, qb, 0.005)
+    assert inf4["n_evaluated"] == 6 == stop_rule(pb, cb, okb, n, max_iterations=5)[1]
+    assert inf4["chosen"] == stop_rule(pb, cb, okb, n, max_iterations=5)[0]
+
+
+# ---- 3. recovery --------------------------------------------------------------------------------------------------
+def _check_recovery(xyz, truth, q, mask):
+    nrm, d0 = truth
+    s = 1.0 if np.asarray(q[:3], np.float64) @ nrm >= 0 else -1.0
+    assert angle_deg(q, nrm) < 0.5
+    assert abs(s * float(q[3]) - d0) < 0.001
+    true_d = np.abs(xyz.astype(np.float64) @ nrm + d0)
+    assert mask[true_d < 0.8 * 0.005].all()
+
+
+def test_recovers_the_table_plane(sc, scene):
+    xyz, truth = scene
+    q, mask, inf = sc.fit_plane(xyz)
+    assert inf["status"] == 0 and inf["n_candidates"] == 1001 and inf["n_valid"] == 1001
+    _check_recovery(xyz, truth, q, mask)
+    assert 0.5 < mask.mean() < 0.7
+
+
+# ---- 4. refit -------------------------------------------------------------------------------------------------------
+def test_refit_is_the_pca_of_the_chosen_inliers(sc, scene):
+    xyz, _ = scene
+    q, mask, inf = sc.fit_plane(xyz, optimize=True)
+    sel = plane_dist(xyz, inf["sampled"])[0] < F(0.005)
+    assert sel.sum() >= 3
+    assert same_plane(q, pca_plane(xyz[sel]), 1e-6)
+    assert np.array_equal(mask, plane_dist(xyz, q)[0] < F(0.005)) and inf["n_inliers"] == mask.sum()
+    # without the refit the sampled plane comes back as it is, with its own strict re-selection
+    q0, mask0, inf0 = sc.fit_plane(xyz, optimize=False)
+    assert np.array_equal(q0, inf["sampled"]) and np.array_equal(mask0, sel)
+
+
+# ---- 5. the real frame --------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def frame():
+    return np.load(os.path.join(GOLD, "test_scene_frame.npz"))
+
+
+def test_real_frame(sc, frame):
+    raw, K = frame["raw"], frame["K"]
+    vox = sc.voxel_grid(sc.backproject_depth(raw, K), 0.005)
+    q, mask, inf = sc.fit_plane(vox)
+    assert mask.mean() >= 0.6
+    tri, qs, ok = draw_triples(vox, 1001, 0)
+    pen, cnt = score(vox, qs, 0.005)
+    ch, ev = stop_rule(pen, cnt, ok, len(vox))
+    assert (inf["chosen"], inf["n_evaluated"]) == (ch, ev)
+    assert np.array_equal(inf["sampled"], qs[ch])
+    best = pca_plane(vox[plane_dist(vox, qs[ch])[0] < F(0.005)])
+    assert angle_deg(q, best) < 2.0
+    depth = decode_raw(raw)
+    for img in (depth, raw):
+        out, nm = sc.mask_plane_depth(img, K, q, 0.005)
+        hit = mask_restated(depth, K, q, 0.005)
+        assert nm == hit.sum() > 0.2 * (depth > 0).sum()
+        assert not out[hit].any()
+        assert np.array_equal(out[~hit].view(np.uint8 if img.dtype == np.uint16 else np.uint32),
+                              img[~hit].view(np.uint8 if img.dtype == np.uint16 else np.uint32))
+
+
+# ---- 6. device and host forms agree -------------------------------------------------------------------------------
+def test_device_forms_and_remove_table(sc, frame, scene):
+    import torch
+    xyz, _ = scene
+    q, mask, inf = sc.fit_plane(xyz)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        d_xyz = torch.from_numpy(xyz).cuda()
+        d_q, d_m, d_n, d_inf = sc.fit_plane_device(d_xyz, stream=s)
+    s.synchronize()
+    assert np.array_equal(d_q.cpu().numpy().view(np.uint32), q.view(np.uint32))
+    assert np.array_equal(d_m.cpu().numpy().astype(bool), mask) and int(d_n.item()) == mask.sum()
+    di = LcpScorer.plane_info(d_inf)
+    assert all(di[k] == inf[k] for k in ("status", "chosen", "n_evaluated", "n_valid", "penalty"))
+    raw, K = frame["raw"], frame["K"]
+    vox = sc.voxel_grid(sc.backproject_depth(raw, K), 0.005)
+    qv, _, _ = sc.fit_plane(vox)
+    for img in (decode_raw(raw), raw):
+        ref, nref = sc.mask_plane_depth(img, K, qv, 0.005)
+        with torch.cuda.stream(s):
+            d_img = torch.from_numpy(img.view(np.int16) if img.dtype == np.uint16 else img).cuda()
+            d_cnt = sc.mask_plane_depth_device(d_img, K, qv, 0.005, stream=s)
+        s.synchronize()
+        got = d_img.cpu().numpy()
+        assert np.array_equal(got.view(np.uint8), ref.view(np.uint8)) and int(d_cnt.item()) == nref
+        # removeTable in one call == back-projection -> voxel grid -> fit -> mask, bit for bit
+        out, qt, nt = sc.remove_table(img, K)
+        assert np.array_equal(qt.view(np.uint32), qv.view(np.uint32))
+        assert np.array_equal(out.view(np.uint8), ref.view(np.uint8)) and nt == nref
+
+
+# ---- 7. determinism -------------------------------------------------------------------------------------------------
+def test_determinism_across_calls_and_contexts(sc, scene):
+    xyz, truth = scene
+    a = sc.fit_plane(xyz, seed=7)
+    b = sc.fit_plane(xyz, seed=7)
+    other = LcpScorer()
+    try:
+        c = other.fit_plane(xyz, seed=7)
+    finally:
+        other.close()
+    for r in (b, c):
+        assert np.array_equal(a[0].view(np.uint32), r[0].view(np.uint32)) and np.array_equal(a[1], r[1])
+        assert a[2]["penalty"] == r[2]["penalty"] and a[2]["chosen"] == r[2]["chosen"]
+    d = sc.fit_plane(xyz, seed=12345)
+    assert d[2]["chosen"] != a[2]["chosen"] or not np.array_equal(d[2]["sampled"], a[2]["sampled"])
+    _check_recovery(xyz, truth, d[0], d[1])
+
+
+# ---- 8. edges -----------------------------------------------------------------------------------------------------
+def test_edges(sc, scene):
+    xyz, _ = scene
+    for bad in (xyz[:2], xyz[:0]):
+        with pytest.raises(PgpError, match="-1"):
+            sc.fit_plane(bad)
+    nan = xyz[:100].copy()
+    nan[37, 1] = np.nan
+    with pytest.raises(PgpError, match="-1"):
+        sc.fit_plane(nan)
+    for thr in (0.0, -0.01):
+        with pytest.raises(PgpError, match="-1"):
+            sc.fit_plane(xyz[:100], threshold=thr)
+    with pytest.raises(PgpError, match="-1"):
+        sc.fit_plane(xyz[:100], samples=[[0, 1, 100]])
+    line = np.stack([np.linspace(-1, 1, 500), np.full(500, 0.25), np.full(500, 0.5)], 1).astype(F)
+    q, mask, inf = sc.fit_plane(line)
+    assert inf["status"] == 0 and inf["n_inliers"] == 0 and not mask.any() and not q.any()
+    assert inf["chosen"] == -1 and inf["n_valid"] == 0 and inf["n_evaluated"] == 0
+    q1, m1, i1 = sc.fit_plane(xyz, max_iterations=1)
+    assert i1["n_candidates"] == 2 and 1 <= i1["n_evaluated"] <= 2 and m1.sum() == i1["n_inliers"] > 0
+
+
+def test_full_frame_cloud(sc):
+    """A full 480 x 640 back-projected cloud (307 200 points), 1000 candidates: the restatement's choice."""
+    rows, cols = 480, 640
+    K = np.array([[615.0, 0, 320.0], [0, 615.0, 240.0], [0, 0, 1]], F)
+    u, v = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    rng = np.random.default_rng(9)
+    # a table seen from above at an angle, with two boxes standing on it
+    ray = np.stack([(v - 320.0) / 615.0, (u - 240.0) / 615.0, np.ones_like(u, float)], -1)
+    nrm = np.array([0.0, -0.5, -0.866])
+    depth = (-0.9 / (ray @ nrm)).astype(F)
+    depth[100:180, 200:300] -= F(0.08)
+    depth[300:360, 400:520] -= F(0.05)
+    depth += rng.normal(0, 0.001, depth.shape).astype(F)
+    xyz = sc.backproject_depth(depth, K, z_min=0.0, z_max=10.0)
+    assert len(xyz) == rows * cols
+    for stop in ("adaptive", "all"):
+        q, mask, inf = sc.fit_plane(xyz, stop=stop)
+        tri, qs, ok = draw_triples(xyz, 1001, 0)
+        pen, cnt = score(xyz, qs, 0.005)
+        assert (inf["chosen"], inf["n_evaluated"]) == stop_rule(pen, cnt, ok, len(xyz), stop=stop)
+        assert abs(inf["penalty"] - pen[inf["chosen"]]) <= 1e-12 * pen[inf["chosen"]]
+        assert mask.mean() > 0.8
