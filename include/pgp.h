@@ -737,6 +737,71 @@ int pgp_cluster_poses_device(pgp_ctx* ctx, const float* d_T, const float* d_scor
 int pgp_pose_error(pgp_ctx* ctx, const float* test, const float* gt, int n, const float sym_deg[3],
                    float* rot_err_deg, float* trans_err);
 
+/* ---- PPF Hough voting: the hypotheses of the node's PPF_HOUGH mode ---------------------------------------------
+ * SceneCfg::generateHypothesis with hypoGenMode "PPF_HOUGH" (PPE/data_layer/SceneCfg.cpp:376-402) builds a
+ * pose_candidates::PPFVoting whose generate (PPE/hypothesis_generation/ObjectPoseCandidateSet.cpp:76-117) filters and
+ * orients the segment and then leaves the estimator commented out.  The reference has no estimator to match: the
+ * algorithm below is this library's statement of point-pair-feature voting (Drost et al., CVPR 2010), its rules
+ * stated exactly (csrc/ppf_vote.hip) and restated in numpy by tests/_ppf_restate.py.
+ *   table      the one of pgp_set_ppf_map, WITH its pair lists: a pair (a, b) of key k has computePPF(a, b) = k, ids
+ *              into the PPF model; the scene pair (s_r, s_j) is keyed by the same device function (u = s_r - s_j,
+ *              the host-libm angle thresholds, 5 mm distance bins), so m_r = a corresponds to s_r
+ *   T_g(p, n)  the rigid map x -> R_g (x - p) with n^ = n / |n| and, when 1 + n^x > 1e-6,
+ *                R_g = [[n^x, n^y, n^z], [-n^y, 1 - k n^y^2, -k n^y n^z], [-n^z, -k n^y n^z, 1 - k n^z^2]],
+ *                k = 1 / (1 + n^x)  (the rotation about n^ x e_x that sends n^ to +x); else diag(-1, -1, 1)
+ *   alpha      of a pair (r, i): q = R_g(r) (p_i - p_r), alpha = atan2(-q_z, q_y) in [-pi, pi]
+ *   votes      for reference point s_r and every other scene point s_j whose key is in the table, every pair
+ *              (m_r, m_i) of the key's list votes +1 into cell m_r * n_bins + bin, bin = floor(d n_bins / 2 pi)
+ *              (clamped to n_bins - 1) of d = alpha_m - alpha_s wrapped into [0, 2 pi); 32-bit integer counters,
+ *              integer atomics only: the counts do not depend on the order of arrival
+ *   peaks      the maximal cell of each reference point (ties: lowest cell), then up to peaks_per_ref - 1 further
+ *              cells in descending (votes, then ascending cell) order; a cell is kept while votes >= min_votes,
+ *              votes > 0 and (float)votes >= min_vote_fraction * (float)max
+ *   pose       T = T_s(s_r)^-1 R_x(alpha) T_m(m_r) with alpha = (bin + 0.5) 2 pi / n_bins, R_x(a) = rotation by a
+ *              about +x: model frame -> scene frame, 16 floats column-major
+ * Clouds are the centred ones of pgp_center: the scene of pgp_set_scene (with normals) and the PPF model of
+ * pgp_set_ppf_model (the node's pclModelSampled minus centroid_Q, what pgp_set_search_model holds), so the poses are
+ * in the frame pgp_score_lcp expects.  Hypotheses come out in (reference point, peak rank) order.  Unpinned: float
+ * rounding of alpha (its error grows as k = 1 / (1 + n^x) for normals near -x) may move a vote whose angle lies near a
+ * bin edge to the neighbouring bin.
+ * PGP_ESTATE: no scene with normals, no table, a table without pair lists, or no PPF model; PGP_EINVAL: bad options
+ * or a model that does not cover the pair ids of the table.  PGP_PPF_ACC=hbm forces the HBM accumulator path
+ * (checker switch: identical results). */
+typedef struct {
+  int ref_step;             /* reference points are scene points 0, ref_step, 2 ref_step, ...: 5 (>= 1) */
+  int n_bins;               /* alpha bins over [0, 2 pi): 30 (1 .. 360) */
+  int peaks_per_ref;        /* 1 (1 .. 4) */
+  float min_vote_fraction;  /* 0.9 ([0, 1]): of the reference point's maximum, for peaks after the first */
+  int min_votes;            /* 3 (>= 1): no hypothesis below this count */
+} pgp_ppf_options;
+int pgp_ppf_default_options(pgp_ppf_options* opt);
+
+/* The positions and normals the pair ids of the table index (n x 3 each, host pointers; n >= 0).  Computes the model
+ * angle alpha_m of every pair of the table once, kept as long as the table and the model stay. */
+int pgp_set_ppf_model(pgp_ctx* ctx, const float* xyz, const float* nrm, int n);
+
+/* The hypotheses in HBM: d_T [cap][16], d_votes [cap], d_ref [cap] (scene id of s_r, nullable), d_cell [cap]
+ * (m_r * n_bins + bin, nullable), d_n_out: 1 int = the full count (may exceed cap: the list is truncated).  Enqueued on
+ * `stream`, no synchronisation; the workspace (peak slots, HBM accumulators) is kept in the context and grows only
+ * when a call needs more than an earlier one. */
+int pgp_ppf_vote_device(pgp_ctx* ctx, const pgp_ppf_options* opt, float* d_T, int* d_votes, int* d_ref, int* d_cell,
+                        int cap, int* d_n_out, void* stream);
+/* Host pointers, synchronous (ref / cell nullable); *n_out may exceed cap, as in pgp_cluster_poses. */
+int pgp_ppf_vote(pgp_ctx* ctx, const pgp_ppf_options* opt, float* T, int* votes, int* ref, int* cell, int cap,
+                 int* n_out);
+/* What PPFVoting::generate should return, in one call with one synchronisation: the votes, then every hypothesis
+ * scored on the device as pgp_score_lcp(mode, gate_deg) scores it (needs pgp_set_model; the scores equal
+ * pgp_score_lcp's on the returned transforms bit for bit).  T [cap][16], scores [cap], votes [cap] (nullable) =
+ * hypothesisSet in (reference, peak) order, *n_out the full count; best_index (into the list, -1 when no score is
+ * > 0; the rule of pgp_score_lcp), best_score and best_T [16] = bestHypothesis (nullable; best_T is left alone at -1). */
+int pgp_ppf_hypotheses(pgp_ctx* ctx, const pgp_ppf_options* opt, int mode, float gate_deg, float* T, float* scores,
+                       int* votes, int cap, int* n_out, int* best_index, float* best_score, float* best_T);
+/* Debug export for parity tests: the full accumulator of k given reference points (scene ids), acc [k][n_model][n_bins]
+ * int32 (n_model = pgp_set_ppf_model's n).  Host pointers, synchronous. */
+int pgp_ppf_accumulator(pgp_ctx* ctx, const pgp_ppf_options* opt, const int* ref_ids, int k, int* acc);
+/* Debug export: alpha_m of every pair of the table in pair-list order (alpha[n], n = the table's pair count). */
+int pgp_ppf_model_angles(pgp_ctx* ctx, float* alpha, long long n);
+
 /* ---- several GPUs of one node (north_star; SceneCfg.cpp:376-406 and
  * HypothesisSelection.cpp:248-257 are the consumers) -----------------------------------------------
  * A pgp_multi is a group of devices in ONE process: one pgp_ctx, one host thread and one stream per

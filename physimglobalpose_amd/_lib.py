@@ -76,6 +76,11 @@ class PlaneInfo(C.Structure):
                 ("sampled", C.c_float * 4)]
 
 
+class PpfOptions(C.Structure):
+    _fields_ = [("ref_step", C.c_int), ("n_bins", C.c_int), ("peaks_per_ref", C.c_int), ("min_vote_fraction", C.c_float),
+                ("min_votes", C.c_int)]
+
+
 # every symbol include/pgp.h declares: (restype, argtypes)
 SIGNATURES = {
     "pgp_version": (C.c_int, []),
@@ -219,6 +224,15 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "pgp_remove_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_float,
                                    C.POINTER(PlaneOptions), _f, _i]),
+    "pgp_ppf_default_options": (C.c_int, [C.POINTER(PpfOptions)]),
+    "pgp_set_ppf_model": (C.c_int, [C.c_void_p, _f, _f, C.c_int]),
+    "pgp_ppf_vote_device": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_void_p]),
+    "pgp_ppf_vote": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), _f, _i, _i, _i, C.c_int, _i]),
+    "pgp_ppf_hypotheses": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), C.c_int, C.c_float, _f, _f, _i, C.c_int, _i, _i, _f,
+                                     _f]),
+    "pgp_ppf_accumulator": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), _i, C.c_int, _i]),
+    "pgp_ppf_model_angles": (C.c_int, [C.c_void_p, _f, C.c_longlong]),
 }
 
 _lib = None

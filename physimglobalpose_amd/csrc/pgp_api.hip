@@ -210,7 +210,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   if (ctx->h_pin) {
@@ -2916,6 +2916,211 @@ int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, c
   PGP_HIP(hipStreamSynchronize(st));
   if (coeff) std::memcpy(coeff, h_c, 16);
   if (n_masked) *n_masked = h_cnt[1];
+  return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- PPF Hough voting (ppf_vote.hip) ----------------------------------------------------------------------------
+extern "C" {
+
+int pgp_ppf_default_options(pgp_ppf_options* opt) {
+  if (!opt) {
+    set_error("pgp_ppf_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->ref_step = 5;
+  opt->n_bins = 30;
+  opt->peaks_per_ref = 1;
+  opt->min_vote_fraction = 0.9f;
+  opt->min_votes = 3;
+  return PGP_OK;
+}
+
+int pgp_set_ppf_model(pgp_ctx* ctx, const float* xyz, const float* nrm, int n) {
+  if (!ctx || n < 0 || (n > 0 && (!xyz || !nrm))) {
+    set_error("pgp_set_ppf_model: bad argument (n = %d; positions and normals)", n);
+    return PGP_EINVAL;
+  }
+  for (size_t i = 0; i < (size_t)n * 3; ++i)
+    if (!std::isfinite(xyz[i]) || !std::isfinite(nrm[i])) {
+      set_error("pgp_set_ppf_model: point %zu is not finite", i / 3);
+      return PGP_EINVAL;
+    }
+  CtxGuard guard(ctx);
+  PGP_HIP(hipDeviceSynchronize());   // a queued vote may still read the old model
+  ctx->ppf_alpha_ready = false;
+  ctx->ppf_model_n = -1;
+  std::vector<float4> h((size_t)std::max(2 * n, 1));
+  for (int i = 0; i < n; ++i) {
+    h[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f);
+    h[(size_t)n + i] = make_float4(nrm[3 * (size_t)i], nrm[3 * (size_t)i + 1], nrm[3 * (size_t)i + 2], 0.f);
+  }
+  int rc = ctx->d_ppf_model.ensure(h.size() * sizeof(float4));
+  if (rc != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(ctx->d_ppf_model.p, h.data(), h.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+  PGP_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->ppf_model_n = n;
+  return ppf_model_angles(ctx);
+}
+
+int pgp_ppf_vote_device(pgp_ctx* ctx, const pgp_ppf_options* opt, float* d_T, int* d_votes, int* d_ref, int* d_cell,
+                        int cap, int* d_n_out, void* stream) {
+  if (!ctx || cap < 0 || !d_n_out || (cap > 0 && (!d_T || !d_votes))) {
+    set_error("pgp_ppf_vote_device: bad argument");
+    return PGP_EINVAL;
+  }
+  int rc = ppf_vote_check(ctx, opt, "pgp_ppf_vote_device");
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = launch_ppf_vote(ctx, opt, nullptr, 0, nullptr, d_T, d_votes, d_ref, d_cell, cap, d_n_out, 0, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_ppf_vote(pgp_ctx* ctx, const pgp_ppf_options* opt, float* T, int* votes, int* ref, int* cell, int cap, int* n_out) {
+  if (!ctx || cap < 0 || !n_out || (cap > 0 && (!T || !votes))) {
+    set_error("pgp_ppf_vote: bad argument");
+    return PGP_EINVAL;
+  }
+  int rc = ppf_vote_check(ctx, opt, "pgp_ppf_vote");
+  if (rc != PGP_OK) return rc;
+  *n_out = 0;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const int m = std::min(cap, ppf_slots(ctx, opt));   // no more hypotheses than slots
+  const size_t b_T = ((size_t)m * 64 + 255) & ~(size_t)255, b_i = ((size_t)m * 4 + 255) & ~(size_t)255;
+  if ((rc = ctx->d_ppf_io.ensure(b_T + 3 * b_i + 256)) != PGP_OK) return rc;
+  unsigned char* base = ctx->d_ppf_io.as<unsigned char>();
+  float* d_T = reinterpret_cast<float*>(base);
+  int* d_v = reinterpret_cast<int*>(base + b_T);
+  int* d_r = reinterpret_cast<int*>(base + b_T + b_i);
+  int* d_c = reinterpret_cast<int*>(base + b_T + 2 * b_i);
+  int* d_n = reinterpret_cast<int*>(base + b_T + 3 * b_i);
+  if ((rc = launch_ppf_vote(ctx, opt, nullptr, 0, nullptr, d_T, d_v, d_r, d_c, m, d_n, 0, st)) != PGP_OK) return rc;
+  int n = 0;
+  PGP_HIP(hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  const int k = std::min(n, m);
+  if (k > 0) {
+    PGP_HIP(hipMemcpyAsync(T, d_T, (size_t)k * 64, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipMemcpyAsync(votes, d_v, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    if (ref) PGP_HIP(hipMemcpyAsync(ref, d_r, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    if (cell) PGP_HIP(hipMemcpyAsync(cell, d_c, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipStreamSynchronize(st));
+  }
+  *n_out = n;
+  return PGP_OK;
+}
+
+int pgp_ppf_hypotheses(pgp_ctx* ctx, const pgp_ppf_options* opt, int mode, float gate_deg, float* T, float* scores,
+                       int* votes, int cap, int* n_out, int* best_index, float* best_score, float* best_T) {
+  if (!ctx || cap < 0 || !n_out || (cap > 0 && (!T || !scores)) || (mode != PGP_MODE_PLAIN && mode != PGP_MODE_WEIGHTED)) {
+    set_error("pgp_ppf_hypotheses: bad argument");
+    return PGP_EINVAL;
+  }
+  int rc = ppf_vote_check(ctx, opt, "pgp_ppf_hypotheses");
+  if (rc != PGP_OK) return rc;
+  *n_out = 0;
+  if (best_index) *best_index = -1;
+  if (best_score) *best_score = 0.f;
+  CtxGuard guard(ctx);
+  const int n_slots = ppf_slots(ctx, opt);
+  if (n_slots == 0) return PGP_OK;
+  if ((rc = reserve_impl(ctx, n_slots)) != PGP_OK) return rc;
+  hipStream_t st = ctx->stream;
+  // every slot is scored: the list, then NaN transforms (score 0) up to the slot count -- the host never needs the count
+  // before the scoring launch, so the call synchronises once
+  const size_t b_T = ((size_t)n_slots * 64 + 255) & ~(size_t)255, b_i = ((size_t)n_slots * 4 + 255) & ~(size_t)255;
+  if ((rc = ctx->d_ppf_io.ensure(b_T + 2 * b_i + 256)) != PGP_OK) return rc;
+  unsigned char* base = ctx->d_ppf_io.as<unsigned char>();
+  float* d_T = reinterpret_cast<float*>(base);
+  int* d_v = reinterpret_cast<int*>(base + b_T);
+  float* d_s = reinterpret_cast<float*>(base + b_T + b_i);
+  int* d_tail = reinterpret_cast<int*>(base + b_T + 2 * b_i);   // [0] count, [2..3] best {index, score bits}
+  if ((rc = launch_ppf_vote(ctx, opt, nullptr, 0, nullptr, d_T, d_v, nullptr, nullptr, n_slots, d_tail, n_slots, st)) != PGP_OK)
+    return rc;
+  if ((rc = launch_score(ctx, d_T, n_slots, mode, gate_deg, d_s, nullptr, d_tail + 2, st)) != PGP_OK) return rc;
+  const int m = std::min(cap, n_slots);
+  std::vector<float> hT((size_t)m * 16), hs(m);
+  std::vector<int> hv(m);
+  int tail[4] = {0, 0, -1, 0};
+  if (m > 0) {
+    PGP_HIP(hipMemcpyAsync(hT.data(), d_T, (size_t)m * 64, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipMemcpyAsync(hs.data(), d_s, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipMemcpyAsync(hv.data(), d_v, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+  }
+  PGP_HIP(hipMemcpyAsync(tail, d_tail, 16, hipMemcpyDeviceToHost, st));
+  std::vector<float> bT(16);
+  int b_idx = -1;
+  PGP_HIP(hipStreamSynchronize(st));
+  const int n = tail[0];
+  b_idx = tail[2];
+  if (b_idx >= n) b_idx = -1;   // (a pad scores 0 and is never the best; belt and braces)
+  const int k = std::min(n, m);
+  if (k > 0) {
+    std::memcpy(T, hT.data(), (size_t)k * 64);
+    std::memcpy(scores, hs.data(), (size_t)k * 4);
+    if (votes) std::memcpy(votes, hv.data(), (size_t)k * 4);
+  }
+  if (b_idx >= 0 && best_T) {
+    if (b_idx < m) std::memcpy(best_T, hT.data() + (size_t)b_idx * 16, 64);
+    else PGP_HIP(hipMemcpy(best_T, d_T + (size_t)b_idx * 16, 64, hipMemcpyDeviceToHost));
+  }
+  *n_out = n;
+  if (best_index) *best_index = b_idx;
+  if (best_score) std::memcpy(best_score, &tail[3], 4);
+  if (best_score && b_idx < 0) *best_score = 0.f;
+  return PGP_OK;
+}
+
+int pgp_ppf_model_angles(pgp_ctx* ctx, float* alpha, long long n) {
+  if (!ctx || n < 0 || (n > 0 && !alpha)) {
+    set_error("pgp_ppf_model_angles: bad argument");
+    return PGP_EINVAL;
+  }
+  if (!ctx->ppf_alpha_ready) {
+    set_error("pgp_ppf_model_angles: no model angles (needs pgp_set_ppf_map with pairs and a covering pgp_set_ppf_model)");
+    return PGP_ESTATE;
+  }
+  if (n != ctx->ppf_n_pairs) {
+    set_error("pgp_ppf_model_angles: the table has %lld pairs, not %lld", ctx->ppf_n_pairs, n);
+    return PGP_EINVAL;
+  }
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  PGP_HIP(hipMemcpyAsync(alpha, ctx->d_ppf_alpha.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PGP_HIP(hipStreamSynchronize(ctx->stream));
+  return PGP_OK;
+}
+
+int pgp_ppf_accumulator(pgp_ctx* ctx, const pgp_ppf_options* opt, const int* ref_ids, int k, int* acc) {
+  if (!ctx || k < 0 || (k > 0 && (!ref_ids || !acc))) {
+    set_error("pgp_ppf_accumulator: bad argument");
+    return PGP_EINVAL;
+  }
+  int rc = ppf_vote_check(ctx, opt, "pgp_ppf_accumulator");
+  if (rc != PGP_OK) return rc;
+  for (int i = 0; i < k; ++i)
+    if (ref_ids[i] < 0 || ref_ids[i] >= ctx->nP) {
+      set_error("pgp_ppf_accumulator: reference %d names scene point %d of %d", i, ref_ids[i], ctx->nP);
+      return PGP_EINVAL;
+    }
+  if (k == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t cells = (size_t)ctx->ppf_model_n * opt->n_bins;
+  const size_t b_r = ((size_t)k * 4 + 255) & ~(size_t)255, b_a = (std::max<size_t>(cells, 1) * k * 4 + 255) & ~(size_t)255;
+  if ((rc = ctx->d_ppf_io.ensure(b_r + b_a + 256)) != PGP_OK) return rc;
+  unsigned char* base = ctx->d_ppf_io.as<unsigned char>();
+  int* d_ids = reinterpret_cast<int*>(base);
+  int* d_acc = reinterpret_cast<int*>(base + b_r);
+  int* d_n = reinterpret_cast<int*>(base + b_r + b_a);
+  PGP_HIP(hipMemcpyAsync(d_ids, ref_ids, (size_t)k * 4, hipMemcpyHostToDevice, st));
+  if ((rc = launch_ppf_vote(ctx, opt, d_ids, k, d_acc, nullptr, nullptr, nullptr, nullptr, 0, d_n, 0, st)) != PGP_OK) return rc;
+  if (cells > 0) PGP_HIP(hipMemcpyAsync(acc, d_acc, cells * k * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
   return PGP_OK;
 }
 

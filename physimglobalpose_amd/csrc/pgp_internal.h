@@ -264,6 +264,17 @@ struct pgp_ctx {
   // normal gate (base.cc:1756-1758) as thresholds on the dot product, see gate_thresholds()
   float gate_deg_cached = -1.f;
   float gate_lo = 2.f, gate_hi = -2.f;
+
+  // PPF voting (ppf_vote.hip).  What set_ppf_map records about the table's pair lists:
+  bool ppf_has_pairs = false;           // the table was given its pair lists
+  int ppf_id_min = 0, ppf_id_max = -1;  // range of the model ids in the pair lists (empty: max < min)
+  int ppf_max_f1 = -1;                  // largest distance key (mm) of the table
+  // the model the pair ids index, and alpha_m of every pair of the table
+  int ppf_model_n = -1;                 // -1: no model set
+  pgp::DevBuf d_ppf_model;              // float4 positions [n] | float4 normals [n]
+  pgp::DevBuf d_ppf_alpha;              // float alpha_m [ppf_n_pairs], valid while ppf_alpha_ready
+  bool ppf_alpha_ready = false;         // dropped whenever the table or the model is rewritten
+  pgp::DevBuf d_ppf_ws, d_ppf_io;       // voting workspace (peak slots, HBM accumulators); host-API staging
 };
 
 namespace pgp {
@@ -500,6 +511,13 @@ int launch_ppf_features(pgp_ctx* ctx, const int* h_pairs, int m, int* h_f, int* 
 int launch_stage_weights(pgp_ctx* ctx, int stage, int b1, int b2, int b3, float* h_cur, float* h_sum, int* h_present,
                          hipStream_t st);
 int launch_base_invariants(pgp_ctx* ctx, int* h_ids, int m, float* h_inv, int* h_ok, hipStream_t st);
+
+// ppf_vote.hip
+int ppf_model_angles(pgp_ctx* ctx);   // alpha_m of every pair, when the table (with pairs) and a covering model are set
+int launch_ppf_vote(pgp_ctx* ctx, const pgp_ppf_options* opt, const int* d_ref_ids, int n_ref_ids, int* d_acc_out,
+                    float* d_T, int* d_votes, int* d_ref, int* d_cell, int cap, int* d_n_out, int pad_to, hipStream_t st);
+int ppf_vote_check(pgp_ctx* ctx, const pgp_ppf_options* opt, const char* who);
+int ppf_slots(const pgp_ctx* ctx, const pgp_ppf_options* opt);   // reference points x peaks_per_ref
 
 // preprocess.hip
 int device_bbox(pgp_ctx* ctx, const float* d_pts, int n, int stride, float mn[3], float mx[3], hipStream_t st);

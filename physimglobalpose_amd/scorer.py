@@ -45,6 +45,7 @@ class LcpScorer:
         self._h = h
         self.nQ = 0
         self.nP = 0
+        self.n_ppf_model = 0
         self.delta = None
 
     @classmethod
@@ -56,6 +57,7 @@ class LcpScorer:
         self._borrowed = True
         self.nQ = 0
         self.nP = 0
+        self.n_ppf_model = 0
         self.delta = None
         return self
 
@@ -675,6 +677,84 @@ class LcpScorer:
         rot, trans = np.zeros(n, np.float32), np.zeros(n, np.float32)
         _lib.check(self._lib.pgp_pose_error(self._h, _fp(test), _fp(gt), n, _fp(sym), _fp(rot), _fp(trans)))
         return rot, trans
+
+    # ---- PPF Hough voting (the PPF_HOUGH generator, ObjectPoseCandidateSet.cpp:76-117) ----------
+    @staticmethod
+    def ppf_options(ref_step=5, n_bins=30, peaks_per_ref=1, min_vote_fraction=0.9, min_votes=3):
+        """pgp_ppf_options (the defaults are pgp_ppf_default_options')."""
+        return _lib.PpfOptions(int(ref_step), int(n_bins), int(peaks_per_ref), float(min_vote_fraction), int(min_votes))
+
+    def set_ppf_model(self, xyz, nrm):
+        """The positions and normals (centred, like the search model) that the pair ids of set_ppf_map index."""
+        xyz, nrm = _f32(xyz, 3), _f32(nrm, 3)
+        assert len(xyz) == len(nrm)
+        _lib.check(self._lib.pgp_set_ppf_model(self._h, _fp(xyz), _fp(nrm), len(xyz)))
+        self.n_ppf_model = len(xyz)
+
+    def _ppf_cap(self, cap, peaks_per_ref, ref_step):
+        if cap is not None:
+            return int(cap)
+        return ((self.nP + ref_step - 1) // ref_step) * peaks_per_ref if ref_step >= 1 and peaks_per_ref >= 1 else 0
+
+    def ppf_vote(self, cap=None, **opt):
+        """pgp_ppf_vote -> (T (k,16), votes (k,), ref (k,), cell (k,), n_out); k = min(n_out, cap), cap default: every slot."""
+        o = self.ppf_options(**opt)
+        cap = self._ppf_cap(cap, o.peaks_per_ref, o.ref_step)
+        T = np.zeros((max(cap, 1), 16), np.float32)
+        v, r, c = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
+        n = C.c_int(0)
+        _lib.check(self._lib.pgp_ppf_vote(self._h, C.byref(o), _fp(T), v.ctypes.data_as(_i), r.ctypes.data_as(_i),
+                                          c.ctypes.data_as(_i), cap, C.byref(n)))
+        k = min(n.value, cap)
+        return T[:k].copy(), v[:k].copy(), r[:k].copy(), c[:k].copy(), n.value
+
+    def ppf_vote_device(self, cap=None, d_T=None, d_votes=None, d_ref=None, d_cell=None, d_n_out=None, stream=None, **opt):
+        """pgp_ppf_vote_device on torch tensors, queued on `stream` (default: the current stream), no synchronisation.
+        Returns (d_T (cap,16), d_votes, d_ref, d_cell, d_n_out (1,) int32)."""
+        import torch
+        o = self.ppf_options(**opt)
+        cap = self._ppf_cap(cap, o.peaks_per_ref, o.ref_step)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_T = torch.empty((max(cap, 1), 16), dtype=torch.float32, device=dev) if d_T is None else d_T
+        d_votes = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if d_votes is None else d_votes
+        d_ref = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if d_ref is None else d_ref
+        d_cell = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if d_cell is None else d_cell
+        d_n_out = torch.empty(1, dtype=torch.int32, device=dev) if d_n_out is None else d_n_out
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_ppf_vote_device(self._h, C.byref(o), p(d_T), p(d_votes), p(d_ref), p(d_cell), cap,
+                                                 p(d_n_out), C.c_void_p(st)))
+        return d_T, d_votes, d_ref, d_cell, d_n_out
+
+    def ppf_hypotheses(self, mode=PGP_MODE_PLAIN, gate_deg=30.0, cap=None, **opt):
+        """What PPFVoting::generate returns: (T (k,16), scores (k,), votes (k,), n_out, best_index, best_score, best_T (16,)
+        or None when no hypothesis scores above 0)."""
+        o = self.ppf_options(**opt)
+        cap = self._ppf_cap(cap, o.peaks_per_ref, o.ref_step)
+        T = np.zeros((max(cap, 1), 16), np.float32)
+        s = np.zeros(max(cap, 1), np.float32)
+        v = np.zeros(max(cap, 1), np.int32)
+        n, bi, bs = C.c_int(0), C.c_int(-1), C.c_float(0)
+        bT = np.zeros(16, np.float32)
+        _lib.check(self._lib.pgp_ppf_hypotheses(self._h, C.byref(o), int(mode), C.c_float(gate_deg), _fp(T), _fp(s),
+                                                v.ctypes.data_as(_i), cap, C.byref(n), C.byref(bi), C.byref(bs), _fp(bT)))
+        k = min(n.value, cap)
+        return T[:k].copy(), s[:k].copy(), v[:k].copy(), n.value, bi.value, bs.value, (bT if bi.value >= 0 else None)
+
+    def ppf_model_angles(self, n_pairs):
+        """alpha_m of every pair of the table, in pair-list order -> (n_pairs,) float32."""
+        a = np.zeros(max(int(n_pairs), 1), np.float32)
+        _lib.check(self._lib.pgp_ppf_model_angles(self._h, _fp(a), C.c_longlong(int(n_pairs))))
+        return a[: int(n_pairs)]
+
+    def ppf_accumulator(self, ref_ids, **opt):
+        """The full accumulators of the given reference points (scene ids) -> (k, n_model, n_bins) int32."""
+        o = self.ppf_options(**opt)
+        ids = np.ascontiguousarray(ref_ids, np.int32).reshape(-1)
+        acc = np.zeros((max(len(ids), 1), self.n_ppf_model, o.n_bins), np.int32)
+        _lib.check(self._lib.pgp_ppf_accumulator(self._h, C.byref(o), ids.ctypes.data_as(_i), len(ids),
+                                                 acc.ctypes.data_as(_i)))
+        return acc[: len(ids)]
 
     # ---- ICP refinement (UCTState::performTrICP / utilities::performICP inner loop) --------------
     def icp_refine(self, src_xyz, tgt_xyz, T, trim=1.0, max_iterations=100, max_corr_dist=0.0,
