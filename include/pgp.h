@@ -802,6 +802,84 @@ int pgp_ppf_accumulator(pgp_ctx* ctx, const pgp_ppf_options* opt, const int* ref
 /* Debug export: alpha_m of every pair of the table in pair-list order (alpha[n], n = the table's pair count). */
 int pgp_ppf_model_angles(pgp_ctx* ctx, float* alpha, long long n);
 
+/* ---- physics settling of MCTS child states: UCTState::correctPhysics --------------------------------------------
+ * Replaces UCTState::correctPhysics (PPE/hypothesis_verification/mcts/UCTState.cpp:208-270, called on every expanded
+ * child and at every rollout level, UCTSearch.cpp:99,158,226) and the Bullet world of physim::PhySim
+ * (PPE/hypothesis_verification/physics_reasoning/PhySim.cpp): every earlier object static (mass 0), the newest one
+ * dynamic, the table a static box of half extents (0.40, 0.40, 0.20) at tableParams (SceneCfg.cpp:145-156), gravity
+ * (0, 0, -2), simulate(60) = 60 x stepSimulation(1/60), the settled pose back in the camera frame.  Bullet is not
+ * matched bit for bit: the device runs the stepping rules stated exactly in csrc/physics.hip (vertex-face contacts,
+ * at most 4 per body pair, sequential impulses, first-order quaternion update), restated in numpy float32 by
+ * tests/_physics_restate.py.  Only one body moves, so its mass cancels: impulses are per unit mass.
+ * Shapes live in a per-context arena until pgp_destroy.  Shape 0 is the built-in table box (8 vertices, 6 planes,
+ * margin 0); pgp_physics_add_shape hands out 1, 2, ... */
+#define PGP_PHYSICS_TABLE_SHAPE 0
+#define PGP_PHYSICS_MAX_VERTICES 256   /* hull vertex cap of one shape */
+#define PGP_PHYSICS_MAX_STATICS 16     /* static bodies of one state besides the table */
+#define PGP_PHYSICS_MAX_CONTACTS 68    /* 4 per body pair: (1 + 16) x 4 */
+typedef struct {
+  float dt;               /* 1/60 (> 0): stepSimulation(1.f/60.f), PhySim.cpp:112 */
+  int steps;              /* 60 (0 .. 100000): simulate(60), UCTState.cpp:247 */
+  float gravity[3];       /* (0, 0, -2), world frame: PhySim.cpp:3,16,110 */
+  float linear_damping;   /* 0.99 ([0, 1)): setDamping(0.99f, 0.99f), PhySim.cpp:43,73 */
+  float angular_damping;  /* 0.99 ([0, 1)) */
+  float friction;         /* 1 (>= 0): the product of the two bodies' frictions (1 x 1) */
+  int iterations;         /* 10 (1 .. 1000): sequential-impulse sweeps per step (Bullet's default) */
+  float erp;              /* 0.2 ([0, 1]): Baumgarte factor beta of the normal rows (Bullet's default) */
+} pgp_physics_options;
+typedef struct {
+  int n_contacts;    /* contacts of the last step (-1: the state was rejected on the device, T_out is NaN) */
+  float min_depth;   /* the smallest contact depth of the last step (<= 0 while touching; 0 without contacts) */
+  float lin_speed;   /* |v| after the last step */
+  float ang_speed;   /* |omega| after the last step */
+} pgp_physics_info;
+int pgp_physics_default_options(pgp_physics_options* opt);
+
+/* The convex hull of n points (n x 3 floats), pure host helper (no context, like pgp_center).  An incremental hull
+ * in double precision with the tolerance eps = 1e-7 x (largest |coordinate|), about float rounding: a point within eps
+ * of a face plane is not outside it.  Coplanar triangles (every vertex within eps of the first triangle's plane) merge into one plane.
+ * When the hull has more than max_vertices (4 .. 256) vertices, max_vertices of them are kept by farthest-point
+ * selection (start: the largest x, ties the lowest input index; then the vertex farthest from the kept set, ties
+ * the lowest index) and the hull of the kept points is rebuilt.  hull_xyz (max_vertices x 3) receives the hull
+ * vertices in ascending input order, planes (2 max_vertices x 4) the outward unit normal and offset (n . x <= d
+ * inside) of each face.  PGP_EINVAL: a NaN / inf, fewer than 4 points, or no 4 points spanning a volume. */
+int pgp_convex_hull(const float* xyz, int n, int max_vertices, float* hull_xyz, int* n_vert, float* planes,
+                    int* n_planes);
+/* Appends the hull of a mesh's vertices (n x 3, body frame: the model frame, its origin the centre of mass) to the
+ * context's shape arena: btConvexHullShape + setMargin (PhySim.cpp:53-79).  The unit-mass inertia is Bullet's
+ * btPolyhedralConvexShape::calculateLocalInertia: the box inertia I = (ly^2 + lz^2, lx^2 + lz^2, lx^2 + ly^2) / 12
+ * of l = hull extent + 6 margin per axis (the cached local AABB carries one margin per side, btTransformAabb adds
+ * one, calculateLocalInertia one more).  margin in [0, 0.1]; *shape_id receives the id. */
+int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, int max_vertices, int* shape_id);
+/* What the device holds for a shape: hull_xyz (256 x 3), planes (512 x 4), inertia[3], margin (each nullable). */
+int pgp_physics_shape_info(pgp_ctx* ctx, int shape_id, float* hull_xyz, int* n_vert, float* planes, int* n_planes,
+                           float inertia[3], float* margin);
+/* correctPhysics for n_states independent states, one dynamic body each: state i drops dyn_shape[i] at T[i] among the
+ * table and its statics static_shape[j] at static_T[j], j in [static_offsets[i], static_offsets[i + 1]) (at most 16).
+ * Poses are 16 floats column-major, object -> camera frame like every T of this header; world = cam_pose . T
+ * (convertToWorld, utilities.cpp:294-296) and T_out = cam_pose^-1 . world (convertToCamera, :324-329) with the rigid
+ * inverse formed on the host.  cam_pose NULL: the poses are world-frame.  table_params: the 12 floats of tableParams,
+ * rows of [R | t] in the world frame.  steps == 0 copies T to T_out bit for bit.  info (nullable, n_states).
+ * Host pointers, synchronous. */
+int pgp_physics_settle(pgp_ctx* ctx, const pgp_physics_options* opt, int n_states, const int* dyn_shape,
+                       const float* T, const int* static_offsets, const int* static_shape, const float* static_T,
+                       const float table_params[12], const float cam_pose[16], float* T_out, pgp_physics_info* info);
+/* The same with DEVICE arrays (d_dyn_shape, d_T, d_static_offsets, d_static_shape, d_static_T, d_T_out, d_info
+ * nullable); table_params and cam_pose stay host arrays (passed by value).  Enqueued on `stream`: no synchronisation,
+ * no allocation.  The shape ids and static ranges are checked on the device: a state that names an unknown shape or
+ * more than 16 statics gets a NaN T_out and n_contacts = -1.  d_T_out may be d_T, and may be the d_T that
+ * pgp_render_depth_device reads next on the same stream. */
+int pgp_physics_settle_device(pgp_ctx* ctx, const pgp_physics_options* opt, int n_states, const int* d_dyn_shape,
+                              const float* d_T, const int* d_static_offsets, const int* d_static_shape,
+                              const float* d_static_T, const float table_params[12], const float cam_pose[16],
+                              float* d_T_out, pgp_physics_info* d_info, void* stream);
+/* Debug export for parity tests: one state (n_static statics), host pointers, synchronous.  Per step k (opt->steps):
+ * state[k][13] = world x[3], q[4] (x, y, z, w), v[3], omega[3] after the step; contacts[k][68][8] = point[3],
+ * normal[3], depth, final lambda_n of each reduced contact in solver order; n_contacts[k] their count. */
+int pgp_physics_trace(pgp_ctx* ctx, const pgp_physics_options* opt, int dyn_shape, const float T[16], int n_static,
+                      const int* static_shape, const float* static_T, const float table_params[12],
+                      const float cam_pose[16], float* state, float* contacts, int* n_contacts);
+
 /* ---- several GPUs of one node (north_star; SceneCfg.cpp:376-406 and
  * HypothesisSelection.cpp:248-257 are the consumers) -----------------------------------------------
  * A pgp_multi is a group of devices in ONE process: one pgp_ctx, one host thread and one stream per

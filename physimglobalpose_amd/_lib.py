@@ -81,6 +81,15 @@ class PpfOptions(C.Structure):
                 ("min_votes", C.c_int)]
 
 
+class PhysicsOptions(C.Structure):
+    _fields_ = [("dt", C.c_float), ("steps", C.c_int), ("gravity", C.c_float * 3), ("linear_damping", C.c_float),
+                ("angular_damping", C.c_float), ("friction", C.c_float), ("iterations", C.c_int), ("erp", C.c_float)]
+
+
+class PhysicsInfo(C.Structure):
+    _fields_ = [("n_contacts", C.c_int), ("min_depth", C.c_float), ("lin_speed", C.c_float), ("ang_speed", C.c_float)]
+
+
 # every symbol include/pgp.h declares: (restype, argtypes)
 SIGNATURES = {
     "pgp_version": (C.c_int, []),
@@ -233,6 +242,17 @@ SIGNATURES = {
                                      _f]),
     "pgp_ppf_accumulator": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), _i, C.c_int, _i]),
     "pgp_ppf_model_angles": (C.c_int, [C.c_void_p, _f, C.c_longlong]),
+    "pgp_physics_default_options": (C.c_int, [C.POINTER(PhysicsOptions)]),
+    "pgp_convex_hull": (C.c_int, [_f, C.c_int, C.c_int, _f, _i, _f, _i]),
+    "pgp_physics_add_shape": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, _i]),
+    "pgp_physics_shape_info": (C.c_int, [C.c_void_p, C.c_int, _f, _i, _f, _i, _f, _f]),
+    "pgp_physics_settle": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, _i, _f, _i, _i, _f, _f, _f, _f,
+                                     C.POINTER(PhysicsInfo)]),
+    "pgp_physics_settle_device": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, _f, _f, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "pgp_physics_trace": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, _f, C.c_int, _i, _f, _f, _f, _f, _f,
+                                    _i]),
 }
 
 _lib = None

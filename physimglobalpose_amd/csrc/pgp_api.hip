@@ -210,7 +210,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   if (ctx->h_pin) {
@@ -3120,6 +3120,225 @@ int pgp_ppf_accumulator(pgp_ctx* ctx, const pgp_ppf_options* opt, const int* ref
   PGP_HIP(hipMemcpyAsync(d_ids, ref_ids, (size_t)k * 4, hipMemcpyHostToDevice, st));
   if ((rc = launch_ppf_vote(ctx, opt, d_ids, k, d_acc, nullptr, nullptr, nullptr, nullptr, 0, d_n, 0, st)) != PGP_OK) return rc;
   if (cells > 0) PGP_HIP(hipMemcpyAsync(acc, d_acc, cells * k * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- physics settling of MCTS child states (physics.hip) --------------------------------------------------------
+namespace {
+size_t phys_al256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" {
+
+int pgp_physics_default_options(pgp_physics_options* opt) {
+  if (!opt) {
+    set_error("pgp_physics_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->dt = 1.f / 60.f;
+  opt->steps = 60;
+  opt->gravity[0] = 0.f;
+  opt->gravity[1] = 0.f;
+  opt->gravity[2] = -2.f;
+  opt->linear_damping = 0.99f;
+  opt->angular_damping = 0.99f;
+  opt->friction = 1.f;
+  opt->iterations = 10;
+  opt->erp = 0.2f;
+  return PGP_OK;
+}
+
+int pgp_convex_hull(const float* xyz, int n, int max_vertices, float* hull_xyz, int* n_vert, float* planes, int* n_planes) {
+  if (!hull_xyz || !n_vert || !planes || !n_planes) {
+    set_error("pgp_convex_hull: null output");
+    return PGP_EINVAL;
+  }
+  std::vector<int> hv;
+  std::vector<std::array<double, 4>> pl;
+  const int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_convex_hull");
+  if (rc != PGP_OK) return rc;
+  for (size_t i = 0; i < hv.size(); ++i)
+    for (int c = 0; c < 3; ++c) hull_xyz[3 * i + c] = xyz[3 * (size_t)hv[i] + c];
+  for (size_t f = 0; f < pl.size(); ++f)
+    for (int c = 0; c < 4; ++c) planes[4 * f + c] = (float)pl[f][c];
+  *n_vert = (int)hv.size();
+  *n_planes = (int)pl.size();
+  return PGP_OK;
+}
+
+int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, int max_vertices, int* shape_id) {
+  if (!ctx || !shape_id || !(margin >= 0.f && margin <= 0.1f)) {
+    set_error("pgp_physics_add_shape: bad argument");
+    return PGP_EINVAL;
+  }
+  std::vector<int> hv;
+  std::vector<std::array<double, 4>> pl;
+  int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_physics_add_shape");
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  if ((rc = physics_arena_init(ctx)) != PGP_OK) return rc;
+  std::vector<float4> v, p;
+  for (int i : hv) v.push_back(make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f));
+  for (const auto& e : pl) p.push_back(make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]));
+  PGP_HIP(hipDeviceSynchronize());   // a queued settle may still read the arena that is about to grow
+  arena_append(ctx, v, p, margin);
+  if ((rc = arena_upload(ctx)) != PGP_OK) {
+    const PhysShape s = ctx->phys_shapes.back();
+    ctx->phys_shapes.pop_back();
+    ctx->phys_verts.resize(s.vert_off);
+    ctx->phys_planes.resize(s.plane_off);
+    return rc;
+  }
+  *shape_id = (int)ctx->phys_shapes.size() - 1;
+  return PGP_OK;
+}
+
+int pgp_physics_shape_info(pgp_ctx* ctx, int shape_id, float* hull_xyz, int* n_vert, float* planes, int* n_planes,
+                           float inertia[3], float* margin) {
+  if (!ctx) {
+    set_error("pgp_physics_shape_info: null context");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  int rc = physics_arena_init(ctx);
+  if (rc != PGP_OK) return rc;
+  if (shape_id < 0 || shape_id >= (int)ctx->phys_shapes.size()) {
+    set_error("pgp_physics_shape_info: unknown shape %d", shape_id);
+    return PGP_EINVAL;
+  }
+  PhysShape s;
+  PGP_HIP(hipMemcpy(&s, ctx->d_phys_shapes.as<PhysShape>() + shape_id, sizeof(s), hipMemcpyDeviceToHost));
+  std::vector<float4> v(s.n_vert), p(s.n_plane);
+  PGP_HIP(hipMemcpy(v.data(), ctx->d_phys_verts.as<float4>() + s.vert_off, v.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  PGP_HIP(hipMemcpy(p.data(), ctx->d_phys_planes.as<float4>() + s.plane_off, p.size() * sizeof(float4), hipMemcpyDeviceToHost));
+  if (n_vert) *n_vert = s.n_vert;
+  if (n_planes) *n_planes = s.n_plane;
+  if (hull_xyz)
+    for (int i = 0; i < s.n_vert; ++i) {
+      hull_xyz[3 * i] = v[i].x; hull_xyz[3 * i + 1] = v[i].y; hull_xyz[3 * i + 2] = v[i].z;
+    }
+  if (planes)
+    for (int f = 0; f < s.n_plane; ++f) {
+      planes[4 * f] = p[f].x; planes[4 * f + 1] = p[f].y; planes[4 * f + 2] = p[f].z; planes[4 * f + 3] = p[f].w;
+    }
+  if (inertia)
+    for (int i = 0; i < 3; ++i) inertia[i] = s.inertia[i];
+  if (margin) *margin = s.margin;
+  return PGP_OK;
+}
+
+int pgp_physics_settle(pgp_ctx* ctx, const pgp_physics_options* opt, int n_states, const int* dyn_shape, const float* T,
+                       const int* static_offsets, const int* static_shape, const float* static_T,
+                       const float table_params[12], const float cam_pose[16], float* T_out, pgp_physics_info* info) {
+  const char* who = "pgp_physics_settle";
+  if (!ctx || n_states < 0 || (n_states > 0 && (!dyn_shape || !T || !static_offsets || !T_out))) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  int rc = check_options(opt, who, PHYS_MAX_STEPS);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  PhysParams P;
+  if ((rc = make_params(ctx, opt, n_states, table_params, cam_pose, who, P)) != PGP_OK) return rc;
+  if (n_states == 0) return PGP_OK;
+  if ((rc = check_states(ctx, n_states, dyn_shape, T, static_offsets, static_shape, static_T, who)) != PGP_OK) return rc;
+  const size_t n = (size_t)n_states, m = (size_t)static_offsets[n_states];
+  const size_t b_dyn = phys_al256(n * 4), b_T = phys_al256(n * 64), b_off = phys_al256((n + 1) * 4), b_ss = phys_al256(std::max<size_t>(m, 1) * 4),
+               b_sT = phys_al256(std::max<size_t>(m, 1) * 64), b_info = phys_al256(n * sizeof(pgp_physics_info));
+  if ((rc = ctx->d_phys_io.ensure(b_dyn + 2 * b_T + b_off + b_ss + b_sT + b_info)) != PGP_OK) return rc;
+  unsigned char* base = ctx->d_phys_io.as<unsigned char>();
+  int* d_dyn = reinterpret_cast<int*>(base);
+  float* d_T = reinterpret_cast<float*>(base + b_dyn);
+  float* d_out = reinterpret_cast<float*>(base + b_dyn + b_T);
+  int* d_off = reinterpret_cast<int*>(base + b_dyn + 2 * b_T);
+  int* d_ss = reinterpret_cast<int*>(base + b_dyn + 2 * b_T + b_off);
+  float* d_sT = reinterpret_cast<float*>(base + b_dyn + 2 * b_T + b_off + b_ss);
+  pgp_physics_info* d_info = reinterpret_cast<pgp_physics_info*>(base + b_dyn + 2 * b_T + b_off + b_ss + b_sT);
+  hipStream_t st = ctx->stream;
+  PGP_HIP(hipMemcpyAsync(d_dyn, dyn_shape, n * 4, hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(d_T, T, n * 64, hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(d_off, static_offsets, (n + 1) * 4, hipMemcpyHostToDevice, st));
+  if (m > 0) {
+    PGP_HIP(hipMemcpyAsync(d_ss, static_shape, m * 4, hipMemcpyHostToDevice, st));
+    PGP_HIP(hipMemcpyAsync(d_sT, static_T, m * 64, hipMemcpyHostToDevice, st));
+  }
+  if ((rc = launch_settle(ctx, P, d_dyn, d_T, d_off, d_ss, d_sT, d_out, d_info, nullptr, nullptr, nullptr, st)) != PGP_OK)
+    return rc;
+  PGP_HIP(hipMemcpyAsync(T_out, d_out, n * 64, hipMemcpyDeviceToHost, st));
+  if (info) PGP_HIP(hipMemcpyAsync(info, d_info, n * sizeof(pgp_physics_info), hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+int pgp_physics_settle_device(pgp_ctx* ctx, const pgp_physics_options* opt, int n_states, const int* d_dyn_shape,
+                              const float* d_T, const int* d_static_offsets, const int* d_static_shape,
+                              const float* d_static_T, const float table_params[12], const float cam_pose[16],
+                              float* d_T_out, pgp_physics_info* d_info, void* stream) {
+  const char* who = "pgp_physics_settle_device";
+  if (!ctx || n_states < 0 || (n_states > 0 && (!d_dyn_shape || !d_T || !d_static_offsets || !d_T_out))) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  int rc = check_options(opt, who, PHYS_MAX_STEPS);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx, false);
+  PhysParams P;
+  if ((rc = make_params(ctx, opt, n_states, table_params, cam_pose, who, P)) != PGP_OK) return rc;
+  if (n_states == 0) return PGP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = launch_settle(ctx, P, d_dyn_shape, d_T, d_static_offsets, d_static_shape, d_static_T, d_T_out, d_info, nullptr,
+                     nullptr, nullptr, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_physics_trace(pgp_ctx* ctx, const pgp_physics_options* opt, int dyn_shape, const float T[16], int n_static,
+                      const int* static_shape, const float* static_T, const float table_params[12],
+                      const float cam_pose[16], float* state, float* contacts, int* n_contacts) {
+  const char* who = "pgp_physics_trace";
+  if (!ctx || !T || n_static < 0 || n_static > PGP_PHYSICS_MAX_STATICS || !state || !contacts || !n_contacts) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  int rc = check_options(opt, who, PHYS_MAX_TRACE_STEPS);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  PhysParams P;
+  if ((rc = make_params(ctx, opt, 1, table_params, cam_pose, who, P)) != PGP_OK) return rc;
+  const int off[2] = {0, n_static};
+  if ((rc = check_states(ctx, 1, &dyn_shape, T, off, static_shape, static_T, who)) != PGP_OK) return rc;
+  const size_t k = (size_t)opt->steps, m = (size_t)n_static;
+  const size_t b_hdr = 256, b_T = 256, b_ss = phys_al256(std::max<size_t>(m, 1) * 4), b_sT = phys_al256(std::max<size_t>(m, 1) * 64),
+               b_s = phys_al256(std::max<size_t>(k, 1) * PHYS_TRACE_STATE * 4),
+               b_c = phys_al256(std::max<size_t>(k, 1) * PGP_PHYSICS_MAX_CONTACTS * PHYS_TRACE_CONTACT * 4), b_n = phys_al256(std::max<size_t>(k, 1) * 4);
+  if ((rc = ctx->d_phys_io.ensure(b_hdr + 2 * b_T + b_ss + b_sT + b_s + b_c + b_n)) != PGP_OK) return rc;
+  unsigned char* base = ctx->d_phys_io.as<unsigned char>();
+  int* d_hdr = reinterpret_cast<int*>(base);   // [0] dyn, [1..2] offsets
+  float* d_T = reinterpret_cast<float*>(base + b_hdr);
+  float* d_out = reinterpret_cast<float*>(base + b_hdr + b_T);
+  int* d_ss = reinterpret_cast<int*>(base + b_hdr + 2 * b_T);
+  float* d_sT = reinterpret_cast<float*>(base + b_hdr + 2 * b_T + b_ss);
+  float* d_s = reinterpret_cast<float*>(base + b_hdr + 2 * b_T + b_ss + b_sT);
+  float* d_c = reinterpret_cast<float*>(base + b_hdr + 2 * b_T + b_ss + b_sT + b_s);
+  int* d_n = reinterpret_cast<int*>(base + b_hdr + 2 * b_T + b_ss + b_sT + b_s + b_c);
+  hipStream_t st = ctx->stream;
+  const int hdr[3] = {dyn_shape, 0, n_static};
+  PGP_HIP(hipMemcpyAsync(d_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(d_T, T, 64, hipMemcpyHostToDevice, st));
+  if (m > 0) {
+    PGP_HIP(hipMemcpyAsync(d_ss, static_shape, m * 4, hipMemcpyHostToDevice, st));
+    PGP_HIP(hipMemcpyAsync(d_sT, static_T, m * 64, hipMemcpyHostToDevice, st));
+  }
+  PGP_HIP(hipMemsetAsync(d_c, 0, b_c, st));
+  if ((rc = launch_settle(ctx, P, d_hdr, d_T, d_hdr + 1, d_ss, d_sT, d_out, nullptr, d_s, d_c, d_n, st)) != PGP_OK) return rc;
+  if (k > 0) {
+    PGP_HIP(hipMemcpyAsync(state, d_s, k * PHYS_TRACE_STATE * 4, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipMemcpyAsync(contacts, d_c, k * PGP_PHYSICS_MAX_CONTACTS * PHYS_TRACE_CONTACT * 4, hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipMemcpyAsync(n_contacts, d_n, k * 4, hipMemcpyDeviceToHost, st));
+  }
   PGP_HIP(hipStreamSynchronize(st));
   return PGP_OK;
 }

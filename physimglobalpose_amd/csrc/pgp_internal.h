@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -76,6 +77,14 @@ struct DevBuf {
   int ensure(size_t bytes);  // returns PGP_OK / PGP_EHIP
   void release();
   template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// one convex shape of the physics arena (physics.hip): hull vertices and planes are float4 slices of the arena
+struct PhysShape {
+  int vert_off, n_vert, plane_off, n_plane;
+  float margin, radius;   // radius: bounding sphere of the hull about the body origin (rounded up to float)
+  float inertia[3];       // unit-mass inertia diagonal
+  float pad;
 };
 
 }  // namespace pgp
@@ -275,6 +284,11 @@ struct pgp_ctx {
   pgp::DevBuf d_ppf_alpha;              // float alpha_m [ppf_n_pairs], valid while ppf_alpha_ready
   bool ppf_alpha_ready = false;         // dropped whenever the table or the model is rewritten
   pgp::DevBuf d_ppf_ws, d_ppf_io;       // voting workspace (peak slots, HBM accumulators); host-API staging
+
+  // physics shape arena (physics.hip): host mirrors and their device copies (shape 0 = the table box)
+  std::vector<pgp::PhysShape> phys_shapes;
+  std::vector<float4> phys_verts, phys_planes;   // body frame: {x, y, z, 0} and {n, d}
+  pgp::DevBuf d_phys_shapes, d_phys_verts, d_phys_planes, d_phys_io;
 };
 
 namespace pgp {
@@ -511,6 +525,31 @@ int launch_ppf_features(pgp_ctx* ctx, const int* h_pairs, int m, int* h_f, int* 
 int launch_stage_weights(pgp_ctx* ctx, int stage, int b1, int b2, int b3, float* h_cur, float* h_sum, int* h_present,
                          hipStream_t st);
 int launch_base_invariants(pgp_ctx* ctx, int* h_ids, int m, float* h_inv, int* h_ok, hipStream_t st);
+
+// physics.hip
+constexpr int PHYS_TRACE_STATE = 13, PHYS_TRACE_CONTACT = 8;   // floats per step / per contact of pgp_physics_trace
+constexpr int PHYS_MAX_STEPS = 100000, PHYS_MAX_TRACE_STEPS = 10000;
+// kernel parameters of one settle launch, passed by value
+struct PhysParams {
+  int n_states, steps, iterations, n_shapes, has_cam;
+  float dt, half_dt, w_max, lin_c, ang_c, mu, erp;
+  float g[3];
+  float cam[16], cam_inv[16];
+  float table[12];
+};
+int physics_arena_init(pgp_ctx* ctx);   // the built-in table box as shape 0, uploaded (idempotent)
+int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>& hv, std::vector<std::array<double, 4>>& pl,
+                     const char* who);
+void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, float margin);
+int arena_upload(pgp_ctx* ctx);
+int check_options(const pgp_physics_options* o, const char* who, int max_steps);
+int make_params(pgp_ctx* ctx, const pgp_physics_options* o, int n_states, const float* table_params, const float* cam_pose,
+                const char* who, PhysParams& P);
+int check_states(pgp_ctx* ctx, int n, const int* dyn, const float* T, const int* off, const int* ss, const float* sT,
+                 const char* who);
+int launch_settle(pgp_ctx* ctx, const PhysParams& P, const int* d_dyn, const float* d_T, const int* d_off, const int* d_ss,
+                  const float* d_sT, float* d_out, pgp_physics_info* d_info, float* tr_s, float* tr_c, int* tr_n,
+                  hipStream_t st);
 
 // ppf_vote.hip
 int ppf_model_angles(pgp_ctx* ctx);   // alpha_m of every pair, when the table (with pairs) and a covering model are set

@@ -35,6 +35,12 @@ def _f32(a, cols=None):
     return a
 
 
+def _info_array(info, n):
+    """pgp_physics_info[n] -> a numpy structured array."""
+    dt = np.dtype([("n_contacts", np.int32), ("min_depth", np.float32), ("lin_speed", np.float32), ("ang_speed", np.float32)])
+    return np.frombuffer(bytes(info), dtype=dt, count=n).copy() if n else np.zeros(0, dt)
+
+
 class LcpScorer:
     """One (scene, model) pair on one GPU."""
 
@@ -995,6 +1001,109 @@ class LcpScorer:
         info = _lib.IndexInfo()
         _lib.check(self._lib.pgp_get_index_info(self._h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
+
+    # ---- physics settling: UCTState::correctPhysics (csrc/physics.hip) ----------------------------------------------
+    @staticmethod
+    def physics_options(**kw):
+        """pgp_physics_default_options with keyword overrides (gravity as a 3-sequence)."""
+        o = _lib.PhysicsOptions()
+        _lib.check(_lib.load().pgp_physics_default_options(C.byref(o)))
+        for k, v in kw.items():
+            if k == "gravity":
+                o.gravity[:] = [float(x) for x in v]
+            else:
+                assert hasattr(o, k), k
+                setattr(o, k, v)
+        return o
+
+    @staticmethod
+    def convex_hull(xyz, max_vertices=256):
+        """pgp_convex_hull -> (hull vertices (k,3), planes (f,4) = outward unit normal and offset, n . x <= d inside)."""
+        P = _f32(xyz, 3)
+        hv = np.zeros((max_vertices, 3), np.float32)
+        pl = np.zeros((2 * max_vertices, 4), np.float32)
+        nv, npl = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.load().pgp_convex_hull(_fp(P), len(P), int(max_vertices), _fp(hv), C.byref(nv), _fp(pl), C.byref(npl)))
+        return hv[:nv.value].copy(), pl[:npl.value].copy()
+
+    def physics_add_shape(self, xyz, margin=0.001, max_vertices=256):
+        """Appends the hull of a mesh's vertices to the context's shape arena -> shape id (0 is the table box)."""
+        P = _f32(xyz, 3)
+        sid = C.c_int(-1)
+        _lib.check(self._lib.pgp_physics_add_shape(self._h, _fp(P), len(P), C.c_float(margin), int(max_vertices), C.byref(sid)))
+        return sid.value
+
+    def physics_shape_info(self, shape_id):
+        """What the device holds for a shape: dict(verts (k,3), planes (f,4), inertia (3,), margin)."""
+        hv = np.zeros((256, 3), np.float32)
+        pl = np.zeros((512, 4), np.float32)
+        inertia = np.zeros(3, np.float32)
+        margin = C.c_float(0)
+        nv, npl = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgp_physics_shape_info(self._h, int(shape_id), _fp(hv), C.byref(nv), _fp(pl), C.byref(npl),
+                                                    _fp(inertia), C.byref(margin)))
+        return dict(verts=hv[:nv.value].copy(), planes=pl[:npl.value].copy(), inertia=inertia, margin=np.float32(margin.value))
+
+    @staticmethod
+    def _statics(statics, n):
+        """statics: one list of (shape_id, T (16,)) per state -> offsets (n+1,), shapes (m,), T (m,16)."""
+        statics = statics if statics is not None else [[] for _ in range(n)]
+        assert len(statics) == n
+        off = np.zeros(n + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in statics])
+        ss = np.array([sid for s in statics for sid, _ in s] or [0], np.int32)
+        sT = np.array([np.asarray(T, np.float32).reshape(16) for s in statics for _, T in s] or [np.zeros(16)], np.float32)
+        return off, ss, sT
+
+    def physics_settle(self, dyn_shape, T, table_params, cam_pose=None, statics=None, **opt):
+        """pgp_physics_settle: dyn_shape (n,), T (n,16) column-major camera-frame poses, statics: per state a list of
+        (shape_id, T (16,)) -> (T_out (n,16), info (n,) structured: n_contacts, min_depth, lin_speed, ang_speed)."""
+        o = self.physics_options(**opt)
+        dyn = np.ascontiguousarray(dyn_shape, np.int32).reshape(-1)
+        n = len(dyn)
+        T = _f32(T, 16)
+        off, ss, sT = self._statics(statics, n)
+        tp = _f32(table_params).reshape(12)
+        cam = None if cam_pose is None else _f32(cam_pose).reshape(16)
+        out = np.zeros((max(n, 1), 16), np.float32)
+        info = (_lib.PhysicsInfo * max(n, 1))()
+        _lib.check(self._lib.pgp_physics_settle(self._h, C.byref(o), n, dyn.ctypes.data_as(_i), _fp(T), off.ctypes.data_as(_i),
+                                                ss.ctypes.data_as(_i), _fp(sT), _fp(tp), _fp(cam), _fp(out), info))
+        return out[:n], _info_array(info, n)
+
+    def physics_settle_device(self, d_dyn_shape, d_T, d_static_offsets, d_static_shape, d_static_T, table_params,
+                              cam_pose=None, d_T_out=None, d_info=None, stream=None, **opt):
+        """pgp_physics_settle_device on torch tensors (int32 / float32), queued on `stream` (default: the current stream),
+        no synchronisation.  d_info: an int32 tensor (n, 4) viewed as pgp_physics_info, or None.  Returns d_T_out."""
+        import torch
+        o = self.physics_options(**opt)
+        n = int(d_dyn_shape.numel())
+        dev = d_T.device
+        d_T_out = torch.empty((max(n, 1), 16), dtype=torch.float32, device=dev) if d_T_out is None else d_T_out
+        tp = _f32(table_params).reshape(12)
+        cam = None if cam_pose is None else _f32(cam_pose).reshape(16)
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_physics_settle_device(self._h, C.byref(o), n, p(d_dyn_shape), p(d_T), p(d_static_offsets),
+                                                       p(d_static_shape), p(d_static_T), _fp(tp), _fp(cam), p(d_T_out),
+                                                       p(d_info), C.c_void_p(st)))
+        return d_T_out
+
+    def physics_trace(self, dyn_shape, T, table_params, cam_pose=None, statics=(), **opt):
+        """pgp_physics_trace for one state -> (state (steps,13) = x, q (xyzw), v, w; contacts (steps,68,8) = point,
+        normal, depth, lambda_n; n_contacts (steps,))."""
+        o = self.physics_options(**opt)
+        k = o.steps
+        off, ss, sT = self._statics([list(statics)], 1)
+        tp = _f32(table_params).reshape(12)
+        cam = None if cam_pose is None else _f32(cam_pose).reshape(16)
+        T = _f32(T).reshape(16)
+        state = np.zeros((max(k, 1), 13), np.float32)
+        contacts = np.zeros((max(k, 1), 68, 8), np.float32)
+        nc = np.zeros(max(k, 1), np.int32)
+        _lib.check(self._lib.pgp_physics_trace(self._h, C.byref(o), int(dyn_shape), _fp(T), int(off[1]), ss.ctypes.data_as(_i),
+                                               _fp(sT), _fp(tp), _fp(cam), _fp(state), _fp(contacts), nc.ctypes.data_as(_i)))
+        return state[:k], contacts[:k], nc[:k]
 
 
 class MultiGpuScorer:
