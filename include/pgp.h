@@ -880,6 +880,77 @@ int pgp_physics_trace(pgp_ctx* ctx, const pgp_physics_options* opt, int dyn_shap
                       const int* static_shape, const float* static_T, const float table_params[12],
                       const float cam_pose[16], float* state, float* contacts, int* n_contacts);
 
+/* ---- MCTS hypothesis selection: UCTSearch::performSearch ----------------------------------------------------------
+ * Replaces the node's MCTS verification mode (SceneCfg.cpp:410-421 -> HypothesisSelection.cpp:241-265 ->
+ * mcts/UCTSearch.cpp, mcts/UCTState.cpp).  The tree and the stop rules live on the host; every state is settled
+ * (pgp_physics_settle's kernel), rendered (pgp_render_depth's) and costed (pgp_depth_cost's) on the device, one
+ * launch per level and stage for all the descents of a step.  The search rules are stated exactly in csrc/mcts.hip
+ * and restated in Python by tests/_mcts_restate.py.  leaves_per_step = 1 follows the reference's order exactly;
+ * B > 1 makes B descents per step with in-flight (virtual) visits. */
+#define PGP_MCTS_ROLLOUT_RANDOM 0   /* UCTSearch::defaultPolicy: a counter-based draw per (descent, level) */
+#define PGP_MCTS_ROLLOUT_LCP 1      /* UCTSearch::LCPPolicy: the first hypothesis of the highest score */
+#define PGP_MCTS_MAX_OBJECTS 17     /* the newest object settles among at most 16 statics */
+#define PGP_MCTS_MAX_LEAVES_PER_STEP 256
+#define PGP_MCTS_STOP_EXPANSIONS 1  /* expansions >= max_expansions (the reference's test) */
+#define PGP_MCTS_STOP_ITERATIONS 2  /* descents == max_iterations */
+#define PGP_MCTS_STOP_EXHAUSTED 3   /* every node of the tree expanded: the best state can no longer change */
+#define PGP_MCTS_STOP_TIME 4        /* elapsed > max_seconds after a step */
+typedef struct {
+  long long max_expansions;      /* <= 0: the reference's sum_{i=0..n_obj} 25^i (UCTSearch.cpp:290-293), clamped to 2^31-1 */
+  int max_iterations;            /* cap on descents (the reference has none); > 0 */
+  float max_seconds;             /* maxSearchTime (60, UCTSearch.cpp:10); 0 = none; checked between steps only */
+  float alpha;                   /* 5000 (UCTState.cpp:10): the exploration weight of getBestChild */
+  float explanation_threshold;   /* 0.01 (UCTState.cpp:8): computeCost's pixel threshold */
+  int rollout;                   /* PGP_MCTS_ROLLOUT_RANDOM (the live defaultPolicy) | PGP_MCTS_ROLLOUT_LCP */
+  unsigned long long seed;       /* the random rollout's draws */
+  int leaves_per_step;           /* B in [1, 256]; 1 = the reference's order exactly */
+  float virtual_cost;            /* V, the reward of an in-flight visit when B > 1; <= 0: rows * cols */
+  pgp_physics_options physics;   /* correctPhysics */
+} pgp_mcts_options;
+/* One object of objOrder: its physics shape, its render mesh and its hypothesisSet. */
+typedef struct {
+  int shape_id;              /* from pgp_physics_add_shape */
+  const float* vertices;     /* n_vert x vertex_stride floats (stride 3 or 4), object frame; host */
+  int vertex_stride;
+  int n_vert;
+  const int* triangles;      /* n_tri x 3 vertex indices, or NULL: vertices are splatted (pgp_render_depth) */
+  int n_tri;
+  int n_hyp;                 /* >= 1 */
+  const float* T;            /* n_hyp x 16 column-major, object -> camera frame */
+  const float* scores;       /* n_hyp LCP scores (finite, >= 0): the children's hval */
+} pgp_mcts_object;
+typedef struct {
+  long long descents;            /* tree-policy descents (the reference's loop iterations) */
+  long long steps;               /* device steps: one synchronisation each */
+  long long expansions;          /* numExpansionsSearch: nodes added to the tree */
+  long long settle_evaluations;  /* states settled (expanded children plus rollout levels) */
+  int stop_reason;               /* PGP_MCTS_STOP_* */
+  float elapsed_ms;              /* wall time of the search, uploads and downloads included */
+} pgp_mcts_info;
+typedef struct {
+  int step;            /* the step that made this descent */
+  int t;               /* the descent's global 0-based index */
+  int depth;           /* depth of the selected node: the expanded child, or a leaf selected again */
+  int hyp[PGP_MCTS_MAX_OBJECTS];   /* the full leaf state's hypothesis per object (-1 past n_obj) */
+  int evaluated;       /* 1: this descent settled, rendered and costed a new leaf state */
+  float render_score;  /* the leaf state's renderScore */
+  float reward;        /* what backupReward added along the path */
+} pgp_mcts_record;
+int pgp_mcts_default_options(pgp_mcts_options* opt);
+/* Runs the search over n_obj objects (1 .. 17) on the frame `observed` (cam->rows x cam->cols float metres, host).
+ * table_params: tableParams (12 floats, rows of [R | t], world frame); cam_pose: camPose (column-major, NULL: poses
+ * are world-frame), as in pgp_physics_settle.  opt NULL: the defaults.  best_hyp[n_obj] and best_T[n_obj x 16]
+ * receive the best leaf state (bestState): its hypothesis ids and its settled poses (camera frame); *best_score its
+ * renderScore (bestRenderScore).  info (nullable).  trace (nullable, trace_cap records): one record per descent in
+ * order; *n_trace (nullable) the number of descents, which may exceed trace_cap (the list is then truncated).
+ * PGP_EINVAL: n_obj outside 1..17, n_hyp < 1, a NaN or negative score, a non-finite pose, an unknown shape id, a bad
+ * mesh, leaves_per_step outside 1..256, alpha not finite, max_iterations <= 0, bad physics options, NULL observed.
+ * Synchronous; the context stays usable after an error. */
+int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_object* objs, int n_obj,
+                    const float table_params[12], const float cam_pose[16], const pgp_camera* cam, const float* observed,
+                    int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
+                    int trace_cap, int* n_trace);
+
 /* ---- several GPUs of one node (north_star; SceneCfg.cpp:376-406 and
  * HypothesisSelection.cpp:248-257 are the consumers) -----------------------------------------------
  * A pgp_multi is a group of devices in ONE process: one pgp_ctx, one host thread and one stream per

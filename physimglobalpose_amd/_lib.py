@@ -90,6 +90,43 @@ class PhysicsInfo(C.Structure):
     _fields_ = [("n_contacts", C.c_int), ("min_depth", C.c_float), ("lin_speed", C.c_float), ("ang_speed", C.c_float)]
 
 
+PGP_MCTS_ROLLOUT_RANDOM = 0
+PGP_MCTS_ROLLOUT_LCP = 1
+PGP_MCTS_MAX_OBJECTS = 17
+PGP_MCTS_STOP_EXPANSIONS, PGP_MCTS_STOP_ITERATIONS, PGP_MCTS_STOP_EXHAUSTED, PGP_MCTS_STOP_TIME = 1, 2, 3, 4
+
+
+def mcts_types():
+    """The MCTS structures of include/pgp.h (pgp_mcts_options, _object, _info, _record), built on first use: the entry
+    points take them as void pointers here."""
+    global _mcts_types
+    if _mcts_types is None:
+        class MctsOptions(C.Structure):
+            _fields_ = [("max_expansions", C.c_longlong), ("max_iterations", C.c_int), ("max_seconds", C.c_float),
+                        ("alpha", C.c_float), ("explanation_threshold", C.c_float), ("rollout", C.c_int),
+                        ("seed", C.c_ulonglong), ("leaves_per_step", C.c_int), ("virtual_cost", C.c_float),
+                        ("physics", PhysicsOptions)]
+
+        class MctsObject(C.Structure):
+            _fields_ = [("shape_id", C.c_int), ("vertices", C.POINTER(C.c_float)), ("vertex_stride", C.c_int),
+                        ("n_vert", C.c_int), ("triangles", C.POINTER(C.c_int)), ("n_tri", C.c_int), ("n_hyp", C.c_int),
+                        ("T", C.POINTER(C.c_float)), ("scores", C.POINTER(C.c_float))]
+
+        class MctsInfo(C.Structure):
+            _fields_ = [("descents", C.c_longlong), ("steps", C.c_longlong), ("expansions", C.c_longlong),
+                        ("settle_evaluations", C.c_longlong), ("stop_reason", C.c_int), ("elapsed_ms", C.c_float)]
+
+        class MctsRecord(C.Structure):
+            _fields_ = [("step", C.c_int), ("t", C.c_int), ("depth", C.c_int), ("hyp", C.c_int * PGP_MCTS_MAX_OBJECTS),
+                        ("evaluated", C.c_int), ("render_score", C.c_float), ("reward", C.c_float)]
+
+        _mcts_types = (MctsOptions, MctsObject, MctsInfo, MctsRecord)
+    return _mcts_types
+
+
+_mcts_types = None
+
+
 # every symbol include/pgp.h declares: (restype, argtypes)
 SIGNATURES = {
     "pgp_version": (C.c_int, []),
@@ -253,6 +290,9 @@ SIGNATURES = {
                                             C.c_void_p]),
     "pgp_physics_trace": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, _f, C.c_int, _i, _f, _f, _f, _f, _f,
                                     _i]),
+    "pgp_mcts_default_options": (C.c_int, [C.c_void_p]),
+    "pgp_mcts_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _f, _f, C.POINTER(Camera), _f, _i, _f, _f,
+                                  C.c_void_p, C.c_void_p, C.c_int, _i]),
 }
 
 _lib = None

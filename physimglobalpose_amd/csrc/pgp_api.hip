@@ -210,7 +210,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_acc, &ctx->d_pub_ticket};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   if (ctx->h_pin) {
@@ -3341,6 +3341,46 @@ int pgp_physics_trace(pgp_ctx* ctx, const pgp_physics_options* opt, int dyn_shap
   }
   PGP_HIP(hipStreamSynchronize(st));
   return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- MCTS hypothesis selection (mcts.hip) -------------------------------------------------------------------------
+extern "C" {
+
+int pgp_mcts_default_options(pgp_mcts_options* opt) {
+  if (!opt) {
+    set_error("pgp_mcts_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->max_expansions = 0;            // sum_{i=0..n_obj} 25^i (UCTSearch.cpp:290-293)
+  opt->max_iterations = 2147483647;
+  opt->max_seconds = 60.f;            // maxSearchTime (UCTSearch.cpp:10)
+  opt->alpha = 5000.f;                // UCTState.cpp:10
+  opt->explanation_threshold = 0.01f; // UCTState.cpp:8
+  opt->rollout = PGP_MCTS_ROLLOUT_RANDOM;
+  opt->seed = 0;
+  opt->leaves_per_step = 1;
+  opt->virtual_cost = 0.f;
+  return pgp_physics_default_options(&opt->physics);
+}
+
+int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_object* objs, int n_obj,
+                    const float table_params[12], const float cam_pose[16], const pgp_camera* cam, const float* observed,
+                    int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
+                    int trace_cap, int* n_trace) {
+  if (!ctx) {
+    set_error("pgp_mcts_search: null context");
+    return PGP_EINVAL;
+  }
+  pgp_mcts_options def;
+  if (!opt) {
+    pgp_mcts_default_options(&def);
+    opt = &def;
+  }
+  CtxGuard guard(ctx);
+  return mcts_search_impl(ctx, opt, objs, n_obj, table_params, cam_pose, cam, observed, best_hyp, best_T, best_score,
+                          info, trace, trace_cap, n_trace);
 }
 
 }  // extern "C"

@@ -289,6 +289,9 @@ struct pgp_ctx {
   std::vector<pgp::PhysShape> phys_shapes;
   std::vector<float4> phys_verts, phys_planes;   // body frame: {x, y, z, 0} and {n, d}
   pgp::DevBuf d_phys_shapes, d_phys_verts, d_phys_planes, d_phys_io;
+
+  // MCTS search (mcts.hip): step workspace (pose tables, settle inputs, descriptors, scores); two images per slot
+  pgp::DevBuf d_mcts_ws, d_mcts_img;
 };
 
 namespace pgp {
@@ -550,6 +553,12 @@ int check_states(pgp_ctx* ctx, int n, const int* dyn, const float* T, const int*
 int launch_settle(pgp_ctx* ctx, const PhysParams& P, const int* d_dyn, const float* d_T, const int* d_off, const int* d_ss,
                   const float* d_sT, float* d_out, pgp_physics_info* d_info, float* tr_s, float* tr_c, int* tr_n,
                   hipStream_t st);
+
+// mcts.hip: pgp_mcts_search after the context guard (opt non-null)
+int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_object* objs, int n_obj,
+                     const float* table_params, const float* cam_pose, const pgp_camera* cam, const float* observed,
+                     int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
+                     int trace_cap, int* n_trace);
 
 // ppf_vote.hip
 int ppf_model_angles(pgp_ctx* ctx);   // alpha_m of every pair, when the table (with pairs) and a covering model are set

@@ -1105,6 +1105,60 @@ class LcpScorer:
                                                _fp(sT), _fp(tp), _fp(cam), _fp(state), _fp(contacts), nc.ctypes.data_as(_i)))
         return state[:k], contacts[:k], nc[:k]
 
+    # ---- MCTS hypothesis selection: UCTSearch::performSearch (csrc/mcts.hip) ------------------------------------------
+    @staticmethod
+    def mcts_options(physics=None, **kw):
+        """pgp_mcts_default_options with keyword overrides; physics: a dict of pgp_physics_options overrides."""
+        o = _lib.mcts_types()[0]()
+        _lib.check(_lib.load().pgp_mcts_default_options(C.byref(o)))
+        for k, v in kw.items():
+            assert hasattr(o, k) and k != "physics", k
+            setattr(o, k, v)
+        if physics:
+            o.physics = LcpScorer.physics_options(**physics)
+        return o
+
+    def mcts_search(self, objects, table_params, cam, observed, cam_pose=None, trace=True, trace_cap=None, **opt):
+        """pgp_mcts_search.  objects: per object (objOrder) a dict with shape_id, vertices (n,3|4), triangles (m,3) or
+        None, T (n_hyp,16) column-major camera frame, scores (n_hyp,).  cam: LcpScorer.camera(...); observed (rows,cols).
+        Returns dict(best_hyp (n_obj,), best_T (n_obj,16), best_score, info (dict), trace (structured array: step, t,
+        depth, hyp (17,), evaluated, render_score, reward), n_trace)."""
+        _, MctsObject, MctsInfo, MctsRecord = _lib.mcts_types()
+        o = opt.pop("options", None) or self.mcts_options(**opt)
+        n_obj = len(objects)
+        keep = []
+        objs = (MctsObject * max(n_obj, 1))()
+        for i, ob in enumerate(objects):
+            v = np.ascontiguousarray(ob["vertices"], np.float32)
+            v = v.reshape(-1, v.shape[-1] if v.ndim > 1 else 3)
+            tri = ob.get("triangles")
+            tri = None if tri is None else np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+            T = _f32(ob["T"], 16)
+            sc = np.ascontiguousarray(ob["scores"], np.float32).reshape(-1)
+            keep += [v, tri, T, sc]
+            objs[i] = MctsObject(int(ob["shape_id"]), _fp(v), int(v.shape[1]), len(v),
+                                      None if tri is None else tri.ctypes.data_as(_i), 0 if tri is None else len(tri),
+                                      len(T), _fp(T), _fp(sc))
+        tp = _f32(table_params).reshape(12)
+        camp = None if cam_pose is None else _f32(cam_pose).reshape(16)
+        obs = None if observed is None else np.ascontiguousarray(observed, np.float32)
+        best_hyp = np.zeros(max(n_obj, 1), np.int32)
+        best_T = np.zeros((max(n_obj, 1), 16), np.float32)
+        best_score = C.c_float(0)
+        info = MctsInfo()
+        cap = 0 if not trace else int(trace_cap if trace_cap is not None else min(int(o.max_iterations), 1 << 16))
+        rec = (MctsRecord * max(cap, 1))()
+        n_trace = C.c_int(0)
+        _lib.check(self._lib.pgp_mcts_search(self._h, C.byref(o), objs, n_obj, _fp(tp), _fp(camp), C.byref(cam), _fp(obs),
+                                             best_hyp.ctypes.data_as(_i), _fp(best_T), C.byref(best_score), C.byref(info),
+                                             rec if cap else None, cap, C.byref(n_trace)))
+        m = min(n_trace.value, cap)
+        rec_dt = np.dtype([("step", np.int32), ("t", np.int32), ("depth", np.int32), ("hyp", np.int32, (17,)),
+                           ("evaluated", np.int32), ("render_score", np.float32), ("reward", np.float32)])
+        tr = np.frombuffer(bytes(rec), dtype=rec_dt, count=m).copy() if m else np.zeros(0, rec_dt)
+        return dict(best_hyp=best_hyp[:n_obj].copy(), best_T=best_T[:n_obj].copy(), best_score=np.float32(best_score.value),
+                    info={k: getattr(info, k) for k, _ in info._fields_}, trace=tr, n_trace=n_trace.value)
+
 
 class MultiGpuScorer:
     """One (scene, model) pair replicated on several GPUs of the node, hypotheses block-partitioned,
