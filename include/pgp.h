@@ -222,6 +222,35 @@ int pgp_set_search_model(pgp_ctx* ctx, const float* xyz, int n);
  * hash set; the ratio thresholds that stand in for atan2f are measured on the host's libm here. */
 int pgp_set_ppf_map(pgp_ctx* ctx, const int* keys, const int* counts, const int* pairs, int n_keys);
 
+/* The same table BUILT on the device from the n-point search model (xyz / nrm: n x 3, host pointers; synchronous), for
+ * an object that has no PPFMap.txt yet, and installed exactly as pgp_set_ppf_map(keys, counts, pairs) installs it: the
+ * hash set, the pair lists and their offsets, the model angles of pgp_set_ppf_model redone, a resident congruent batch
+ * discarded.  The pair lists never visit the host; *n_keys / *n_pairs (nullable) receive the table's size.
+ * The table: every ordered pair (i, j), i != j, of the model is filed under the key computePPF(i, j)
+ * (base.cc:582-598: u = p_i - p_j, the distance in mm binned to 5, the angles (n_i, u), (n_j, u), (n_i, n_j) binned to
+ * 10 degrees, approximate_bin base.cc:150-160), evaluated by the code that evaluates the scene's pairs, with the
+ * host-measured atan2f thresholds; the normals are used as given, like pgp_set_scene's, so pgp_ppf_features of the
+ * same cloud set as a scene returns the same four integers.  A pair whose feature is no key (a non-finite input) is
+ * left out.  Keys come in std::map<std::vector<int>, ...> order (lexicographic), the pairs of a key in ascending
+ * (i, j) -- the order a double loop over the model inserts them; the result is bitwise the same from run to run.
+ * PGP_EINVAL: n outside 2 .. PGP_PPF_BUILD_MAX_POINTS, a null xyz / nrm, or a model whose finite points span more
+ * than PGP_PPF_BUILD_MAX_MM millimetres (the distance field of the 64-bit sort keys).  The previous table survives
+ * these; a failure later in the build (PGP_ENOMEM, PGP_EHIP) leaves the context without a table.
+ * Memory: 16 n^2 bytes of sort keys (two buffers of 8 n^2; 2 x 0.5 GB at the cap) plus rocPRIM's scratch (a few MB)
+ * while the call runs, all released before it returns; what stays is what pgp_set_ppf_map holds: 8 bytes per pair,
+ * 4 per key of offsets and <= 48 per key of hash set. */
+#define PGP_PPF_BUILD_MAX_POINTS 8192
+#define PGP_PPF_BUILD_MAX_MM 10000000
+int pgp_set_ppf_map_from_model(pgp_ctx* ctx, const float* xyz, const float* nrm, int n, int* n_keys, long long* n_pairs);
+
+/* Reads the installed table back in pgp_set_ppf_map's layout (to write PPFMap.txt, or to fill the std::map of an
+ * unmodified node): keys[cap_keys][4], counts[cap_keys], pairs[cap_pairs][2], each nullable.  *n_keys / *n_pairs
+ * (nullable) receive the FULL counts, which may exceed the caps; the arrays are filled up to their caps.  A row whose
+ * key no lookup can reach (pgp_set_ppf_map was handed a repeated or an out-of-range key) reads {-1, -1, -1, -1}.
+ * PGP_ESTATE without a table, or when `pairs` is asked for and the table was set without pair lists. */
+int pgp_get_ppf_map(pgp_ctx* ctx, int* keys, int* counts, int* pairs, int cap_keys, long long cap_pairs, int* n_keys,
+                    long long* n_pairs);
+
 /* Replaces n_attempts calls of Match4PCSBase::SelectQuadrilateralStoCS (base.cc:600-792; the
  * reference seeds a fresh engine per call, so attempts are independent) + TryQuadrilateral
  * (:415-464) in ONE launch, on the scene set by pgp_set_scene (positions, normals, weights =
@@ -1007,6 +1036,10 @@ int pgp_multi_set_object_scene_weights(pgp_multi* m, int obj, const float* weigh
 int pgp_multi_set_object_model(pgp_multi* m, int obj, const float* xyz, const float* nrm, int n);
 int pgp_multi_set_object_search_model(pgp_multi* m, int obj, const float* xyz, int n);
 int pgp_multi_set_object_ppf_map(pgp_multi* m, int obj, const int* keys, const int* counts, const int* pairs, int n_keys);
+/* pgp_set_ppf_map_from_model on every member's context of the object: each member builds its own copy (nothing but
+ * the n points and normals crosses to it); the counts are member 0's, and every member's are the same. */
+int pgp_multi_set_object_ppf_map_from_model(pgp_multi* m, int obj, const float* xyz, const float* nrm, int n, int* n_keys,
+                                            long long* n_pairs);
 int pgp_multi_flat_slices(const int* n_h, int n_obj, int k, int n_dev, int* obj, int* lo, int* hi, int* n_pieces);
 int pgp_multi_score_objects(pgp_multi* m, const float* const* T, const int* n_h, int n_obj, int mode, float gate_deg,
                             float* scores, int* counts, int* best_index, float* best_score);

@@ -151,6 +151,8 @@ SIGNATURES = {
     "pgp_running_best": (C.c_int, [_f, C.c_int, _i, _i]),
     "pgp_set_search_model": (C.c_int, [C.c_void_p, _f, C.c_int]),
     "pgp_set_ppf_map": (C.c_int, [C.c_void_p, _i, _i, _i, C.c_int]),
+    "pgp_set_ppf_map_from_model": (C.c_int, [C.c_void_p, _f, _f, C.c_int, _i, C.POINTER(C.c_longlong)]),
+    "pgp_get_ppf_map": (C.c_int, [C.c_void_p, _i, _i, _i, C.c_int, C.c_longlong, _i, C.POINTER(C.c_longlong)]),
     "pgp_select_bases": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, _i, _f, _i]),
     "pgp_select_bases_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, _i, _f, _i, _i]),
     "pgp_select_bases_rows_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
@@ -249,6 +251,7 @@ SIGNATURES = {
     "pgp_multi_set_object_model": (C.c_int, [C.c_void_p, C.c_int, _f, _f, C.c_int]),
     "pgp_multi_set_object_search_model": (C.c_int, [C.c_void_p, C.c_int, _f, C.c_int]),
     "pgp_multi_set_object_ppf_map": (C.c_int, [C.c_void_p, C.c_int, _i, _i, _i, C.c_int]),
+    "pgp_multi_set_object_ppf_map_from_model": (C.c_int, [C.c_void_p, C.c_int, _f, _f, C.c_int, _i, C.POINTER(C.c_longlong)]),
     "pgp_multi_flat_slices": (C.c_int, [_i, C.c_int, C.c_int, C.c_int, _i, _i, _i, _i]),
     "pgp_multi_score_objects": (C.c_int, [C.c_void_p, C.POINTER(_f), _i, C.c_int, C.c_int, C.c_float, _f, _i, _i, _f]),
     "pgp_multi_upload_objects": (C.c_int, [C.c_void_p, C.POINTER(_f), _i, C.c_int]),

@@ -964,6 +964,17 @@ int pgp_multi_set_object_ppf_map(pgp_multi* m, int obj, const int* keys, const i
   return run_all(m, [=](int k) -> int { return pgp_set_ppf_map(m->octx[(size_t)obj][(size_t)k], keys, counts, pairs, n_keys); });
 }
 
+int pgp_multi_set_object_ppf_map_from_model(pgp_multi* m, int obj, const float* xyz, const float* nrm, int n, int* n_keys,
+                                            long long* n_pairs) {
+  if (bad_object(m, obj, "pgp_multi_set_object_ppf_map_from_model")) return PGP_EINVAL;
+  m->cs_lo[(size_t)obj].clear();
+  // (every member builds its own copy; member 0 reports the size)
+  return run_all(m, [=](int k) -> int {
+    return pgp_set_ppf_map_from_model(m->octx[(size_t)obj][(size_t)k], xyz, nrm, n, k == 0 ? n_keys : nullptr,
+                                      k == 0 ? n_pairs : nullptr);
+  });
+}
+
 int pgp_multi_set_scene(pgp_multi* m, const float* xyz, const float* nrm, const float* weight, int n, float delta) {
   return pgp_multi_set_object_scene(m, 0, xyz, nrm, weight, n, delta);
 }

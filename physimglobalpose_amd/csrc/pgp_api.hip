@@ -1079,6 +1079,38 @@ int pgp_set_ppf_map(pgp_ctx* ctx, const int* keys, const int* counts, const int*
   return set_ppf_map(ctx, keys, counts, pairs, n_keys);
 }
 
+int pgp_set_ppf_map_from_model(pgp_ctx* ctx, const float* xyz, const float* nrm, int n, int* n_keys, long long* n_pairs) {
+  if (!ctx || !xyz || !nrm || n < 2 || n > PGP_PPF_BUILD_MAX_POINTS) {
+    set_error("pgp_set_ppf_map_from_model: bad argument (n=%d, 2 .. %d points with normals)", n, PGP_PPF_BUILD_MAX_POINTS);
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  PGP_HIP(hipDeviceSynchronize());
+  int nk = 0;
+  long long np = 0;
+  const int rc = build_ppf_map(ctx, xyz, nrm, n, &nk, &np);
+  if (rc != PGP_OK) return rc;
+  if (n_keys) *n_keys = nk;
+  if (n_pairs) *n_pairs = np;
+  return PGP_OK;
+}
+
+int pgp_get_ppf_map(pgp_ctx* ctx, int* keys, int* counts, int* pairs, int cap_keys, long long cap_pairs, int* n_keys,
+                    long long* n_pairs) {
+  if (!ctx || cap_keys < 0 || cap_pairs < 0) {
+    set_error("pgp_get_ppf_map: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  int nk = 0;
+  long long np = 0;
+  const int rc = get_ppf_map(ctx, keys, counts, pairs, cap_keys, cap_pairs, &nk, &np);
+  if (rc != PGP_OK) return rc;
+  if (n_keys) *n_keys = nk;
+  if (n_pairs) *n_pairs = np;
+  return PGP_OK;
+}
+
 int pgp_select_bases(pgp_ctx* ctx, const double* u, int n_attempts, int* ids, float* invariants, int* status) {
   if (!ctx || n_attempts < 0 || (n_attempts > 0 && (!u || !ids || !invariants || !status))) {
     set_error("pgp_select_bases: bad argument");

@@ -529,6 +529,11 @@ int launch_stage_weights(pgp_ctx* ctx, int stage, int b1, int b2, int b3, float*
                          hipStream_t st);
 int launch_base_invariants(pgp_ctx* ctx, int* h_ids, int m, float* h_inv, int* h_ok, hipStream_t st);
 
+// ppf_build.hip: the table built from the search model (pgp_set_ppf_map_from_model) and read back (pgp_get_ppf_map)
+int build_ppf_map(pgp_ctx* ctx, const float* xyz, const float* nrm, int n, int* n_keys_out, long long* n_pairs_out);
+int get_ppf_map(pgp_ctx* ctx, int* keys, int* counts, int* pairs, int cap_keys, long long cap_pairs, int* n_keys_out,
+                long long* n_pairs_out);
+
 // physics.hip
 constexpr int PHYS_TRACE_STATE = 13, PHYS_TRACE_CONTACT = 8;   // floats per step / per contact of pgp_physics_trace
 constexpr int PHYS_MAX_STEPS = 100000, PHYS_MAX_TRACE_STEPS = 10000;

@@ -195,6 +195,31 @@ class LcpScorer:
                                              None if c is None else c.ctypes.data_as(_i),
                                              None if p is None else p.ctypes.data_as(_i), len(keys)))
 
+    def set_ppf_map_from_model(self, xyz, nrm):
+        """pgp_set_ppf_map_from_model: the pair-feature table of the search model (xyz, nrm: (n,3)) built on the device and
+        installed as set_ppf_map(keys, counts, pairs) would -> (n_keys, n_pairs)."""
+        xyz, nrm = _f32(xyz, 3), _f32(nrm, 3)
+        assert len(xyz) == len(nrm)
+        nk, np_ = C.c_int(0), C.c_longlong(0)
+        _lib.check(self._lib.pgp_set_ppf_map_from_model(self._h, _fp(xyz), _fp(nrm), len(xyz), C.byref(nk), C.byref(np_)))
+        return nk.value, np_.value
+
+    def get_ppf_map(self, cap_keys=None, cap_pairs=None, pairs=True):
+        """pgp_get_ppf_map: the installed table in set_ppf_map's layout -> (keys (k,4), counts (k,), pairs (p,2) or None).
+        With caps the arrays are cut to them (the counts stay the full counts of their keys)."""
+        nk, np_ = C.c_int(0), C.c_longlong(0)
+        _lib.check(self._lib.pgp_get_ppf_map(self._h, None, None, None, 0, 0, C.byref(nk), C.byref(np_)))
+        ck = nk.value if cap_keys is None else int(cap_keys)
+        cp = np_.value if cap_pairs is None else int(cap_pairs)
+        keys = np.zeros((max(ck, 1), 4), np.int32)
+        counts = np.zeros(max(ck, 1), np.int32)
+        pr = np.zeros((max(cp, 1), 2), np.int32) if pairs else None
+        _lib.check(self._lib.pgp_get_ppf_map(self._h, keys.ctypes.data_as(_i), counts.ctypes.data_as(_i),
+                                             None if pr is None else pr.ctypes.data_as(_i), ck, C.c_longlong(cp),
+                                             C.byref(nk), C.byref(np_)))
+        k, p = min(ck, nk.value), min(cp, np_.value)
+        return keys[:k], counts[:k], (None if pr is None else pr[:p])
+
     def select_bases(self, u, rows=False):
         """u (n,4) float64 uniforms in [0,1) -> (ids (n,4), invariants (n,2), status (n,)); rows=True: also the pair-feature
         table rows (n,2) of every base's two edges (pgp_select_bases_rows)."""
@@ -1326,6 +1351,15 @@ class MultiGpuScorer:
         _lib.check(self._lib.pgp_multi_set_object_ppf_map(
             self._h, int(obj), k.ctypes.data_as(_i), None if c is None else c.ctypes.data_as(_i),
             None if p is None else p.ctypes.data_as(_i), len(k)))
+
+    def set_object_ppf_map_from_model(self, obj, xyz, nrm):
+        """pgp_multi_set_object_ppf_map_from_model: every member builds the object's table itself -> (n_keys, n_pairs)."""
+        q, qn = _f32(xyz, 3), _f32(nrm, 3)
+        assert len(q) == len(qn)
+        nk, np_ = C.c_int(0), C.c_longlong(0)
+        _lib.check(self._lib.pgp_multi_set_object_ppf_map_from_model(self._h, int(obj), _fp(q), _fp(qn), len(q), C.byref(nk),
+                                                                     C.byref(np_)))
+        return nk.value, np_.value
 
     @staticmethod
     def flat_slices(counts, k, n_dev):
