@@ -56,6 +56,7 @@
 //     cells of edge max_corr, 27 cells per query, identical (d2, lowest j) results to the scan.
 
 #include "pgp_internal.h"
+#include "icp_plan.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -3282,11 +3283,8 @@ static const void* persist_kernel_at(int k) {
 #undef PGP_PK
   return tab[k];
 }
-static const void* persist_kernel(int metric, bool img_lds, bool cluster, bool trim_only, int n_src) {
-  if (metric != 1 && img_lds) {
-    const int r = n_src <= 2 * kIcpBase ? 0 : (n_src <= 3 * kIcpBase ? 1 : 2);
-    return persist_kernel_at((cluster ? 6 : 0) + (trim_only ? 3 : 0) + r);
-  }
+static const void* persist_kernel(int metric, bool img_lds, bool cluster, bool trim_only, int pir) {   // pir: class 2 / 3 / 4
+  if (metric != 1 && img_lds) return persist_kernel_at((cluster ? 6 : 0) + (trim_only ? 3 : 0) + (pir - 2));
   if (metric == 1 && img_lds) return persist_kernel_at(cluster ? 13 : 12);
   return persist_kernel_at(14 + (metric == 1 ? 2 : 0) + (cluster ? 1 : 0));
 }
@@ -3325,15 +3323,49 @@ static int ensure_icp_attrs(pgp_ctx* ctx) {
   return PGP_OK;
 }
 
-// Builds the exact index of the target in ctx->d_icp_grid (image | counters | starts | keys) when its
+static_assert(kPiR * kIcpThreads == kPlanPoseSrcMax && kIcpBase == kPlanClassBase && kMaxSmooth == kPlanSmoothMax &&
+                  kIcpMultiMax == kPlanMultiMax, "icp_plan.h states the kernels' limits");
+
+// The knobs of the ICP host side (icp_plan.h IcpEnv), read at every launch: a test changes them between calls.
+static IcpEnv icp_env() {
+  IcpEnv e;
+  const auto on = [](const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; };
+  if (const char* v = getenv("PGP_ICP_NN")) e.nn = !strcmp(v, "scan") ? 1 : (!strcmp(v, "index") ? 2 : 3);
+  if (const char* v = getenv("PGP_ICP_SPLIT")) e.split = atoi(v) != 0;
+  if (const char* v = getenv("PGP_ICP_PERSIST")) e.persist = atoi(v) != 0;
+  e.scene_persist = on("PGP_ICP_SCENE_PERSIST", true);
+  e.part = on("PGP_ICP_PART", true);
+  e.open_grid = on("PGP_ICP_OPEN_GRID", true);
+  e.multi = on("PGP_ICP_MULTI", true);
+  e.help = on("PGP_ICP_HELP", false);
+  if (const char* v = getenv("PGP_ICP_WGS")) e.wgs = atoi(v) == 4 ? 4 : (atoi(v) == 2 ? 2 : 1);
+  if (const char* v = getenv("PGP_ICP_IMAGE")) e.image_global = !strcmp(v, "global");
+  if (const char* v = getenv("PGP_ICP_CELL")) e.cell = atof(v);
+  if (const char* v = getenv("PGP_ICP_ASPECT")) e.aspect = fmax(1.0, atof(v));
+  e.vic = on("PGP_ICP_VIC", true);
+  if (const char* v = getenv("PGP_ICP_FIRST_WALK")) e.first_walk = atoi(v) < 0 ? 0 : atoi(v);
+  if (const char* v = getenv("PGP_ICP_SOLO_TICKS")) e.solo_ticks = (unsigned)atoi(v);
+  if (const char* v = getenv("PGP_ICP_OPEN_CELL")) e.open_cell = atof(v) > 0.0 ? atof(v) : e.open_cell;
+  if (const char* v = getenv("PGP_ICP_SCENE_WGS")) e.scene_wgs = (unsigned)atoi(v);
+  if (const char* v = getenv("PGP_ICP_SCENE_SLEEP")) e.scene_sleep = atoi(v);
+  if (const char* v = getenv("PGP_ICP_DBG_POSE")) e.dbg_pose = atoi(v);
+  if (const char* v = getenv("PGP_ICP_SLOTS")) e.slots = atoi(v);
+  if (const char* v = getenv("PGP_ICP_ROWS")) e.rows = atoi(v);
+  e.cooperative = on("PGP_COOPERATIVE_LAUNCH", false);
+  if (const char* v = getenv("PGP_ICP_WAIT_MS")) e.wait_ms = atof(v) > 0.0 ? atof(v) : e.wait_ms;
+  e.force_lost = getenv("PGP_ICP_FORCE_LOST") != nullptr;
+  e.debug = getenv("PGP_ICP_DEBUG") != nullptr;
+  return e;
+}
+
+// Builds the exact index of the target in ctx->d_icp_grid (image | counters | starts | keys | vicinity graph) when its
 // image fits one workgroup's LDS.  *fits = false (and PGP_OK): the caller keeps the exhaustive search.
-static int build_nn_index(pgp_ctx* ctx, const float4* d_tgt, int n_tgt, int n_q, IcpArgs* a, bool* fits, hipStream_t stream,
-                          unsigned long long token) {
+static int build_nn_index(pgp_ctx* ctx, const IcpEnv& env, const float4* d_tgt, int n_tgt, int n_q, IcpArgs* a, bool* fits,
+                          hipStream_t stream, unsigned long long token) {
   *fits = false;
   static_assert(sizeof(NnGeom) <= sizeof(ctx->icp_idx_geom), "NnGeom outgrew its slot in the context");
   constexpr int kLdsBytes = 160 * 1024, kScratch = 8 * 1024;   // static LDS of icp_persist_index + slack
-  bool force_global = false;
-  if (const char* v = getenv("PGP_ICP_IMAGE")) force_global = !strcmp(v, "global");   // A/B knob
+  const bool force_global = env.image_global;
   if (token != 0 && ctx->icp_idx_valid && ctx->icp_idx_token == token && ctx->icp_idx_tgt == (const void*)d_tgt &&
       ctx->icp_idx_ntgt == n_tgt) {
     NnGeom g;
@@ -3368,11 +3400,9 @@ static int build_nn_index(pgp_ctx* ctx, const float4* d_tgt, int n_tgt, int n_q,
   for (int k = 0; k < 3; ++k) ext[k] = fmax((double)bb[3 + k] - (double)bb[k], 1e-6);
   // cell edge from the spacing of a surface sampling of the box: ~3 points per occupied cell
   const double area = 2.0 * (ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0]);
-  double h = 1.7 * sqrt(area / (double)n_tgt);
-  if (const char* v = getenv("PGP_ICP_CELL")) h *= atof(v);       // tuning: cell edge multiplier
+  double h = 1.7 * sqrt(area / (double)n_tgt) * env.cell;
   // cells are plates: a * h in y and z, h / a^2 along x (same volume, same points per cell)
-  double aspect = 1.8;   // measured flat over 1.7 .. 2 (tools/icp_time.py), 20 % faster than cubes
-  if (const char* v = getenv("PGP_ICP_ASPECT")) aspect = fmax(1.0, atof(v));
+  const double aspect = env.aspect;   // 1.8: measured flat over 1.7 .. 2 (tools/icp_time.py), 20 % faster than cubes
   NnGeom g{};
   double hx, hyz;
   for (;;) {
@@ -3402,26 +3432,30 @@ static int build_nn_index(pgp_ctx* ctx, const float4* d_tgt, int n_tgt, int n_q,
   g.bytes = (g.off_rep + (uint32_t)g.n_cells * 2u + 15u) & ~15u;
   if (in_lds && (long long)nn_lds_bytes(g.bytes, n_q) + kScratch > kLdsBytes) in_lds = false;
   const size_t nc1 = (size_t)g.n_cells + 1;
-  const size_t off_ctr = ((size_t)g.bytes + 255) & ~(size_t)255, off_st = off_ctr + ((nc1 * 4 + 255) & ~(size_t)255),
-               off_key = off_st + ((nc1 * 4 + 255) & ~(size_t)255),
-               off_vic = (off_key + (size_t)g.n_cells * 8 + 255) & ~(size_t)255;
-  bool want_vic = n_tgt <= kVicMaxTargets;
-  if (const char* v = getenv("PGP_ICP_VIC")) want_vic = want_vic && atoi(v) != 0;   // A/B knob: 0 = searches only
+  const bool want_vic = n_tgt <= kVicMaxTargets && env.vic;
   const int vic_chunks = (n_tgt + kVicChunk - 1) / kVicChunk;
-  if ((rc = ctx->d_icp_grid.ensure(off_vic + (want_vic ? (size_t)n_tgt * 16 : 0) + 256)) != PGP_OK) return rc;
-  if (want_vic && (rc = ctx->d_icp_ws.ensure((size_t)vic_chunks * n_tgt * (kVicK + 1) * 8 + 64)) != PGP_OK) return rc;
+  Carve cv, cw;   // d_icp_grid: the image and its build area; d_icp_ws: the vicinity graph's partial lists
+  const auto p_image = cv.add<unsigned char>(g.bytes);
+  const auto p_ctr = cv.add<uint32_t>(nc1, 256), p_start = cv.add<uint32_t>(nc1, 256);
+  const auto p_key = cv.add<unsigned long long>((size_t)g.n_cells, 256);
+  const auto p_vic = cv.add<uint4>(want_vic ? (size_t)n_tgt : 0, 256);
+  cv.pad(256);
+  const auto p_part = cw.add<float2>((size_t)vic_chunks * n_tgt * (kVicK + 1));
+  cw.pad(64);
+  if ((rc = cv.ensure(ctx->d_icp_grid)) != PGP_OK) return rc;
+  if (want_vic && (rc = cw.ensure(ctx->d_icp_ws)) != PGP_OK) return rc;
   if ((rc = ctx->d_scan_tmp.ensure((nc1 / 2048 + 2) * 4)) != PGP_OK) return rc;
-  unsigned char* image = ctx->d_icp_grid.as<unsigned char>();
-  uint32_t* ctr = reinterpret_cast<uint32_t*>(image + off_ctr);
-  uint32_t* start = reinterpret_cast<uint32_t*>(image + off_st);
-  unsigned long long* key = reinterpret_cast<unsigned long long*>(image + off_key);
+  unsigned char* image = cv.at(p_image);
+  uint32_t* ctr = cv.at(p_ctr);
+  uint32_t* start = cv.at(p_start);
+  unsigned long long* key = cv.at(p_key);
   const dim3 gt((n_tgt + 255) / 256);
-  PGP_HIP(hipMemsetAsync(ctr, 0, nc1 * 4, stream));
+  PGP_HIP(hipMemsetAsync(ctr, 0, p_ctr.bytes(), stream));
   hipLaunchKernelGGL(nnidx_scatter<false>, gt, dim3(256), 0, stream, d_tgt, n_tgt, g, ctr, (const uint32_t*)nullptr,
                      (float4*)nullptr);
   if ((rc = device_exclusive_scan(ctr, start, nc1, ctx->d_scan_tmp.as<uint32_t>(), stream)) != PGP_OK) return rc;
-  PGP_HIP(hipMemsetAsync(ctr, 0, nc1 * 4, stream));
-  PGP_HIP(hipMemsetAsync(key, 0xFF, (size_t)g.n_cells * 8, stream));
+  PGP_HIP(hipMemsetAsync(ctr, 0, p_ctr.bytes(), stream));
+  PGP_HIP(hipMemsetAsync(key, 0xFF, p_key.bytes(), stream));
   hipLaunchKernelGGL(nnidx_scatter<true>, gt, dim3(256), 0, stream, d_tgt, n_tgt, g, ctr, (const uint32_t*)start,
                      reinterpret_cast<float4*>(image));
   hipLaunchKernelGGL(nnidx_rep, dim3((g.n_cells + 255) / 256, (n_tgt + 511) / 512), dim3(256), 0, stream,
@@ -3429,18 +3463,17 @@ static int build_nn_index(pgp_ctx* ctx, const float4* d_tgt, int n_tgt, int n_q,
   hipLaunchKernelGGL(nnidx_pack, dim3((g.n_cells + 1 + 255) / 256), dim3(256), 0, stream, g, (const uint32_t*)start,
                      (const unsigned long long*)key, image);
   if (want_vic) {   // the vicinity graph over the points in image order
-    float2* part = ctx->d_icp_ws.as<float2>();
-    uint4* vic = reinterpret_cast<uint4*>(image + off_vic);
+    float2* part = cw.at(p_part);
     hipLaunchKernelGGL(nnidx_vic_partial, dim3((n_tgt + 63) / 64, vic_chunks), dim3(64), 0, stream,
                        reinterpret_cast<const float4*>(image), n_tgt, part);
-    hipLaunchKernelGGL(nnidx_vic_merge, dim3((n_tgt + 63) / 64), dim3(64), 0, stream, (const float2*)part, n_tgt, vic_chunks, vic);
+    hipLaunchKernelGGL(nnidx_vic_merge, dim3((n_tgt + 63) / 64), dim3(64), 0, stream, (const float2*)part, n_tgt, vic_chunks, cv.at(p_vic));
   }
   PGP_HIP(hipGetLastError());
   a->nn = g;
   a->nn_image = image;
   a->nn_image_in_lds = in_lds ? 1 : 0;
-  a->nn_vic = want_vic ? reinterpret_cast<const uint4*>(image + off_vic) : nullptr;
-  ctx->icp_idx_vic_off = want_vic ? off_vic : 0;
+  a->nn_vic = want_vic ? cv.at(p_vic) : nullptr;
+  ctx->icp_idx_vic_off = want_vic ? p_vic.off : 0;
   *fits = true;
   memcpy(ctx->icp_idx_geom, &g, sizeof g);
   ctx->icp_idx_valid = token != 0;
@@ -3463,20 +3496,6 @@ struct CoopChain {
 CoopChain g_coop;
 }  // namespace
 
-// The host-pointer call redoes a scene-sized job whose one-launch form reported a pose as lost (iteration count -1: its
-// units did not arrive within the clock bound) with the host-driven iterations: this thread's next launch_icp calls.
-// The floor of the clock bounds of the kernels whose workgroups wait for each other, in ticks of the 100 MHz counter: 3 ms --
-// two orders above an iteration (~25 us), three below the 2 s of round 5.  PGP_ICP_WAIT_MS overrides it (tests).
-static unsigned icp_wait_ticks() {   // (read at every launch: a test changes it between calls)
-  double ms = 3.0;
-  if (const char* v = getenv("PGP_ICP_WAIT_MS")) ms = atof(v) > 0.0 ? atof(v) : ms;
-  const double t = ms * 1e5;
-  return (unsigned)(t < 100.0 ? 100.0 : (t > 4.0e9 ? 4.0e9 : t));
-}
-
-static thread_local bool t_scene_form_off = false;
-void icp_scene_form_off(bool off) { t_scene_form_off = off; }
-
 // A launch whose workgroups wait for each other (the clustered, the helping and the scene-sized kernels).  By default a
 // PLAIN launch of a grid that fits on the device at the kernel's occupancy: on an idle or lightly shared device every
 // workgroup is resident at once; behind somebody else's long kernel the late ones arrive when it ends, and every wait in
@@ -3485,10 +3504,14 @@ void icp_scene_form_off(bool off) { t_scene_form_off = off; }
 // that queue, once it exists, makes the hardware scheduler time-slice the device between processes: every OTHER process
 // on the GPU (the node's segmentation network, say) then meets stalls of ~11 ms although this one is idle (measured:
 // tools/child_under_parent.py, profiles/r05_ab/cooperative_queue_stalls.log).  PGP_COOPERATIVE_LAUNCH=1: the runtime's form.
-static hipError_t launch_resident(pgp_ctx* ctx, const void* fn, unsigned grid, unsigned threads, void** params, unsigned lds,
-                                  hipStream_t stream) {
-  const char* coop = getenv("PGP_COOPERATIVE_LAUNCH");
-  if (coop && atoi(coop) != 0) return hipLaunchCooperativeKernel(fn, dim3(grid), dim3(threads), params, lds, stream);
+struct ResidentKernel {
+  const void* fn = nullptr;   // null: nothing to launch (the chain reports hipErrorInvalidValue)
+  unsigned grid = 0, threads = 0;
+  void** params = nullptr;
+  unsigned lds = 0;
+};
+static hipError_t launch_resident(pgp_ctx* ctx, bool cooperative, const ResidentKernel& k, hipStream_t stream) {
+  if (cooperative) return hipLaunchCooperativeKernel(k.fn, dim3(k.grid), dim3(k.threads), k.params, k.lds, stream);
   struct Known {
     const void* fn;
     unsigned threads, lds;
@@ -3499,31 +3522,66 @@ static hipError_t launch_resident(pgp_ctx* ctx, const void* fn, unsigned grid, u
   int per_cu = -1;
   {
     std::lock_guard<std::mutex> lk(mu);
-    for (const Known& k : known)
-      if (k.fn == fn && k.threads == threads && k.lds == lds) per_cu = k.per_cu;
+    for (const Known& q : known)
+      if (q.fn == k.fn && q.threads == k.threads && q.lds == k.lds) per_cu = q.per_cu;
     if (per_cu < 0) {
       int v = 0;
-      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, (int)threads, lds);
+      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k.fn, (int)k.threads, k.lds);
       if (e != hipSuccess) return e;
       per_cu = v;
-      known.push_back(Known{fn, threads, lds, v});
+      known.push_back(Known{k.fn, k.threads, k.lds, v});
     }
   }
-  if ((long long)grid > (long long)per_cu * ctx->n_cus) return hipErrorCooperativeLaunchTooLarge;
-  return hipLaunchKernel(fn, dim3(grid), dim3(threads), params, lds, stream);
+  if ((long long)k.grid > (long long)per_cu * ctx->n_cus) return hipErrorCooperativeLaunchTooLarge;
+  return hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.threads), k.params, k.lds, stream);
 }
 
-// the options of a call (pgp_icp_options) as kernel arguments; k_trim = the trimmed count of a cloud of n_src points
-static int icp_trim_count(const pgp_icp_options* prm, int n_src) {
-  float tf = prm->trim_fraction;
-  if (!(tf > 0.f) || tf > 1.f) tf = 1.f;
-  // float numPoints = trim * size; align(..., abs(numPoints), ...) -> int (UCTState.cpp:176,194)
-  int k = (int)fabsf(tf * (float)n_src);
-  if (k < 1) k = 1;
-  if (k > n_src) k = n_src;
-  return k;
+// what the launchers of the forms share
+struct IcpCall {
+  pgp_ctx* ctx;
+  hipStream_t stream;
+  const IcpEnv& env;
+  const IcpPlan& plan;
+  int n, n_src, n_tgt;
+  size_t need() const { return (size_t)n * n_src; }
+};
+
+// The chain of one resident launch.  Under the chain's lock: the previous resident launch of this device (any stream of this
+// process) has finished before prepare() (re)allocates and clears this one's buffers and names its kernel; the kernel goes
+// through launch_resident; behind() queues what belongs behind it; the device's event is recorded.  *e = the launch's
+// result: anything but hipSuccess (the grid does not fit on this device at the kernel's occupancy) leaves the stream
+// without the kernel and the caller takes the plan's fall-back.
+template <class Prepare, class Behind>
+static int launch_chained(const IcpCall& c, Prepare&& prepare, Behind&& behind, hipError_t* e) {
+  const int dev = c.ctx->device >= 0 && c.ctx->device < 64 ? c.ctx->device : 0;
+  std::lock_guard<std::mutex> chain(g_coop.mu);
+  if (g_coop.last[dev]) PGP_HIP(hipStreamWaitEvent(c.stream, g_coop.last[dev], 0));
+  else PGP_HIP(hipEventCreateWithFlags(&g_coop.last[dev], hipEventDisableTiming));
+  ResidentKernel k;
+  int rc;
+  if ((rc = prepare(&k)) != PGP_OK) return rc;
+  *e = k.fn ? launch_resident(c.ctx, c.env.cooperative, k, c.stream) : hipErrorInvalidValue;
+  if (*e != hipSuccess) {
+    (void)hipGetLastError();
+    return PGP_OK;
+  }
+  if ((rc = behind()) != PGP_OK) return rc;
+  PGP_HIP(hipEventRecord(g_coop.last[dev], c.stream));
+  PGP_HIP(hipGetLastError());
+  return PGP_OK;
 }
-static void icp_option_args(const pgp_icp_options* prm, int n_src, IcpArgs* a) {
+static int nothing_behind() { return PGP_OK; }
+
+// (an error of the query counts as capturing: the forms that cannot be captured are not taken)
+static bool stream_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+}
+
+// the options of a call (pgp_icp_options) and the knobs every form reads, as kernel arguments
+static void icp_option_args(const pgp_icp_options* prm, const IcpEnv& env, int n_src, IcpArgs* a) {
+  a->first_walk = env.first_walk;
+  a->wait_ticks = icp_wait_ticks(env);
   a->max_iter = prm->max_iterations > 0 ? prm->max_iterations : 100;
   a->k_trim = icp_trim_count(prm, n_src);
   a->max_corr2 = prm->max_corr_dist > 0.f ? prm->max_corr_dist * prm->max_corr_dist : -1.f;
@@ -3534,515 +3592,437 @@ static void icp_option_args(const pgp_icp_options* prm, int n_src, IcpArgs* a) {
   a->abs_mse = prm->absolute_mse;
   a->diff_rot = prm->min_diff_rot;
   a->diff_trans = prm->min_diff_trans;
-  a->smooth = (prm->min_diff_rot > 0.f && prm->min_diff_trans > 0.f)
-                  ? (prm->smooth_length < 1 ? 1 : (prm->smooth_length > kMaxSmooth ? kMaxSmooth : prm->smooth_length))
-                  : 0;
+  a->smooth = icp_smooth(prm);
 }
-static bool icp_trim_only(const IcpArgs& a) {
-  return !(a.max_corr2 >= 0.f) && !(a.t_eps >= 0.f || a.rel_mse > 0.f || a.abs_mse >= 0.f || a.smooth > 0);
+static int icp_fail(const IcpError& e) {
+  set_error("%s", e.msg);
+  return e.rc;
+}
+static size_t hist_doubles(const IcpArgs& a, int n) { return a.smooth > 0 ? (size_t)n * (kMaxSmooth + 1) * 7 : 0; }
+
+// ---- the forms with one launch for all iterations of a pose, the index in one workgroup's reach --------------------------
+
+static const void* per_pose_kernel(const IcpCall& c, const IcpArgs& a, bool cluster) {
+  return persist_kernel(a.metric, a.nn_image_in_lds != 0, cluster, c.plan.trim_only, c.plan.pir);
+}
+static unsigned per_pose_lds(const IcpCall& c, const IcpArgs& a) { return (unsigned)nn_lds_bytes(a.nn.bytes, c.n_src, a.nn_image_in_lds != 0); }
+
+// one workgroup per pose
+static int launch_per_pose(const IcpCall& c, IcpArgs& a) {
+  void* params[] = {&a};
+  PGP_HIP(hipLaunchKernel(per_pose_kernel(c, a, false), dim3(c.n), dim3(kIcpThreads), params, per_pose_lds(c, a), c.stream));
+  PGP_HIP(hipGetLastError());
+  return PGP_OK;
 }
 
-int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt, const float4* d_tgt_n, int n_tgt,
-               float* d_T, int n, const pgp_icp_options* prm, float* d_energy, int* d_iters, hipStream_t stream,
-               unsigned long long tgt_token) {
-  if (n <= 0) return PGP_OK;
-  if (n_src <= 0 || n_tgt <= 0) {
-    set_error("icp: empty source or target cloud");
-    return PGP_EINVAL;
-  }
-  if (prm->error_metric == 1 && !d_tgt_n) {
-    set_error("icp: the point-to-plane metric needs target normals");
-    return PGP_EINVAL;
-  }
-  if (prm->error_metric != 0 && prm->error_metric != 1) {
-    set_error("icp: unknown error metric %d", prm->error_metric);
-    return PGP_EINVAL;
-  }
-  // the pose index rides on gridDim.z / .y (<= 65535): larger batches go in slices
-  constexpr int kMaxPoses = 32768;
-  if (n > kMaxPoses) {
-    for (int off = 0; off < n; off += kMaxPoses) {
-      const int m = n - off < kMaxPoses ? n - off : kMaxPoses;
-      int rc = launch_icp(ctx, d_src, n_src, d_tgt, d_tgt_n, n_tgt, d_T + 16 * (size_t)off, m, prm,
-                          d_energy ? d_energy + off : nullptr, d_iters ? d_iters + off : nullptr, stream, tgt_token);
-      if (rc != PGP_OK) return rc;
-    }
+// Few poses: 2 or 4 workgroups per pose share the search (64 poses alone would use 64 of the 256 CUs).  They meet once per
+// iteration, so all of them should be resident at once: a grid that fits the device, one workgroup per CU, chained behind
+// the previous such launch (launch_chained).
+static int launch_clustered(const IcpCall& c, IcpArgs& a, bool* launched) {
+  const size_t n = (size_t)c.n, need = c.need();
+  a.wgs_per_pose = c.plan.wgs_per_pose;
+  void* params[] = {&a};
+  hipError_t e = hipSuccess;
+  const int rc = launch_chained(c, [&](ResidentKernel* k) -> int {
+    // meeting buffers | arrival counters, workgroups that have left, abandoned meetings (one fill) | search ticks
+    Carve cv;
+    const auto p_buf = cv.add<unsigned long long>(2 * need);
+    const auto p_ctr = cv.add<unsigned>(3 * n + 4);
+    const auto p_ticks = cv.add<unsigned>(8 * n);
+    cv.pad(64);
+    const void* x_before = c.ctx->d_icp_x.p;
+    const size_t x_cap_before = c.ctx->d_icp_x.cap;
+    int r;
+    if ((r = cv.ensure(c.ctx->d_icp_x)) != PGP_OK) return r;
+    a.x_buf = cv.at(p_buf);
+    a.x_ctr = cv.at(p_ctr);
+    a.x_done = a.x_ctr + n + 4;
+    a.x_abandon = a.x_done + n;
+    a.x_ticks = cv.at(p_ticks);
+    if (c.env.force_lost) a.force_lost = 1;
+    a.solo_ticks = c.env.solo_ticks;
+    // The counters are zero whenever a clustered launch on this context is over (every pose's last workgroup to leave
+    // puts them back, lost meeting or not: cluster_leave): a fill only when these words were not the counters of the
+    // last such launch (first use, a grown buffer, another pose count, the helping launch's layout in between).
+    const bool same_words = c.ctx->icp_x_clean && c.ctx->d_icp_x.p == x_before && c.ctx->d_icp_x.cap == x_cap_before &&
+                            c.ctx->icp_x_n == c.n && c.ctx->icp_x_need == need;
+    if (!same_words) PGP_HIP(hipMemsetAsync(a.x_ctr, 0, p_ctr.bytes(), c.stream));
+    c.ctx->icp_x_clean = true;
+    c.ctx->icp_x_n = c.n;
+    c.ctx->icp_x_need = need;
+    *k = ResidentKernel{per_pose_kernel(c, a, true), (unsigned)(c.n * a.wgs_per_pose), kIcpThreads, params, per_pose_lds(c, a)};
     return PGP_OK;
-  }
-  IcpArgs a{};
-  a.src = d_src;
-  a.tgt = d_tgt;
-  a.tgt_n = d_tgt_n;
-  a.n_src = n_src;
-  a.n_tgt = n_tgt;
-  a.T = d_T;
-  a.n = n;
-  icp_option_args(prm, n_src, &a);
-  a.first_walk = 1;
-  if (const char* v = getenv("PGP_ICP_FIRST_WALK")) a.first_walk = atoi(v) < 0 ? 0 : atoi(v);   // A/B knob
-  a.wait_ticks = icp_wait_ticks();
+  }, nothing_behind, &e);
+  // (nothing behind the kernel: after a lost meeting the pose's workgroup 0 goes on alone inside the launch, icp_persist_body)
+  if (rc != PGP_OK) return rc;
+  if (c.env.debug) fprintf(stderr, "icp: %d poses x %d workgroups, resident launch: %s\n", c.n, a.wgs_per_pose, hipGetErrorString(e));
+  *launched = e == hipSuccess;
+  if (!*launched) a.wgs_per_pose = 1;
+  return PGP_OK;
+}
+
+// One workgroup per pose and all of them resident at once (129 .. 256 poses on 256 compute units): a workgroup
+// that is through with its pose takes search passes of the poses still running (HelpPub) -- the launch then
+// lasts about as long as the MEAN pose, not the slowest.  Launched and chained like the clustered launches; a repair
+// launch behind it (the clustered launch needs none).  Off unless PGP_ICP_HELP=1: measured slower (icp_plan.h).
+static int launch_helping(const IcpCall& c, const IcpArgs& a, bool* launched) {
+  const size_t N = (size_t)c.n, hb = help_bytes(c.n_src);
+  IcpArgs h = a, fix = a;
+  void* hparams[] = {&h};
+  void* fparams[] = {&fix};
+  hipError_t e = hipSuccess;
+  const int rc = launch_chained(c, [&](ResidentKernel* k) -> int {
+    // header, one fill: claim words | slot counts | passes done | finished, lost;  saved transforms;  publications
+    Carve cv;
+    const auto p_ctl = cv.add<unsigned long long>(N);
+    const auto p_words = cv.add<unsigned>(2 * N + 2);
+    const auto p_save = cv.add<float>(16 * N, 256);
+    const auto p_help = cv.add<unsigned char>(N * hb, 256);
+    cv.pad(256);
+    int r;
+    if ((r = cv.ensure(c.ctx->d_icp_x)) != PGP_OK) return r;
+    c.ctx->icp_x_clean = false;   // (the clustered launch's counters live in the same buffer)
+    h.help_ctl = cv.at(p_ctl);
+    h.help_nslots = cv.at(p_words);
+    h.help_done = h.help_nslots + N;
+    h.help_finished = h.help_done + N;
+    h.x_lost = h.help_finished + 1;
+    h.T_save = cv.at(p_save);
+    h.help = cv.at(p_help);
+    h.help_stride = hb;
+    PGP_HIP(hipMemsetAsync(h.help_ctl, 0, p_ctl.bytes() + p_words.bytes(), c.stream));
+    *k = ResidentKernel{help_kernel(c.plan.trim_only, c.plan.pir), (unsigned)c.n, kIcpThreads, hparams, per_pose_lds(c, a)};
+    return PGP_OK;
+  }, [&]() -> int {   // the repair launch: poses the helping launch reported lost, from their saved transforms
+    fix.wgs_per_pose = 1;
+    fix.run_if = h.x_lost;
+    fix.T_in = h.T_save;
+    fix.T_save = nullptr;
+    PGP_HIP(hipLaunchKernel(per_pose_kernel(c, a, false), dim3(c.n), dim3(kIcpThreads), fparams, per_pose_lds(c, a), c.stream));
+    return PGP_OK;
+  }, &e);
+  if (rc != PGP_OK) return rc;
+  if (c.env.debug) fprintf(stderr, "icp: %d poses, helping launch: %s\n", c.n, hipGetErrorString(e));
+  *launched = e == hipSuccess;
+  return PGP_OK;
+}
+
+// ---- the host-driven family: the split workspace, the search's grid, the scene-sized one-launch form ------------------------
+
+// what the host-driven iterations need beside IcpArgs
+struct HostWs {
+  double* d_part = nullptr;    // partial sums by block
+  int* open_list = nullptr;    // open grid: the queries left to the scan, and their count per pose
+  int* open_cnt = nullptr;
+  float open_r2 = 0.f;         // open grid: the squared radius the grid settles
+};
+
+// d_icp_ws of the host-driven forms (the legacy kernel uses its first two pieces only)
+static int carve_split_ws(const IcpCall& c, IcpArgs& a, HostWs* w) {
+  const size_t n = (size_t)c.n, need = c.need();
+  const bool split = c.plan.form != IcpForm::Legacy, open_grid = c.plan.search == IcpSearch::OpenGrid;
+  const bool use_index = c.plan.search == IcpSearch::IndexLds || c.plan.search == IcpSearch::IndexL2;
+  Carve cv;
+  const auto p_d2 = cv.add<float>(need);
+  const auto p_j = cv.add<int>(need);
+  const auto p_key = cv.add<unsigned long long>(split ? need : 0, 16);
+  const auto p_E = cv.add<double>(split ? n : 0);
+  const auto p_state = cv.add<int>(split ? 2 * n + 1 : 0);   // iteration counts | stopped flags | stopped poses: one fill
+  const auto p_hist = cv.add<double>(split ? hist_doubles(a, c.n) : 0, 16);
+  const auto p_pos = cv.add<int>(split && use_index ? need : 0, 16);
+  const auto p_open = cv.add<int>(open_grid ? need : 0, 16);
+  const auto p_open_cnt = cv.add<int>(open_grid ? n : 0);
+  const auto p_part = cv.add<double>(c.plan.part_sums ? n * c.plan.n_blk * kPartStride : 0, 16);
+  cv.pad(64);
   int rc;
-  size_t need = (size_t)n * n_src;
-  // measured (tools/icp_time.py, 2500 x 5000, 10 iterations): the split path wins at every batch
-  // size tried -- 1 pose 1.2 vs 7.7 ms, 64 poses 3.6 vs 12.8 ms, 256 poses 9.4 vs 12.9 ms -- so it
-  // is the default; PGP_ICP_SPLIT=0 selects the single-launch persistent kernel (fully
-  // asynchronous, graph-capturable)
-  bool split = true;
-  if (const char* v = getenv("PGP_ICP_SPLIT")) split = atoi(v) != 0;
-  // grid search: only with a correspondence cap; by default when the scan would be >= 2^27 tests per pose
-  bool use_grid = false;
-  if (a.max_corr2 >= 0.f) {
-    if (prm->nn_search == 2) use_grid = true;
-    else if (prm->nn_search == 0) use_grid = (double)n_src * (double)n_tgt >= 134217728.0;
-  } else if (prm->nn_search == 2) {
-    set_error("icp: the grid search needs max_corr_dist > 0");
-    return PGP_EINVAL;
-  }
-  // exact index of the static target: the default whenever its image fits a workgroup's LDS.  The
-  // exhaustive searches stay as the checker paths (nn_search 1, PGP_ICP_NN=scan, or PGP_ICP_SPLIT set).
-  bool use_index = false, persist_index = false;
-  {
-    const char* env_nn = getenv("PGP_ICP_NN");
-    const bool legacy = getenv("PGP_ICP_SPLIT") != nullptr;
-    bool want = !use_grid && !legacy && (prm->nn_search == 0 || prm->nn_search == 3);
-    if (env_nn && !strcmp(env_nn, "scan")) want = false;
-    if (env_nn && !strcmp(env_nn, "index") && !use_grid && prm->nn_search != 1) want = true;
-    bool want_persist = n_src <= kPiR * kIcpThreads;
-    if (const char* v = getenv("PGP_ICP_PERSIST")) want_persist = want_persist && atoi(v) != 0;
-    if (want) {
-      // one persistent workgroup per pose keeps all n_src correspondences in LDS; the host-driven path 1024
-      if (want_persist) {
-        if ((rc = build_nn_index(ctx, d_tgt, n_tgt, n_src, &a, &use_index, stream, tgt_token)) != PGP_OK) return rc;
-        persist_index = use_index;
-      }
-      if (!use_index && (rc = build_nn_index(ctx, d_tgt, n_tgt, kIdxThreads, &a, &use_index, stream, tgt_token)) != PGP_OK) return rc;
-      if (!use_index && prm->nn_search == 3) {
-        set_error("icp: the target (%d points) does not fit the LDS index", n_tgt);
-        return PGP_EINVAL;
-      }
-    }
-  }
-  if (use_grid || a.smooth > 0 || use_index) split = true;   // all live on the host-driven path
-  const size_t hist_bytes = a.smooth > 0 ? (size_t)n * (kMaxSmooth + 1) * 7 * 8 : 0;
-  a.energy = d_energy;
-  a.iters = d_iters;
-  const size_t lds = (size_t)kTgtTile * sizeof(float4);
-  if ((rc = ensure_icp_attrs(ctx)) != PGP_OK) return rc;
-  if (persist_index) {
-    // everything of an iteration lives in LDS: the workspace holds the pointmatcher history only
-    if (a.smooth > 0) {
-      if ((rc = ctx->d_icp_ws.ensure(hist_bytes + 64)) != PGP_OK) return rc;
-      a.st_hist = ctx->d_icp_ws.as<double>();
-      PGP_HIP(hipMemsetAsync(a.st_hist, 0, hist_bytes, stream));
-    }
-    const bool il = a.nn_image_in_lds != 0;
-    const size_t plds = nn_lds_bytes(a.nn.bytes, n_src, il);
-    const bool trim_only = icp_trim_only(a);
-    const void* fn = persist_kernel(a.metric, il, false, trim_only, n_src);
-    const void* fn_cluster = persist_kernel(a.metric, il, true, trim_only, n_src);
-    // Few poses: 2 or 4 workgroups per pose share the search (64 poses alone would use 64 of the 256 CUs).  They
-    // meet once per iteration, so all of them should be resident at once: a grid that fits the device, one workgroup
-    // per CU, chained behind the previous such launch (launch_resident, g_coop).  Not while the stream is being
-    // captured (the chain's event wait is not for a graph) and not with the pointmatcher history.
-    a.wgs_per_pose = 1;
-    if (const char* v = getenv("PGP_ICP_DBG_POSE")) a.dbg_pose = atoi(v);
-    if (const char* v = getenv("PGP_ICP_SLOTS")) a.slot_budget = atoi(v);
-    if (const char* v = getenv("PGP_ICP_ROWS")) a.rows_mode = atoi(v);
-    int want_wgs = n * 4 <= ctx->n_cus ? 4 : (n * 2 <= ctx->n_cus ? 2 : 1);
-    if (const char* v = getenv("PGP_ICP_WGS")) want_wgs = atoi(v) == 4 ? 4 : (atoi(v) == 2 ? 2 : 1);   // A/B knob
-    if (want_wgs > 1 && a.smooth == 0 && n * want_wgs <= ctx->n_cus && n_src >= 64 * want_wgs) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(stream, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;
-      if (cap == hipStreamCaptureStatusNone) a.wgs_per_pose = want_wgs;
-    }
-    if (getenv("PGP_ICP_DEBUG")) fprintf(stderr, "icp: n_cus %d want %d -> %d\n", ctx->n_cus, want_wgs, a.wgs_per_pose);
-    if (a.wgs_per_pose > 1) {
-      const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-      // The chain first: the previous clustered launch of this device (any stream of this process) has finished
-      // before this one's buffers are (re)allocated, its counters zeroed and its workgroups started.
-      std::lock_guard<std::mutex> chain(g_coop.mu);
-      if (g_coop.last[dev]) PGP_HIP(hipStreamWaitEvent(stream, g_coop.last[dev], 0));
-      else PGP_HIP(hipEventCreateWithFlags(&g_coop.last[dev], hipEventDisableTiming));
-      // meeting buffers | arrival counters | workgroups that have left | search ticks
-      const size_t xbytes = 2 * need * 8, ctr_words = 3 * (size_t)n + 4;
-      const void* x_before = ctx->d_icp_x.p;
-      const size_t x_cap_before = ctx->d_icp_x.cap;
-      if ((rc = ctx->d_icp_x.ensure(xbytes + ctr_words * 4 + (size_t)n * 32 + 64)) != PGP_OK) return rc;
-      a.x_buf = ctx->d_icp_x.as<unsigned long long>();
-      a.x_ctr = reinterpret_cast<unsigned*>(a.x_buf + 2 * need);
-      a.x_done = a.x_ctr + n + 4;
-      a.x_abandon = a.x_done + n;
-      if (getenv("PGP_ICP_FORCE_LOST")) a.force_lost = 1;   // test knob: the first meeting of every pose counts as lost
-      a.x_ticks = a.x_ctr + ctr_words;
-      a.solo_ticks = 1100;   // 11 us (tools/icp_time.py, PGP_ICP_SOLO_TICKS sweep)
-      if (const char* v = getenv("PGP_ICP_SOLO_TICKS")) a.solo_ticks = (unsigned)atoi(v);
-      // The counters are zero whenever a clustered launch on this context is over (every pose's last workgroup to leave
-      // puts them back, lost meeting or not: cluster_leave): a fill only when these words were not the counters of the
-      // last such launch (first use, a grown buffer, another pose count, the helping launch's layout in between).
-      const bool same_words = ctx->icp_x_clean && ctx->d_icp_x.p == x_before && ctx->d_icp_x.cap == x_cap_before &&
-                              ctx->icp_x_n == n && ctx->icp_x_need == (size_t)need;
-      if (!same_words) PGP_HIP(hipMemsetAsync(a.x_ctr, 0, ctr_words * 4, stream));
-      ctx->icp_x_clean = true;
-      ctx->icp_x_n = n;
-      ctx->icp_x_need = (size_t)need;
-      void* params[] = {&a};
-      hipError_t e = launch_resident(ctx, fn_cluster, (unsigned)(n * a.wgs_per_pose), kIcpThreads, params, (unsigned)plds, stream);
-      if (getenv("PGP_ICP_DEBUG"))
-        fprintf(stderr, "icp: %d poses x %d workgroups, resident launch: %s\n", n, a.wgs_per_pose, hipGetErrorString(e));
-      if (e == hipSuccess) {
-        // Nothing behind the kernel: a meeting that is lost (another process holding the chip's compute units for
-        // seconds) makes the pose's workgroup 0 go on alone inside the launch (icp_persist_body), so the caller --
-        // host-pointer or device-pointer API -- always gets refined transforms.  (Rounds 3-4 queued a repair launch
-        // behind every clustered launch for that case: 1.6 us + ~12 us of dependency latency per call.)
-        PGP_HIP(hipEventRecord(g_coop.last[dev], stream));
-        PGP_HIP(hipGetLastError());
-        return PGP_OK;
-      }
-      (void)hipGetLastError();   // the grid does not fit on this device at the kernel's occupancy: one workgroup per pose
-      a.wgs_per_pose = 1;
-    }
-    // One workgroup per pose and all of them resident at once (129 .. 256 poses on 256 compute units): a workgroup
-    // that is through with its pose takes search passes of the poses still running (HelpPub) -- the launch then
-    // lasts about as long as the MEAN pose, not the slowest.  Launched and chained like the clustered launches
-    // (launch_resident); a repair launch behind it (the clustered launch needs none any more).
-    // MEASURED SLOWER and therefore OFF unless PGP_ICP_HELP=1 (profiles/r04_ab/icp_helping.log: 256 poses from far
-    // 0.84 -> 1.00 ms, from near 0.25 -> 0.28 ms, same bits): the helped kernel's own passes lose the one-trip-ahead
-    // prefetch of the plain slot loop, a published iteration costs ~10 us of write-through traffic and waiting, and
-    // idle workgroups only exist once the fast poses are through -- when the slow ones have few far iterations left.
-    bool want_help = a.wgs_per_pose == 1 && n >= 2 && n <= ctx->n_cus && a.metric == 0 && il && a.smooth == 0;
-    {
-      const char* v = getenv("PGP_ICP_HELP");
-      want_help = want_help && v && atoi(v) != 0;
-    }
-    if (want_help) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) want_help = false;
-    }
-    if (want_help) {
-      const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-      std::lock_guard<std::mutex> chain(g_coop.mu);
-      if (g_coop.last[dev]) PGP_HIP(hipStreamWaitEvent(stream, g_coop.last[dev], 0));
-      else PGP_HIP(hipEventCreateWithFlags(&g_coop.last[dev], hipEventDisableTiming));
-      // counters (claim words | slot counts | passes done | finished, lost) | saved transforms | publications
-      const size_t N = (size_t)n, hdr = (N * 16 + 8 + 255) & ~(size_t)255, save = (N * 64 + 255) & ~(size_t)255, hb = help_bytes(n_src);
-      if ((rc = ctx->d_icp_x.ensure(hdr + save + N * hb + 256)) != PGP_OK) return rc;
-      ctx->icp_x_clean = false;   // (the clustered launch's counters live in the same buffer)
-      unsigned char* base = ctx->d_icp_x.as<unsigned char>();
-      IcpArgs h = a;
-      h.help_ctl = reinterpret_cast<unsigned long long*>(base);
-      h.help_nslots = reinterpret_cast<unsigned*>(base + N * 8);
-      h.help_done = h.help_nslots + N;
-      h.help_finished = h.help_done + N;
-      h.x_lost = h.help_finished + 1;
-      h.T_save = reinterpret_cast<float*>(base + hdr);
-      h.help = base + hdr + save;
-      h.help_stride = hb;
-      PGP_HIP(hipMemsetAsync(base, 0, hdr, stream));
-      void* hparams[] = {&h};
-      hipError_t e = launch_resident(ctx, help_kernel(trim_only, n_src <= 2 * kIcpBase ? 2 : (n_src <= 3 * kIcpBase ? 3 : 4)),
-                                     (unsigned)n, kIcpThreads, hparams, (unsigned)plds, stream);
-      if (getenv("PGP_ICP_DEBUG")) fprintf(stderr, "icp: %d poses, helping launch: %s\n", n, hipGetErrorString(e));
-      if (e == hipSuccess) {
-        IcpArgs fix = a;
-        fix.wgs_per_pose = 1;
-        fix.run_if = h.x_lost;
-        fix.T_in = h.T_save;
-        fix.T_save = nullptr;
-        void* fparams[] = {&fix};
-        PGP_HIP(hipLaunchKernel(fn, dim3(n), dim3(kIcpThreads), fparams, plds, stream));
-        PGP_HIP(hipEventRecord(g_coop.last[dev], stream));
-        PGP_HIP(hipGetLastError());
-        return PGP_OK;
-      }
-      (void)hipGetLastError();   // the grid does not fit here: the launch without helpers below
-    }
-    void* params[] = {&a};
-    PGP_HIP(hipLaunchKernel(fn, dim3(n), dim3(kIcpThreads), params, plds, stream));
-    PGP_HIP(hipGetLastError());
-    return PGP_OK;
-  }
-  // Targets beyond the exact index's 65 535 points, no correspondence cap: a uniform grid answers every query that has a
-  // neighbour within a safe radius, the exhaustive scan only the others (icp_nn_grid_open; PGP_ICP_OPEN_GRID=0: the scan alone)
-  bool open_grid = split && !use_grid && !use_index && a.max_corr2 < 0.f && n_tgt > 65535 && prm->nn_search != 1;
-  if (const char* v = getenv("PGP_ICP_OPEN_GRID")) open_grid = open_grid && atoi(v) != 0;
-  // Scenes beyond one block of 4096 points, nothing to trim (a cap, or every pair kept): the iteration's sums are formed by one
-  // workgroup per block (icp_sums_partial) and icp_refine only adds them up (PGP_ICP_PART=0: one workgroup walks the scene)
-  const int n_blk = (n_src + kSumR * kIcpThreads - 1) / (kSumR * kIcpThreads);
-  bool part_sums = split && n_blk > 1 && !(a.max_corr2 < 0.f && a.k_trim < a.n_src);
-  if (const char* v = getenv("PGP_ICP_PART")) part_sums = part_sums && atoi(v) != 0;
-  const size_t part_bytes = part_sums ? (size_t)n * n_blk * kPartStride * 8 + 64 : 0;
-  const size_t state_bytes = split ? need * 8 + (size_t)n * 16 + 64 + hist_bytes + 64 + (use_index ? need * 4 + 64 : 0) +
-                                         (open_grid ? need * 4 + (size_t)n * 4 + 128 : 0) + part_bytes : 0;
-  if ((rc = ctx->d_icp_ws.ensure(need * 8 + state_bytes + 64)) != PGP_OK) return rc;
-  a.ws_d2 = ctx->d_icp_ws.as<float>();
-  a.ws_j = reinterpret_cast<int*>(a.ws_d2 + need);
-  if (!split) {
-    hipLaunchKernelGGL(icp_refine<false>, dim3(n), dim3(kIcpThreads), lds, stream, a);
-    PGP_HIP(hipGetLastError());
-    return PGP_OK;
-  }
-  // ---- split path: per iteration, correspondences over many workgroups + one update workgroup
-  unsigned char* p = reinterpret_cast<unsigned char*>(a.ws_j + need);
-  p = reinterpret_cast<unsigned char*>(((uintptr_t)p + 15) & ~(uintptr_t)15);
-  a.ws_key = reinterpret_cast<unsigned long long*>(p);
-  a.st_E = reinterpret_cast<double*>(a.ws_key + need);
-  a.st_it = reinterpret_cast<int*>(a.st_E + n);
+  if ((rc = cv.ensure(c.ctx->d_icp_ws)) != PGP_OK) return rc;
+  a.ws_d2 = cv.at(p_d2);
+  a.ws_j = cv.at(p_j);
+  if (!split) return PGP_OK;
+  a.ws_key = cv.at(p_key);
+  a.st_E = cv.at(p_E);
+  a.st_it = cv.at(p_state);
   a.st_done = a.st_it + n;
   a.n_done = a.st_done + n;
-  a.st_hist = a.smooth > 0 ? reinterpret_cast<double*>(((uintptr_t)(a.n_done + 1) + 15) & ~(uintptr_t)15) : nullptr;
-  if (use_index) a.ws_pos = reinterpret_cast<int*>(((uintptr_t)(a.n_done + 1) + hist_bytes + 31) & ~(uintptr_t)15);
-  // the state of the host-driven iterations (not needed -- and its host synchronisation not paid -- by the one-launch form below)
-  auto init_split_state = [&]() -> int {
-    if (use_index) PGP_HIP(hipMemsetAsync(a.ws_pos, 0xFF, need * 4, stream));   // no previous correspondence yet
-    PGP_HIP(hipMemsetAsync(a.ws_key, 0xFF, need * 8, stream));
-    PGP_HIP(hipMemsetAsync(a.ws_j, 0xFF, need * 4, stream));  // no previous correspondence yet
-    PGP_HIP(hipMemsetAsync(a.st_it, 0, (size_t)n * 8 + 4, stream));
-    if (a.st_hist) PGP_HIP(hipMemsetAsync(a.st_hist, 0, hist_bytes, stream));
-    std::vector<double> e0((size_t)n, (double)FLT_MAX);
-    PGP_HIP(hipMemcpyAsync(a.st_E, e0.data(), (size_t)n * 8, hipMemcpyHostToDevice, stream));
-    PGP_HIP(hipStreamSynchronize(stream));  // e0 is a stack temporary
-    return PGP_OK;
-  };
-  // (up to 64 poses: the reference's call has one; the unit sums of many poses would be gigabytes)
-  bool scene_persist = use_grid && n_blk > 1 && !(a.max_corr2 < 0.f && a.k_trim < a.n_src) && a.smooth == 0 && ctx->n_cus > 0 && n <= 64 &&
-                       !t_scene_form_off;
-  if (const char* v = getenv("PGP_ICP_PART")) scene_persist = scene_persist && atoi(v) != 0;
-  if (const char* v = getenv("PGP_ICP_SCENE_PERSIST")) scene_persist = scene_persist && atoi(v) != 0;
-  if (scene_persist) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) scene_persist = false;
-  }
-  if (!scene_persist && (rc = init_split_state()) != PGP_OK) return rc;
-  double* d_part = nullptr;
-  if (part_sums) {   // the last part_bytes of the workspace
-    unsigned char* end = ctx->d_icp_ws.as<unsigned char>() + need * 8 + state_bytes + 64;
-    d_part = reinterpret_cast<double*>(((uintptr_t)(end - part_bytes) + 47) & ~(uintptr_t)15);
-  }
-  int* open_list = nullptr;
-  int* open_cnt = nullptr;
-  float open_r2 = 0.f;
+  a.st_hist = a.smooth > 0 ? cv.at(p_hist) : nullptr;
+  if (use_index) a.ws_pos = cv.at(p_pos);
   if (open_grid) {
-    unsigned char* q = reinterpret_cast<unsigned char*>(a.n_done + 1) + hist_bytes + 64;
-    q = reinterpret_cast<unsigned char*>(((uintptr_t)q + 15) & ~(uintptr_t)15);
-    open_list = reinterpret_cast<int*>(q);
-    open_cnt = open_list + need;
+    w->open_list = cv.at(p_open);
+    w->open_cnt = cv.at(p_open_cnt);
   }
-  // The grid of the capped search stays valid across calls like the exact index does: same (target pointer, size, token
-  // != 0) and the same cap = the same cells (the reference aligns every frame's scene to the SAME table model with the same
-  // cap, SceneCfg.cpp:101,135-141: bounding box, two scatters and a scan -- ~0.15 ms and a host synchronisation -- per call).
-  const bool grid_cached = use_grid && !open_grid && tgt_token != 0 && ctx->icp_grid_valid && ctx->icp_grid_token == tgt_token &&
-                           ctx->icp_grid_tgt == (const void*)d_tgt && ctx->icp_grid_ntgt == n_tgt && ctx->icp_grid_cap == prm->max_corr_dist;
-  if (grid_cached) {
-    a.gox = ctx->icp_grid_geom[0];
-    a.goy = ctx->icp_grid_geom[1];
-    a.goz = ctx->icp_grid_geom[2];
-    a.ginv_h = ctx->icp_grid_geom[3];
-    a.gnx = ctx->icp_grid_n[0];
-    a.gny = ctx->icp_grid_n[1];
-    a.gnz = ctx->icp_grid_n[2];
-    const size_t cells = (size_t)a.gnx * a.gny * a.gnz;
-    const size_t off_pts = ((cells + 1) * 8 + 64 + 255) & ~(size_t)255;
-    unsigned char* gb = ctx->d_icp_grid.as<unsigned char>();
-    a.gcell_start = reinterpret_cast<uint32_t*>(gb + 64) + (cells + 1);
-    a.gpts = reinterpret_cast<float4*>(gb + off_pts);
+  if (c.plan.part_sums) w->d_part = cv.at(p_part);
+  return PGP_OK;
+}
+
+// the state of the host-driven iterations (not needed -- and its host synchronisation not paid -- by the one-launch form)
+static int init_split_state(const IcpCall& c, const IcpArgs& a) {
+  const size_t n = (size_t)c.n, need = c.need();
+  if (a.ws_pos) PGP_HIP(hipMemsetAsync(a.ws_pos, 0xFF, need * 4, c.stream));   // no previous correspondence yet
+  PGP_HIP(hipMemsetAsync(a.ws_key, 0xFF, need * 8, c.stream));
+  PGP_HIP(hipMemsetAsync(a.ws_j, 0xFF, need * 4, c.stream));  // no previous correspondence yet
+  PGP_HIP(hipMemsetAsync(a.st_it, 0, n * 8 + 4, c.stream));
+  if (a.st_hist) PGP_HIP(hipMemsetAsync(a.st_hist, 0, hist_doubles(a, c.n) * 8, c.stream));
+  std::vector<double> e0(n, (double)FLT_MAX);
+  PGP_HIP(hipMemcpyAsync(a.st_E, e0.data(), n * 8, hipMemcpyHostToDevice, c.stream));
+  PGP_HIP(hipStreamSynchronize(c.stream));  // e0 is a stack temporary
+  return PGP_OK;
+}
+
+// d_icp_grid as the uniform grid of the capped / open search: 64 bytes | counters | cell starts | the points by cell
+struct GridPieces {
+  Carve cv;
+  Carve::Piece<uint32_t> ctr, start;
+  Carve::Piece<float4> pts;
+};
+static GridPieces grid_pieces(const IcpArgs& a, int n_tgt) {
+  const size_t cells = (size_t)a.gnx * a.gny * a.gnz;
+  GridPieces g;
+  g.cv.pad(64);
+  g.ctr = g.cv.add<uint32_t>(cells + 1);
+  g.start = g.cv.add<uint32_t>(cells + 1);
+  g.pts = g.cv.add<float4>((size_t)n_tgt, 256);
+  g.cv.pad(64);
+  return g;
+}
+
+// Builds the search's grid over the target, or reuses the one the context holds.  The grid of the capped search stays valid
+// across calls like the exact index does: same (target pointer, size, token != 0) and the same cap = the same cells (the
+// reference aligns every frame's scene to the SAME table model with the same cap, SceneCfg.cpp:101,135-141: bounding box,
+// two scatters and a scan -- ~0.15 ms and a host synchronisation -- per call).
+static int search_grid(const IcpCall& c, const pgp_icp_options* prm, const float4* d_tgt, unsigned long long tgt_token, IcpArgs& a,
+                       HostWs* w) {
+  pgp_ctx* ctx = c.ctx;
+  hipStream_t stream = c.stream;
+  const int n_tgt = c.n_tgt;
+  const bool open_grid = c.plan.search == IcpSearch::OpenGrid;
+  const bool keep = !open_grid && tgt_token != 0;
+  float* const geom[4] = {&a.gox, &a.goy, &a.goz, &a.ginv_h};   // what the context keeps of a capped grid
+  int* const cells[3] = {&a.gnx, &a.gny, &a.gnz};
+  if (keep && ctx->icp_grid_valid && ctx->icp_grid_token == tgt_token && ctx->icp_grid_tgt == (const void*)d_tgt &&
+      ctx->icp_grid_ntgt == n_tgt && ctx->icp_grid_cap == prm->max_corr_dist) {
+    for (int k = 0; k < 4; ++k) *geom[k] = ctx->icp_grid_geom[k];
+    for (int k = 0; k < 3; ++k) *cells[k] = ctx->icp_grid_n[k];
+    GridPieces g = grid_pieces(a, n_tgt);
+    g.cv.bind(ctx->d_icp_grid);
+    a.gcell_start = g.cv.at(g.start);
+    a.gpts = g.cv.at(g.pts);
+    return PGP_OK;
   }
-  if ((use_grid || open_grid) && !grid_cached) {
-    ctx->icp_grid_valid = false;
-    ctx->icp_idx_valid = false;   // d_icp_grid is about to hold the search's grid
-    // ---- the target's grid: bounding box (device), cell edge >= max_corr (grown to keep <= 2^26 cells)
-    float bb[6];
-    if ((rc = device_bbox(ctx, reinterpret_cast<const float*>(d_tgt), n_tgt, 4, bb, bb + 3, stream)) != PGP_OK) return rc;
-    if (!(bb[0] <= bb[3])) bb[0] = bb[1] = bb[2] = bb[3] = bb[4] = bb[5] = 0.f;   // no finite target point
-    float maxabs = 0.f;
-    for (int q = 0; q < 6; ++q) maxabs = fmaxf(maxabs, fabsf(bb[q]));
-    // margin for the rounding of the cell coordinate: a point within max_corr of a query is at most
-    // one cell away from the query's cell
-    const float margin = 64.f * FLT_EPSILON * maxabs;
-    float h = prm->max_corr_dist * 1.001f + margin;
-    if (open_grid) {
-      // no cap to size the cells by: twice the spacing of n_tgt points spread over the bounding box's surface (a table,
-      // a room's walls), so that whatever lies within ~2 spacings of the target -- every query of a pose that is not far
-      // off -- is settled by the grid, from a few dozen candidates.  Measured (tools/icp_big_target.py, 30 000 x 100 000,
-      // 10 iterations): 1.5 / 2 / 3 / 4 / 6 spacings -> 2.63 / 2.32 / 2.94 / 3.84 / 6.67 ms from 4 mm off and 3.86 / 4.12 /
-      // 4.69 / 5.53 / 8.11 ms from 8 cm off, against 6.3 ms for the exhaustive scan alone.
-      const double ex = (double)bb[3] - bb[0], ey = (double)bb[4] - bb[1], ez = (double)bb[5] - bb[2];
-      const double area = 2.0 * (ex * ey + ey * ez + ez * ex);
-      double spacings = 2.0;
-      if (const char* v = getenv("PGP_ICP_OPEN_CELL")) spacings = atof(v) > 0.0 ? atof(v) : spacings;   // A/B knob
-      h = (float)(spacings * std::sqrt(std::max(area, 1e-12) / (double)n_tgt)) + margin;
-      if (!(h > 0.f) || !std::isfinite(h)) h = 1.f;
-    }
-    for (;;) {
-      // one spare cell per axis: the float cell coordinate of a point on the upper face may round up
-      const double nx = floor((double)(bb[3] - bb[0]) / h) + 2, ny = floor((double)(bb[4] - bb[1]) / h) + 2,
-                   nz = floor((double)(bb[5] - bb[2]) / h) + 2;
-      if (nx * ny * nz <= 67108864.0) {
-        a.gnx = (int)nx;
-        a.gny = (int)ny;
-        a.gnz = (int)nz;
-        break;
-      }
-      h *= 1.26f;
-    }
-    if (open_grid) {
-      // every target point within r of a query lies in the 27 cells around the query's: r = (h - margin) / 1.001, taken a
-      // little smaller still (the comparison is on squared distances as the kernels round them)
-      const double r = ((double)h - (double)margin) / 1.001;
-      open_r2 = (float)(r * r * (1.0 - 1e-5));
-      if (!(open_r2 > 0.f)) open_r2 = 0.f;
-      if (getenv("PGP_ICP_DEBUG"))
-        fprintf(stderr, "icp: open grid over %d target points: cell %.4g, %d x %d x %d cells, settles neighbours within %.4g\n", n_tgt,
-                (double)h, a.gnx, a.gny, a.gnz, r);
-    }
-    a.gox = bb[0];
-    a.goy = bb[1];
-    a.goz = bb[2];
-    a.ginv_h = 1.0f / h;
-    const size_t cells = (size_t)a.gnx * a.gny * a.gnz;
-    const size_t off_pts = ((cells + 1) * 8 + 64 + 255) & ~(size_t)255;
-    if ((rc = ctx->d_icp_grid.ensure(off_pts + (size_t)n_tgt * 16 + 64)) != PGP_OK) return rc;
-    if ((rc = ctx->d_scan_tmp.ensure(((cells + 1) / 2048 + 2) * 4)) != PGP_OK) return rc;
-    unsigned char* gb = ctx->d_icp_grid.as<unsigned char>();
-    uint32_t* ctr = reinterpret_cast<uint32_t*>(gb + 64);
-    uint32_t* start = ctr + (cells + 1);
-    float4* pts = reinterpret_cast<float4*>(gb + off_pts);
-    a.gcell_start = start;
-    a.gpts = pts;
-    const dim3 gt((n_tgt + 255) / 256);
-    PGP_HIP(hipMemsetAsync(ctr, 0, (cells + 1) * 4, stream));
-    hipLaunchKernelGGL(grid_scatter<false>, gt, dim3(256), 0, stream, a, ctr, (float4*)nullptr);
-    if ((rc = device_exclusive_scan(ctr, start, cells + 1, ctx->d_scan_tmp.as<uint32_t>(), stream)) != PGP_OK) return rc;
-    PGP_HIP(hipMemsetAsync(ctr, 0, (cells + 1) * 4, stream));
-    hipLaunchKernelGGL(grid_scatter<true>, gt, dim3(256), 0, stream, a, ctr, pts);
-    PGP_HIP(hipGetLastError());
-    if (use_grid && !open_grid && tgt_token != 0) {
-      ctx->icp_grid_valid = true;
-      ctx->icp_grid_token = tgt_token;
-      ctx->icp_grid_tgt = (const void*)d_tgt;
-      ctx->icp_grid_ntgt = n_tgt;
-      ctx->icp_grid_cap = prm->max_corr_dist;
-      ctx->icp_grid_geom[0] = a.gox;
-      ctx->icp_grid_geom[1] = a.goy;
-      ctx->icp_grid_geom[2] = a.goz;
-      ctx->icp_grid_geom[3] = a.ginv_h;
-      ctx->icp_grid_n[0] = a.gnx;
-      ctx->icp_grid_n[1] = a.gny;
-      ctx->icp_grid_n[2] = a.gnz;
-    }
+  ctx->icp_grid_valid = false;
+  ctx->icp_idx_valid = false;   // d_icp_grid is about to hold the search's grid
+  // ---- the target's grid: bounding box (device), cell edge >= max_corr (grown to keep <= 2^26 cells)
+  float bb[6];
+  int rc;
+  if ((rc = device_bbox(ctx, reinterpret_cast<const float*>(d_tgt), n_tgt, 4, bb, bb + 3, stream)) != PGP_OK) return rc;
+  if (!(bb[0] <= bb[3])) bb[0] = bb[1] = bb[2] = bb[3] = bb[4] = bb[5] = 0.f;   // no finite target point
+  float maxabs = 0.f;
+  for (int q = 0; q < 6; ++q) maxabs = fmaxf(maxabs, fabsf(bb[q]));
+  // margin for the rounding of the cell coordinate: a point within max_corr of a query is at most
+  // one cell away from the query's cell
+  const float margin = 64.f * FLT_EPSILON * maxabs;
+  float h = prm->max_corr_dist * 1.001f + margin;
+  if (open_grid) {
+    // no cap to size the cells by: twice the spacing of n_tgt points spread over the bounding box's surface (a table,
+    // a room's walls), so that whatever lies within ~2 spacings of the target -- every query of a pose that is not far
+    // off -- is settled by the grid, from a few dozen candidates.  Measured (tools/icp_big_target.py, 30 000 x 100 000,
+    // 10 iterations): 1.5 / 2 / 3 / 4 / 6 spacings -> 2.63 / 2.32 / 2.94 / 3.84 / 6.67 ms from 4 mm off and 3.86 / 4.12 /
+    // 4.69 / 5.53 / 8.11 ms from 8 cm off, against 6.3 ms for the exhaustive scan alone.
+    const double ex = (double)bb[3] - bb[0], ey = (double)bb[4] - bb[1], ez = (double)bb[5] - bb[2];
+    const double area = 2.0 * (ex * ey + ey * ez + ez * ex);
+    h = (float)(c.env.open_cell * std::sqrt(std::max(area, 1e-12) / (double)n_tgt)) + margin;
+    if (!(h > 0.f) || !std::isfinite(h)) h = 1.f;
   }
-  // The capped grid search with sums by block -- the shape of the reference's table alignment -- as ONE launch of resident
-  // workgroups (icp_scene_persist): every iteration on the device, no host round trip.  PGP_ICP_SCENE_PERSIST=0: the host-
-  // driven iterations below (the checker of that kernel: same bits); also taken while the stream is being captured and with
-  // the pointmatcher history.
-  {
-    if (scene_persist) {
-      SceneArgs z{};
-      z.n_chunks = (n_src + kSceneQ - 1) / kSceneQ;
-      z.n_units = (n_src + 255) / 256;
-      z.n_blk = n_blk;
-      z.n_units16 = n_blk * 16;
-      const size_t N = (size_t)n, w_bytes = N * z.n_units16 * kPartStride * 8, uc_bytes = (N * z.n_units16 * 4 + 63) & ~(size_t)63;
-      const size_t st_bytes = N * kSceneRep * kSceneRepStride * 4, pc_bytes = (N * 4 + 63) & ~(size_t)63, eo_bytes = (N * 8 + 63) & ~(size_t)63;
-      const size_t tail = pc_bytes + st_bytes + eo_bytes + 64;
-      const int dev = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-      std::lock_guard<std::mutex> chain(g_coop.mu);   // launches of resident workgroups of one process never overlap on a device
-      if (g_coop.last[dev]) PGP_HIP(hipStreamWaitEvent(stream, g_coop.last[dev], 0));
-      else PGP_HIP(hipEventCreateWithFlags(&g_coop.last[dev], hipEventDisableTiming));
-      if ((rc = ctx->d_icp_x.ensure(w_bytes + uc_bytes + tail + 256)) != PGP_OK) return rc;
-      ctx->icp_x_clean = false;   // (the clustered launch's counters live in the same buffer)
-      unsigned char* xb = ctx->d_icp_x.as<unsigned char>();
-      z.W = reinterpret_cast<double*>(xb);
-      z.unit_ctr = reinterpret_cast<unsigned*>(xb + w_bytes);
-      z.pose_ctr = reinterpret_cast<unsigned*>(xb + w_bytes + uc_bytes);
-      z.state = reinterpret_cast<unsigned*>(xb + w_bytes + uc_bytes + pc_bytes);
-      z.E_old = reinterpret_cast<double*>(xb + w_bytes + uc_bytes + pc_bytes + st_bytes);
-      z.lost = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(z.E_old) + eo_bytes);
-      z.keys = a.ws_key;
+  for (;;) {
+    // one spare cell per axis: the float cell coordinate of a point on the upper face may round up
+    const double nx = floor((double)(bb[3] - bb[0]) / h) + 2, ny = floor((double)(bb[4] - bb[1]) / h) + 2,
+                 nz = floor((double)(bb[5] - bb[2]) / h) + 2;
+    if (nx * ny * nz <= 67108864.0) {
+      a.gnx = (int)nx;
+      a.gny = (int)ny;
+      a.gnz = (int)nz;
+      break;
+    }
+    h *= 1.26f;
+  }
+  if (open_grid) {
+    // every target point within r of a query lies in the 27 cells around the query's: r = (h - margin) / 1.001, taken a
+    // little smaller still (the comparison is on squared distances as the kernels round them)
+    const double r = ((double)h - (double)margin) / 1.001;
+    w->open_r2 = (float)(r * r * (1.0 - 1e-5));
+    if (!(w->open_r2 > 0.f)) w->open_r2 = 0.f;
+    if (c.env.debug)
+      fprintf(stderr, "icp: open grid over %d target points: cell %.4g, %d x %d x %d cells, settles neighbours within %.4g\n", n_tgt,
+              (double)h, a.gnx, a.gny, a.gnz, r);
+  }
+  a.gox = bb[0];
+  a.goy = bb[1];
+  a.goz = bb[2];
+  a.ginv_h = 1.0f / h;
+  GridPieces g = grid_pieces(a, n_tgt);
+  const size_t cells1 = g.ctr.count;
+  if ((rc = g.cv.ensure(ctx->d_icp_grid)) != PGP_OK) return rc;
+  if ((rc = ctx->d_scan_tmp.ensure((cells1 / 2048 + 2) * 4)) != PGP_OK) return rc;
+  uint32_t* ctr = g.cv.at(g.ctr);
+  uint32_t* start = g.cv.at(g.start);
+  float4* pts = g.cv.at(g.pts);
+  a.gcell_start = start;
+  a.gpts = pts;
+  const dim3 gt((n_tgt + 255) / 256);
+  PGP_HIP(hipMemsetAsync(ctr, 0, g.ctr.bytes(), stream));
+  hipLaunchKernelGGL(grid_scatter<false>, gt, dim3(256), 0, stream, a, ctr, (float4*)nullptr);
+  if ((rc = device_exclusive_scan(ctr, start, cells1, ctx->d_scan_tmp.as<uint32_t>(), stream)) != PGP_OK) return rc;
+  PGP_HIP(hipMemsetAsync(ctr, 0, g.ctr.bytes(), stream));
+  hipLaunchKernelGGL(grid_scatter<true>, gt, dim3(256), 0, stream, a, ctr, pts);
+  PGP_HIP(hipGetLastError());
+  if (keep) {
+    ctx->icp_grid_valid = true;
+    ctx->icp_grid_token = tgt_token;
+    ctx->icp_grid_tgt = (const void*)d_tgt;
+    ctx->icp_grid_ntgt = n_tgt;
+    ctx->icp_grid_cap = prm->max_corr_dist;
+    for (int k = 0; k < 4; ++k) ctx->icp_grid_geom[k] = *geom[k];
+    for (int k = 0; k < 3; ++k) ctx->icp_grid_n[k] = *cells[k];
+  }
+  return PGP_OK;
+}
+
 #ifdef PGP_SCENE_STAMPS
-      static unsigned long long* d_dbg = nullptr;
-      if (!d_dbg) PGP_HIP(hipMalloc(&d_dbg, (1024 + 4096) * 8));
-      PGP_HIP(hipMemsetAsync(d_dbg, 0, (1024 + 4096) * 8, stream));
-      z.dbg = d_dbg;
-#endif
-      PGP_HIP(hipMemsetAsync(xb, 0, w_bytes + uc_bytes + tail, stream));
-      int per_cu = 0;
-      const void* fn_scene = a.metric == 1 ? reinterpret_cast<const void*>(icp_scene_persist<1>) : reinterpret_cast<const void*>(icp_scene_persist<0>);
-      if (a.metric == 1) PGP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, icp_scene_persist<1>, kSceneThreads, 0));
-      else PGP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, icp_scene_persist<0>, kSceneThreads, 0));
-      const long long items = (long long)n * z.n_chunks, room = (long long)per_cu * ctx->n_cus;
-      z.n_upd = std::min(n, kSceneUpdMax);
-      unsigned grid = (unsigned)std::max<long long>(z.n_upd + 1, std::min(items + z.n_upd, room));
-      if (const char* v = getenv("PGP_ICP_SCENE_WGS")) grid = std::max((unsigned)z.n_upd + 1u, std::min(grid, (unsigned)atoi(v)));   // A/B knob
-      z.poll_sleep = 1;
-      z.wait_ticks = icp_wait_ticks();
-      if (const char* v = getenv("PGP_ICP_SCENE_SLEEP")) z.poll_sleep = atoi(v);
-      if (getenv("PGP_ICP_FORCE_LOST")) z.force_lost = 1;
-      void* params[] = {&a, &z};
-      const hipError_t e = room > z.n_upd ? launch_resident(ctx, fn_scene, grid, kSceneThreads, params, 0, stream) : hipErrorInvalidValue;
-      if (getenv("PGP_ICP_DEBUG"))
-        fprintf(stderr, "icp: scene-sized capped ICP in one launch: %d poses x %d chunks on %u workgroups (%d per CU): %s\n", n, z.n_chunks,
-                grid, per_cu, hipGetErrorString(e));
-      if (e == hipSuccess) {
-        PGP_HIP(hipEventRecord(g_coop.last[dev], stream));
-        PGP_HIP(hipGetLastError());
-#ifdef PGP_SCENE_STAMPS
-        {
-          std::vector<unsigned long long> h(1024 + 4096);
-          PGP_HIP(hipStreamSynchronize(stream));
-          PGP_HIP(hipMemcpy(h.data(), d_dbg, (1024 + 4096) * 8, hipMemcpyDeviceToHost));
-          {   // iteration 10: every worker's go and searched times relative to the publication of iteration 9
-            const unsigned long long pub = h[9 * 16 + 3];
-            std::vector<double> go, se;
-            for (int w = 0; w < 2048; ++w)
-              if (h[1024 + w]) {
-                go.push_back((double)((long long)(h[1024 + w] - pub)) * 0.01);
-                se.push_back((double)((long long)(h[1024 + 2048 + w] - pub)) * 0.01);
-              }
-            if (!go.empty()) {
-              auto pct = [](std::vector<double> v, double p) { std::sort(v.begin(), v.end()); return v[(size_t)(p * (v.size() - 1))]; };
-              fprintf(stderr, "iteration 10, %zu workers: go min %.2f median %.2f p90 %.2f max %.2f | searched min %.2f median %.2f p90 %.2f p99 %.2f max %.2f us\n",
-                      go.size(), pct(go, 0), pct(go, 0.5), pct(go, 0.9), pct(go, 1), pct(se, 0), pct(se, 0.5), pct(se, 0.9), pct(se, 0.99), pct(se, 1));
-              int slow = 0;
-              for (size_t w = 0; w < se.size() && slow < 12; ++w)
-                if (se[w] > pct(se, 0.97)) { fprintf(stderr, "  worker %zu: go %.2f searched %.2f\n", w, go[w], se[w]); ++slow; }
-            }
-          }
-          // per iteration, in 10 ns ticks relative to the previous publication: worker 0's two chunks (go, searched, ticket),
-          // the last unit closed, the updater (units in, sums added, solved, published)
-          unsigned long long prev = h[4];
-          for (int it = 0; it < 64 && h[it * 16 + 3]; ++it) {
-            const unsigned long long* r = &h[it * 16];
-            auto d = [&](unsigned long long v) { return v ? (double)((long long)(v - prev)) * 0.01 : -1.0; };
-            fprintf(stderr, "it %2d  w0 chunk A: go %6.2f searched %6.2f ticket %6.2f | last unit closed %6.2f | updater: units in %6.2f summed %6.2f solved %6.2f "
-                            "published %6.2f us\n", it, d(r[4]), d(r[5]), d(r[6]), d(r[12]), d(r[0]), d(r[1]), d(r[2]), d(r[3]));
-            prev = r[3];
-          }
-        }
-#endif
-        return PGP_OK;
+// diagnostic build: the stamps of icp_scene_persist, reported on stderr after the launch
+static unsigned long long* g_scene_dbg = nullptr;
+static int scene_stamps_begin(SceneArgs* z, hipStream_t stream) {
+  if (!g_scene_dbg) PGP_HIP(hipMalloc(&g_scene_dbg, (1024 + 4096) * 8));
+  PGP_HIP(hipMemsetAsync(g_scene_dbg, 0, (1024 + 4096) * 8, stream));
+  z->dbg = g_scene_dbg;
+  return PGP_OK;
+}
+static int scene_stamps_report(hipStream_t stream) {
+  std::vector<unsigned long long> h(1024 + 4096);
+  PGP_HIP(hipStreamSynchronize(stream));
+  PGP_HIP(hipMemcpy(h.data(), g_scene_dbg, (1024 + 4096) * 8, hipMemcpyDeviceToHost));
+  {   // iteration 10: every worker's go and searched times relative to the publication of iteration 9
+    const unsigned long long pub = h[9 * 16 + 3];
+    std::vector<double> go, se;
+    for (int w = 0; w < 2048; ++w)
+      if (h[1024 + w]) {
+        go.push_back((double)((long long)(h[1024 + w] - pub)) * 0.01);
+        se.push_back((double)((long long)(h[1024 + 2048 + w] - pub)) * 0.01);
       }
-      (void)hipGetLastError();   // the grid does not fit here: the host-driven iterations
-      if ((rc = init_split_state()) != PGP_OK) return rc;
+    if (!go.empty()) {
+      auto pct = [](std::vector<double> v, double p) { std::sort(v.begin(), v.end()); return v[(size_t)(p * (v.size() - 1))]; };
+      fprintf(stderr, "iteration 10, %zu workers: go min %.2f median %.2f p90 %.2f max %.2f | searched min %.2f median %.2f p90 %.2f p99 %.2f max %.2f us\n",
+              go.size(), pct(go, 0), pct(go, 0.5), pct(go, 0.9), pct(go, 1), pct(se, 0), pct(se, 0.5), pct(se, 0.9), pct(se, 0.99), pct(se, 1));
+      int slow = 0;
+      for (size_t w = 0; w < se.size() && slow < 12; ++w)
+        if (se[w] > pct(se, 0.97)) { fprintf(stderr, "  worker %zu: go %.2f searched %.2f\n", w, go[w], se[w]); ++slow; }
     }
   }
-  const dim3 gnn((n_src + kNnThreads * kIcpR - 1) / (kNnThreads * kIcpR), (n_tgt + kNnTgt - 1) / kNnTgt, n);
+  // per iteration, in 10 ns ticks relative to the previous publication: worker 0's two chunks (go, searched, ticket),
+  // the last unit closed, the updater (units in, sums added, solved, published)
+  unsigned long long prev = h[4];
+  for (int it = 0; it < 64 && h[it * 16 + 3]; ++it) {
+    const unsigned long long* r = &h[it * 16];
+    auto d = [&](unsigned long long v) { return v ? (double)((long long)(v - prev)) * 0.01 : -1.0; };
+    fprintf(stderr, "it %2d  w0 chunk A: go %6.2f searched %6.2f ticket %6.2f | last unit closed %6.2f | updater: units in %6.2f summed %6.2f solved %6.2f "
+                    "published %6.2f us\n", it, d(r[4]), d(r[5]), d(r[6]), d(r[12]), d(r[0]), d(r[1]), d(r[2]), d(r[3]));
+    prev = r[3];
+  }
+  return PGP_OK;
+}
+#endif
+
+// The capped grid search with sums by block -- the shape of the reference's table alignment -- as ONE launch of resident
+// workgroups (icp_scene_persist): every iteration on the device, no host round trip.  PGP_ICP_SCENE_PERSIST=0: the host-
+// driven iterations (the checker of that kernel: same bits).
+static int launch_scene(const IcpCall& c, IcpArgs& a, bool* launched) {
+  const size_t N = (size_t)c.n;
+  SceneArgs z{};
+  z.n_chunks = (c.n_src + kSceneQ - 1) / kSceneQ;
+  z.n_units = (c.n_src + 255) / 256;
+  z.n_blk = c.plan.n_blk;
+  z.n_units16 = c.plan.n_blk * 16;
+  void* params[] = {&a, &z};
+  int per_cu = 0;
+  unsigned grid = 0;
+  hipError_t e = hipSuccess;
+  const int rc = launch_chained(c, [&](ResidentKernel* k) -> int {
+    // unit sums | unit counters | pose counters | state words | previous energies | lost: one fill
+    Carve cv;
+    const auto p_W = cv.add<double>(N * z.n_units16 * kPartStride);
+    const auto p_unit = cv.add<unsigned>(N * z.n_units16);
+    const auto p_pose = cv.add<unsigned>(N, 64);
+    const auto p_state = cv.add<unsigned>(N * kSceneRep * kSceneRepStride, 64);
+    const auto p_E = cv.add<double>(N, 64);
+    const auto p_lost = cv.add<unsigned>(16, 64);
+    const size_t filled = cv.bytes();
+    cv.pad(256);
+    int r;
+    if ((r = cv.ensure(c.ctx->d_icp_x)) != PGP_OK) return r;
+    c.ctx->icp_x_clean = false;   // (the clustered launch's counters live in the same buffer)
+    z.W = cv.at(p_W);
+    z.unit_ctr = cv.at(p_unit);
+    z.pose_ctr = cv.at(p_pose);
+    z.state = cv.at(p_state);
+    z.E_old = cv.at(p_E);
+    z.lost = cv.at(p_lost);
+    z.keys = a.ws_key;
+#ifdef PGP_SCENE_STAMPS
+    if ((r = scene_stamps_begin(&z, c.stream)) != PGP_OK) return r;
+#endif
+    PGP_HIP(hipMemsetAsync(z.W, 0, filled, c.stream));
+    const void* fn = a.metric == 1 ? reinterpret_cast<const void*>(icp_scene_persist<1>) : reinterpret_cast<const void*>(icp_scene_persist<0>);
+    PGP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kSceneThreads, 0));
+    const long long items = (long long)c.n * z.n_chunks, room = (long long)per_cu * c.ctx->n_cus;
+    z.n_upd = std::min(c.n, kSceneUpdMax);
+    grid = (unsigned)std::max<long long>(z.n_upd + 1, std::min(items + z.n_upd, room));
+    grid = std::max((unsigned)z.n_upd + 1u, std::min(grid, c.env.scene_wgs));
+    z.poll_sleep = c.env.scene_sleep;
+    z.wait_ticks = icp_wait_ticks(c.env);
+    if (c.env.force_lost) z.force_lost = 1;
+    if (room > z.n_upd) *k = ResidentKernel{fn, grid, kSceneThreads, params, 0};
+    return PGP_OK;
+  }, nothing_behind, &e);
+  if (rc != PGP_OK) return rc;
+  if (c.env.debug)
+    fprintf(stderr, "icp: scene-sized capped ICP in one launch: %d poses x %d chunks on %u workgroups (%d per CU): %s\n", c.n, z.n_chunks,
+            grid, per_cu, hipGetErrorString(e));
+  *launched = e == hipSuccess;
+#ifdef PGP_SCENE_STAMPS
+  if (*launched) return scene_stamps_report(c.stream);
+#endif
+  return PGP_OK;
+}
+
+// the single-launch persistent kernel of the exhaustive search (PGP_ICP_SPLIT=0: fully asynchronous, graph-capturable)
+static int launch_legacy(const IcpCall& c, const IcpArgs& a) {
+  hipLaunchKernelGGL(icp_refine<false>, dim3(c.n), dim3(kIcpThreads), (size_t)kTgtTile * sizeof(float4), c.stream, a);
+  PGP_HIP(hipGetLastError());
+  return PGP_OK;
+}
+
+// Host-driven iterations: per iteration, correspondences over many workgroups + one update workgroup per pose; every four
+// iterations the host asks whether every pose has stopped.
+static int launch_host(const IcpCall& c, const IcpArgs& a, const HostWs& w) {
+  const int n = c.n, n_src = c.n_src, n_blk = c.plan.n_blk;
+  hipStream_t stream = c.stream;
+  const IcpSearch search = c.plan.search;
+  const size_t lds = (size_t)kTgtTile * sizeof(float4);
+  const dim3 gnn((n_src + kNnThreads * kIcpR - 1) / (kNnThreads * kIcpR), (c.n_tgt + kNnTgt - 1) / kNnTgt, n);
   const dim3 ggrid((unsigned)(((size_t)n_src * kGridLanes + 255) / 256), n);
+  const dim3 gidx((n_src + kIdxThreads - 1) / kIdxThreads, n);
   for (int it = 0; it < a.max_iter; ++it) {
-    if (use_grid) hipLaunchKernelGGL(icp_nn_grid, ggrid, dim3(256), 0, stream, a);
-    else if (open_grid) {
-      PGP_HIP(hipMemsetAsync(open_cnt, 0, (size_t)n * 4, stream));
-      hipLaunchKernelGGL(icp_nn_grid_open, ggrid, dim3(256), 0, stream, a, open_r2, open_list, open_cnt);
-      hipLaunchKernelGGL(icp_nn_split<true>, gnn, dim3(kNnThreads), 0, stream, a, (const int*)open_list, (const int*)open_cnt);
-    } else if (use_index && a.nn_image_in_lds)
-      hipLaunchKernelGGL(icp_nn_index<true>, dim3((n_src + kIdxThreads - 1) / kIdxThreads, n), dim3(kIdxThreads),
-                         nn_lds_bytes(a.nn.bytes, kIdxThreads, true), stream, a);
-    else if (use_index)
-      hipLaunchKernelGGL(icp_nn_index<false>, dim3((n_src + kIdxThreads - 1) / kIdxThreads, n), dim3(kIdxThreads),
-                         nn_lds_bytes(a.nn.bytes, kIdxThreads, false), stream, a);
+    if (search == IcpSearch::CappedGrid) hipLaunchKernelGGL(icp_nn_grid, ggrid, dim3(256), 0, stream, a);
+    else if (search == IcpSearch::OpenGrid) {
+      PGP_HIP(hipMemsetAsync(w.open_cnt, 0, (size_t)n * 4, stream));
+      hipLaunchKernelGGL(icp_nn_grid_open, ggrid, dim3(256), 0, stream, a, w.open_r2, w.open_list, w.open_cnt);
+      hipLaunchKernelGGL(icp_nn_split<true>, gnn, dim3(kNnThreads), 0, stream, a, (const int*)w.open_list, (const int*)w.open_cnt);
+    } else if (search == IcpSearch::IndexLds)
+      hipLaunchKernelGGL(icp_nn_index<true>, gidx, dim3(kIdxThreads), nn_lds_bytes(a.nn.bytes, kIdxThreads, true), stream, a);
+    else if (search == IcpSearch::IndexL2)
+      hipLaunchKernelGGL(icp_nn_index<false>, gidx, dim3(kIdxThreads), nn_lds_bytes(a.nn.bytes, kIdxThreads, false), stream, a);
     else hipLaunchKernelGGL(icp_nn_split<false>, gnn, dim3(kNnThreads), 0, stream, a, (const int*)nullptr, (const int*)nullptr);
-    if (part_sums) {
-      hipLaunchKernelGGL(icp_sums_partial, dim3(n_blk, n), dim3(kIcpThreads), 0, stream, a, d_part, n_blk);
-      hipLaunchKernelGGL((icp_refine<true, true>), dim3(n), dim3(kIcpThreads), lds, stream, a, (const double*)d_part, n_blk);
+    if (c.plan.part_sums) {
+      hipLaunchKernelGGL(icp_sums_partial, dim3(n_blk, n), dim3(kIcpThreads), 0, stream, a, w.d_part, n_blk);
+      hipLaunchKernelGGL((icp_refine<true, true>), dim3(n), dim3(kIcpThreads), lds, stream, a, (const double*)w.d_part, n_blk);
     } else {
       hipLaunchKernelGGL((icp_refine<true, false>), dim3(n), dim3(kIcpThreads), lds, stream, a, (const double*)nullptr, 0);
     }
@@ -4058,11 +4038,99 @@ int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt
   return PGP_OK;
 }
 
+// Which form a call takes, and every knob: icp_plan.h.
+int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt, const float4* d_tgt_n, int n_tgt,
+               float* d_T, int n, const pgp_icp_options* prm, float* d_energy, int* d_iters, hipStream_t stream,
+               unsigned long long tgt_token, bool scene_form_off) {
+  if (n <= 0) return PGP_OK;
+  IcpShape shape{n, n_src, n_tgt, ctx->n_cus, /*capturing*/ false, d_tgt_n != nullptr, scene_form_off, kSumR * kIcpThreads};
+  const IcpError bad = icp_validate(prm, shape);
+  if (bad.rc != PGP_OK) return icp_fail(bad);
+  // the pose index rides on gridDim.z / .y (<= 65535): larger batches go in slices
+  if (n > kPlanPosesMax) {
+    for (int off = 0; off < n; off += kPlanPosesMax) {
+      const int m = n - off < kPlanPosesMax ? n - off : kPlanPosesMax;
+      int rc = launch_icp(ctx, d_src, n_src, d_tgt, d_tgt_n, n_tgt, d_T + 16 * (size_t)off, m, prm,
+                          d_energy ? d_energy + off : nullptr, d_iters ? d_iters + off : nullptr, stream, tgt_token, scene_form_off);
+      if (rc != PGP_OK) return rc;
+    }
+    return PGP_OK;
+  }
+  const IcpEnv env = icp_env();
+  shape.capturing = stream_capturing(stream);
+  IcpArgs a{};
+  a.src = d_src;
+  a.tgt = d_tgt;
+  a.tgt_n = d_tgt_n;
+  a.n_src = n_src;
+  a.n_tgt = n_tgt;
+  a.T = d_T;
+  a.n = n;
+  a.energy = d_energy;
+  a.iters = d_iters;
+  icp_option_args(prm, env, n_src, &a);
+
+  const IcpStage1 s1 = icp_stage1(prm, shape, env);
+  if (s1.err.rc != PGP_OK) return icp_fail(s1.err);
+  int rc;
+  IcpFit fit;
+  if (s1.want == IcpWant::IndexPerPose && (rc = build_nn_index(ctx, env, d_tgt, n_tgt, n_src, &a, &fit.per_pose, stream, tgt_token)) != PGP_OK)
+    return rc;
+  if ((s1.want == IcpWant::IndexHost || (s1.want == IcpWant::IndexPerPose && !fit.per_pose)) &&
+      (rc = build_nn_index(ctx, env, d_tgt, n_tgt, kIdxThreads, &a, &fit.host, stream, tgt_token)) != PGP_OK)
+    return rc;
+  fit.image_in_lds = a.nn_image_in_lds != 0;
+  const IcpPlan plan = icp_stage2(prm, shape, env, s1, fit);
+  if (plan.err.rc != PGP_OK) return icp_fail(plan.err);
+  if ((rc = ensure_icp_attrs(ctx)) != PGP_OK) return rc;
+  const IcpCall c{ctx, stream, env, plan, n, n_src, n_tgt};
+  bool launched = false;
+  IcpForm form = plan.form;
+
+  if (form == IcpForm::PerPose || form == IcpForm::Clustered || form == IcpForm::Helping) {
+    // everything of an iteration lives in LDS: the workspace holds the pointmatcher history only
+    if (a.smooth > 0) {
+      Carve cv;
+      const auto p_hist = cv.add<double>(hist_doubles(a, n));
+      cv.pad(64);
+      if ((rc = cv.ensure(ctx->d_icp_ws)) != PGP_OK) return rc;
+      a.st_hist = cv.at(p_hist);
+      PGP_HIP(hipMemsetAsync(a.st_hist, 0, p_hist.bytes(), stream));
+    }
+    a.wgs_per_pose = 1;
+    a.dbg_pose = env.dbg_pose;
+    a.slot_budget = env.slots;
+    a.rows_mode = env.rows;
+    if (env.debug) fprintf(stderr, "icp: n_cus %d, %d poses -> %d workgroups per pose\n", ctx->n_cus, n, plan.wgs_per_pose);
+    if (form == IcpForm::Clustered) {
+      if ((rc = launch_clustered(c, a, &launched)) != PGP_OK || launched) return rc;
+      form = plan.fallback;   // the grid does not fit on this device at the kernel's occupancy
+    }
+    if (form == IcpForm::Helping && ((rc = launch_helping(c, a, &launched)) != PGP_OK || launched)) return rc;
+    return launch_per_pose(c, a);   // (also when the helping grid does not fit)
+  }
+
+  HostWs w;
+  if ((rc = carve_split_ws(c, a, &w)) != PGP_OK) return rc;
+  if (form == IcpForm::Legacy) return launch_legacy(c, a);
+  if (form != IcpForm::Scene && (rc = init_split_state(c, a)) != PGP_OK) return rc;
+  if ((plan.search == IcpSearch::CappedGrid || plan.search == IcpSearch::OpenGrid) &&
+      (rc = search_grid(c, prm, d_tgt, tgt_token, a, &w)) != PGP_OK)
+    return rc;
+  if (form == IcpForm::Scene) {
+    if ((rc = launch_scene(c, a, &launched)) != PGP_OK || launched) return rc;
+    if ((rc = init_split_state(c, a)) != PGP_OK) return rc;   // the grid does not fit here: the host-driven iterations
+  }
+  return launch_host(c, a, w);
+}
+
 // Several (segment, target) jobs in ONE launch (icp_persist_multi).  Falls back to one launch_icp per job whenever
-// the single launch cannot serve them all: a target whose index does not fit LDS, a segment beyond 4096 points,
-// the point-to-plane metric, the pointmatcher history, more than kIcpMultiMax jobs.  Same results either way.
+// the single launch cannot serve them all (icp_plan.h icp_multi_plan): a target whose index does not fit LDS, a segment
+// beyond 4096 points, the point-to-plane metric, the pointmatcher history, more than kIcpMultiMax jobs.  Same results
+// either way.
 int launch_icp_multi(const IcpJob* jobs, int n_jobs, const pgp_icp_options* prm, hipStream_t stream) {
   if (n_jobs <= 0) return PGP_OK;
+  IcpMultiJob shape[kIcpMultiMax];
   for (int j = 0; j < n_jobs; ++j) {
     const IcpJob& q = jobs[j];
     if (!q.ctx || q.n < 0 || (q.n > 0 && (!q.d_src || !q.d_tgt || !q.d_T || q.n_src <= 0 || q.n_tgt <= 0))) {
@@ -4073,68 +4141,49 @@ int launch_icp_multi(const IcpJob* jobs, int n_jobs, const pgp_icp_options* prm,
       set_error("icp (multi): the jobs' contexts live on different devices (%d, %d)", jobs[0].ctx->device, q.ctx->device);
       return PGP_EINVAL;
     }
+    if (j < kIcpMultiMax) shape[j] = IcpMultiJob{q.n, q.n_src, q.ctx};
   }
+  const IcpEnv env = icp_env();
   IcpArgs a{};
-  icp_option_args(prm, 1, &a);
-  a.first_walk = 1;
-  if (const char* v = getenv("PGP_ICP_FIRST_WALK")) a.first_walk = atoi(v) < 0 ? 0 : atoi(v);
-  a.wait_ticks = icp_wait_ticks();
-  bool one_launch = n_jobs >= 2 && n_jobs <= kIcpMultiMax && a.metric == 0 && a.smooth == 0 && prm->nn_search != 1 &&
-                    prm->nn_search != 2 && !getenv("PGP_ICP_NN") && !getenv("PGP_ICP_PERSIST") && !getenv("PGP_ICP_SPLIT");
-  if (const char* v = getenv("PGP_ICP_MULTI")) one_launch = one_launch && atoi(v) != 0;   // A/B knob: 0 = job by job
-  // a context keeps ONE target index (d_icp_grid): two jobs with poses on the same context would have the second build
-  // overwrite -- or reallocate -- the image the first job's descriptor points to.  Such jobs run one after the other
-  // (each launch_icp builds its index in stream order behind the previous job's kernel).
-  for (int j = 0; j < n_jobs && one_launch; ++j)
-    for (int i = 0; i < j && one_launch; ++i)
-      if (jobs[i].n > 0 && jobs[j].n > 0 && jobs[i].ctx == jobs[j].ctx) one_launch = false;
+  icp_option_args(prm, env, 1, &a);
   IcpMulti mt{};
-  int total = 0, max_src = 0, rc;
   size_t lds = 0;
-  for (int j = 0; j < n_jobs && one_launch; ++j) {
+  // (beyond kIcpMultiMax jobs the plan says "job by job" before it looks at a job)
+  const IcpMultiPlan mp = icp_multi_plan(prm, env, shape, n_jobs, [&](int j, int first, int* rc) {
     const IcpJob& q = jobs[j];
-    mt.first[j] = total;
-    if (q.n == 0) continue;
-    if (q.n_src > kPiR * kIcpThreads) {
-      one_launch = false;
-      break;
-    }
     IcpArgs aj{};
     bool fits = false;
-    if ((rc = build_nn_index(q.ctx, q.d_tgt, q.n_tgt, q.n_src, &aj, &fits, stream, q.token)) != PGP_OK) return rc;
-    if (!fits || !aj.nn_image_in_lds) {
-      one_launch = false;
-      break;
-    }
+    if ((*rc = build_nn_index(q.ctx, env, q.d_tgt, q.n_tgt, q.n_src, &aj, &fits, stream, q.token)) != PGP_OK) return false;
+    if (!fits || !aj.nn_image_in_lds) return false;
+    mt.first[j] = first;
     IcpTarget& tg = mt.tg[j];
     tg.src = q.d_src;
     tg.nn_image = aj.nn_image;
     tg.nn_vic = aj.nn_vic;
-    tg.T = q.d_T - 16 * (ptrdiff_t)total;
-    tg.energy = q.d_energy ? q.d_energy - total : nullptr;
-    tg.iters = q.d_iters ? q.d_iters - total : nullptr;
+    tg.T = q.d_T - 16 * (ptrdiff_t)first;
+    tg.energy = q.d_energy ? q.d_energy - first : nullptr;
+    tg.iters = q.d_iters ? q.d_iters - first : nullptr;
     tg.nn = aj.nn;
     tg.n_src = q.n_src;
     tg.n_tgt = q.n_tgt;
     tg.k_trim = icp_trim_count(prm, q.n_src);
-    total += q.n;
-    max_src = q.n_src > max_src ? q.n_src : max_src;
-    const size_t l = nn_lds_bytes(aj.nn.bytes, q.n_src, true);
-    lds = l > lds ? l : lds;
-  }
-  if (one_launch && total > 0 && total <= 32768) {
+    lds = std::max(lds, (size_t)nn_lds_bytes(aj.nn.bytes, q.n_src, true));
+    return true;
+  });
+  int rc = mp.rc;
+  if (rc != PGP_OK) return rc;
+  if (mp.one_launch) {
     mt.n_jobs = n_jobs;
-    for (int j = n_jobs; j <= kIcpMultiMax; ++j) mt.first[j] = total;
+    for (int j = n_jobs; j <= kIcpMultiMax; ++j) mt.first[j] = mp.total;
     // (jobs without poses keep first[j] = first[j + 1]: no workgroup ever selects them)
     for (int j = n_jobs - 1; j >= 0; --j)
       if (jobs[j].n == 0) mt.first[j] = mt.first[j + 1];
-    a.n = total;
+    a.n = mp.total;
     a.wgs_per_pose = 1;
     a.energy = nullptr;   // per job, through the descriptor
     if ((rc = ensure_icp_attrs(jobs[0].ctx)) != PGP_OK) return rc;
-    const int pir = max_src <= 2 * kIcpBase ? 2 : (max_src <= 3 * kIcpBase ? 3 : 4);
     void* params[] = {&a, &mt};
-    PGP_HIP(hipLaunchKernel(multi_kernel(icp_trim_only(a), pir), dim3(total), dim3(kIcpThreads), params, lds, stream));
+    PGP_HIP(hipLaunchKernel(multi_kernel(mp.trim_only, mp.pir), dim3(mp.total), dim3(kIcpThreads), params, lds, stream));
     PGP_HIP(hipGetLastError());
     return PGP_OK;
   }

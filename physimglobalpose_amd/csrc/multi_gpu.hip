@@ -1381,17 +1381,13 @@ int pgp_multi_icp_refine(pgp_multi* m, const pgp_multi_icp_job* jobs, int n_jobs
       bool lost = false;
       for (int i = 0; i < dj[(size_t)p].n; ++i) lost = lost || it[i] < 0;
       if (!lost) continue;
-      struct Off {
-        Off() { pgp::icp_scene_form_off(true); }
-        ~Off() { pgp::icp_scene_form_off(false); }
-      } off;
       const pgp_multi_icp_job& q = jobs[pj[(size_t)p]];
       const int n = dj[(size_t)p].n;
       if ((r = icp_host_stage(c, q.src_xyz, q.n_src, q.tgt_xyz, q.n_tgt, q.T + 16 * (size_t)plo[(size_t)p], n, st, &stage[(size_t)p])) != PGP_OK)
         return r;
       const IcpHostStage& g2 = stage[(size_t)p];
       dj[(size_t)p] = IcpJob{c, g2.d_src, q.n_src, g2.d_tgt, q.n_tgt, g2.d_T, n, g2.d_energy, g2.d_iters, g2.token};
-      if ((r = launch_icp(c, g2.d_src, q.n_src, g2.d_tgt, nullptr, q.n_tgt, g2.d_T, n, &opt, g2.d_energy, g2.d_iters, st, g2.token)) != PGP_OK)
+      if ((r = launch_icp(c, g2.d_src, q.n_src, g2.d_tgt, nullptr, q.n_tgt, g2.d_T, n, &opt, g2.d_energy, g2.d_iters, st, g2.token, true)) != PGP_OK)
         return r;
       if ((r = icp_host_collect_enqueue(c, g2, st)) != PGP_OK) return r;
       PGP_HIP(hipStreamSynchronize(st));

@@ -2140,10 +2140,6 @@ void icp_host_collect(pgp_ctx* ctx, const IcpHostStage& g, int n, float* T, floa
 
 }  // namespace pgp
 
-namespace pgp {
-void icp_scene_form_off(bool off);   // icp.hip: this thread's next launch_icp calls take the host-driven scene-sized form
-}
-
 extern "C" {
 
 int pgp_icp_refine_ex(pgp_ctx* ctx, const float* src_xyz, int n_src, const float* tgt_xyz, const float* tgt_nrm,
@@ -2193,12 +2189,8 @@ int pgp_icp_refine_ex(pgp_ctx* ctx, const float* src_xyz, int n_src, const float
     bool lost = false;
     for (int i = 0; i < n; ++i) lost = lost || it[i] < 0;
     if (lost) {
-      struct Off {
-        Off() { pgp::icp_scene_form_off(true); }
-        ~Off() { pgp::icp_scene_form_off(false); }
-      } off;
       if ((rc = icp_host_stage(ctx, src_xyz, n_src, tgt_xyz, n_tgt, T, n, st, &g)) != PGP_OK) return rc;
-      rc = launch_icp(ctx, g.d_src, n_src, g.d_tgt, d_n, n_tgt, g.d_T, n, opt, g.d_energy, g.d_iters, st, g.token);
+      rc = launch_icp(ctx, g.d_src, n_src, g.d_tgt, d_n, n_tgt, g.d_T, n, opt, g.d_energy, g.d_iters, st, g.token, true);
       if (rc != PGP_OK) return rc;
       if ((rc = home()) != PGP_OK) return rc;
     }

@@ -79,6 +79,36 @@ struct DevBuf {
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// Carves one device buffer into typed pieces: name the pieces (type, count, alignment) in order, read bytes(), ensure() the
+// buffer (or bind() one that already holds this layout), then read typed pointers with at().  Alignments are powers of two
+// up to hipMalloc's 256.
+class Carve {
+ public:
+  template <class T> struct Piece {
+    size_t off = 0, count = 0;
+    size_t bytes() const { return count * sizeof(T); }
+  };
+  template <class T> Piece<T> add(size_t count, size_t align = alignof(T)) {
+    total_ = (total_ + align - 1) & ~(align - 1);
+    const Piece<T> p{total_, count};
+    total_ += p.bytes();
+    return p;
+  }
+  void pad(size_t bytes) { total_ += bytes; }   // slack: keeps a buffer's end clear of the last piece
+  size_t bytes() const { return total_; }
+  void bind(const DevBuf& b) { base_ = static_cast<unsigned char*>(b.p); }
+  int ensure(DevBuf& b) {
+    const int rc = b.ensure(total_);
+    bind(b);
+    return rc;
+  }
+  template <class T> T* at(const Piece<T>& p) const { return reinterpret_cast<T*>(base_ + p.off); }
+
+ private:
+  size_t total_ = 0;
+  unsigned char* base_ = nullptr;
+};
+
 // one convex shape of the physics arena (physics.hip): hull vertices and planes are float4 slices of the arena
 struct PhysShape {
   int vert_off, n_vert, plane_off, n_plane;
@@ -500,7 +530,8 @@ struct IcpJob {
 int launch_icp_multi(const IcpJob* jobs, int n_jobs, const pgp_icp_options* prm, hipStream_t stream);
 int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt, const float4* d_tgt_n, int n_tgt,
                float* d_T, int n, const pgp_icp_options* prm, float* d_energy, int* d_iters, hipStream_t stream,
-               unsigned long long tgt_token = 0);
+               unsigned long long tgt_token = 0, bool scene_form_off = false);   // scene_form_off: redo of a job the scene-sized
+                                                                                 // one-launch form lost -- host-driven this time
 
 // pgp_api.hip: a host-pointer ICP job staged in a context's buffers (pgp_icp_refine_ex; the device group's pose shards)
 struct IcpHostStage {
@@ -517,7 +548,6 @@ int icp_host_stage(pgp_ctx* ctx, const float* src_xyz, int n_src, const float* t
 int icp_host_collect_enqueue(pgp_ctx* ctx, const IcpHostStage& g, hipStream_t st);
 void icp_host_collect(pgp_ctx* ctx, const IcpHostStage& g, int n, float* T, float* energy, int* iters);
 pgp_icp_options icp_options_of(const pgp_icp_params* p);
-void icp_scene_form_off(bool off);   // icp.hip: this THREAD's next launch_icp calls take the host-driven scene-sized form
 
 // base_select.hip
 int set_ppf_map(pgp_ctx* ctx, const int* keys, const int* counts, const int* pairs, int n_keys);
