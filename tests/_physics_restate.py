@@ -47,9 +47,10 @@ def radius(verts):
 
 
 def box_inertia(verts, margin):
-    """The unit-mass inertia rule of pgp_physics_add_shape: box inertia of the hull extent + 6 margin per axis."""
+    """The unit-mass inertia rule of pgp_physics_add_shape: box inertia of the hull extent + 6 margin per axis, in
+    double from the float32 margin that the shape holds."""
     v = np.asarray(verts, np.float64)
-    l2 = ((v.max(0) - v.min(0)) + 6.0 * float(margin)) ** 2
+    l2 = ((v.max(0) - v.min(0)) + 6.0 * float(f32(margin))) ** 2
     return np.array([(l2[1] + l2[2]) / 12.0, (l2[0] + l2[2]) / 12.0, (l2[0] + l2[1]) / 12.0], np.float32)
 
 
@@ -76,21 +77,28 @@ def rigid_inverse(C):
     return I
 
 
-def quat_from_R(R):
+def quat_from_R(R, stats=None):
+    """Shepperd's method; stats (a dict, optional) receives the branch taken, 1 .. 4, under "branch"."""
     r00, r01, r02, r10, r11, r12, r20, r21, r22 = [f32(v) for v in R]
     tr = (r00 + r11) + r22
+    branch = 1
     if tr > 0:
         s = fsq(tr + ONE) * TWO
         w, x, y, z = f32(0.25) * s, fdv(r21 - r12, s), fdv(r02 - r20, s), fdv(r10 - r01, s)
     elif r00 > r11 and r00 > r22:
+        branch = 2
         s = fsq(((ONE + r00) - r11) - r22) * TWO
         w, x, y, z = fdv(r21 - r12, s), f32(0.25) * s, fdv(r01 + r10, s), fdv(r02 + r20, s)
     elif r11 > r22:
+        branch = 3
         s = fsq(((ONE + r11) - r00) - r22) * TWO
         w, x, y, z = fdv(r02 - r20, s), fdv(r01 + r10, s), f32(0.25) * s, fdv(r12 + r21, s)
     else:
+        branch = 4
         s = fsq(((ONE + r22) - r00) - r11) * TWO
         w, x, y, z = fdv(r10 - r01, s), fdv(r02 + r20, s), fdv(r12 + r21, s), f32(0.25) * s
+    if stats is not None:
+        stats["branch"] = branch
     n = fsq(((x * x + y * y) + z * z) + w * w)
     return [fdv(x, n), fdv(y, n), fdv(z, n), fdv(w, n)]
 
@@ -203,10 +211,17 @@ def default_options(**kw):
     return o
 
 
-def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
+def settle(shapes, dyn, T, table_params, cam=None, statics=(), stats=None, **opt):
     """One state.  shapes: {id: dict(verts, planes, inertia, margin)} (pgp_physics_shape_info); T (16,) column-major;
     statics: [(shape_id, T (16,))].  Returns dict(T_out (16,), state (steps,13), contacts [per step: list of
-    (point, normal, depth, lambda_n)], info (n_contacts, min_depth, lin_speed, ang_speed))."""
+    (point, normal, depth, lambda_n)], info (n_contacts, min_depth, lin_speed, ang_speed)).
+    stats: an optional dict that is filled and otherwise ignored: branch (the Shepperd branch of the start pose, 1 .. 4)
+    and, per step, candidates ([(body, count)] of the tested pairs, body 0 the table, 1 + j static j), candidate_ids
+    ([(body, candidate numbers)]), c1_ties ([(body, the candidate numbers that share the least depth)] of the pairs
+    that are reduced), skipped ([body] the sphere rule left out), clamp (the angular clamp fired) and contacts (the
+    reduced contact count)."""
+    if stats is not None:
+        stats.update(branch=None, candidates=[], candidate_ids=[], c1_ties=[], skipped=[], clamp=[], contacts=[])
     o = default_options(**opt)
     dt = f32(o["dt"])
     g = [f32(v) for v in o["gravity"]]
@@ -222,7 +237,7 @@ def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
     cam = None if cam is None else np.asarray(cam, np.float32).reshape(16)
     W = mat4_mul(cam, T) if cam is not None else T.copy()
     R0 = [W[c * 4 + i] for i in range(3) for c in range(3)]
-    q = quat_from_R(R0)
+    q = quat_from_R(R0, stats)
     x = [W[12], W[13], W[14]]
     v, w = [ZERO] * 3, [ZERO] * 3
     D = shapes[dyn]
@@ -241,7 +256,8 @@ def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
         v = [(v[i] + dt * g[i]) * lin_c for i in range(3)]
         w = [w[i] * ang_c for i in range(3)]
         L = fsq(norm2(w))
-        if L * dt > HALF_PI:
+        clamped = bool(L * dt > HALF_PI)
+        if clamped:
             sc = fdv(w_max, L)
             w = [w[i] * sc for i in range(3)]
         R = R_from_q(q)
@@ -249,15 +265,17 @@ def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
               for i in range(3) for j in range(3)]
         Dw = np.stack([((R[3 * i] * Dv[:, 0] + R[3 * i + 1] * Dv[:, 1]) + R[3 * i + 2] * Dv[:, 2]) + x[i] for i in range(3)], 1)
         contacts = []
-        for sid, B, t in bodies:
+        st_cand, st_ids, st_ties, st_skip = [], [], [], []
+        for b, (sid, B, t) in enumerate(bodies):
             S = shapes[sid]
             Sv = np.asarray(S["verts"], np.float32)
             Sp = np.asarray(S["planes"], np.float32)
             m = mD + f32(S["margin"])
             rr = (rD + radius(Sv)) + m
             if norm2([t[0] - x[0], t[1] - x[1], t[2] - x[2]]) > rr * rr:
+                st_skip.append(b)
                 continue
-            cands = []
+            cands, cand_ids = [], []
             # D's vertices against S's planes
             u = [Dw[:, i] - t[i] for i in range(3)]
             loc = np.stack([(B[i] * u[0] + B[3 + i] * u[1]) + B[6 + i] * u[2] for i in range(3)], 1)
@@ -266,6 +284,7 @@ def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
                 e = Sp[bf[k]]
                 nw = [(B[3 * i] * e[0] + B[3 * i + 1] * e[1]) + B[3 * i + 2] * e[2] for i in range(3)]
                 cands.append(([Dw[k, 0], Dw[k, 1], Dw[k, 2]], nw, best[k] - m))
+                cand_ids.append(int(k))
             # S's vertices against D's planes
             Sw = np.stack([((B[3 * i] * Sv[:, 0] + B[3 * i + 1] * Sv[:, 1]) + B[3 * i + 2] * Sv[:, 2]) + t[i] for i in range(3)], 1)
             u = [Sw[:, i] - x[i] for i in range(3)]
@@ -275,8 +294,21 @@ def settle(shapes, dyn, T, table_params, cam=None, statics=(), **opt):
                 e = Dp[bf[k]]
                 nw = [-((R[3 * i] * e[0] + R[3 * i + 1] * e[1]) + R[3 * i + 2] * e[2]) for i in range(3)]
                 cands.append(([Sw[k, 0], Sw[k, 1], Sw[k, 2]], nw, best[k] - m))
+                cand_ids.append(len(Dv) + int(k))
+            st_cand.append((b, len(cands)))
+            st_ids.append((b, cand_ids))
+            if len(cands) > 4:
+                least = min(c[2] for c in cands)
+                st_ties.append((b, [k for k, c in enumerate(cands) if c[2] == least]))
             for k in reduce4(cands):
                 contacts.append(cands[k])
+        if stats is not None:
+            stats["candidates"].append(st_cand)
+            stats["candidate_ids"].append(st_ids)
+            stats["c1_ties"].append(st_ties)
+            stats["skipped"].append(st_skip)
+            stats["clamp"].append(clamped)
+            stats["contacts"].append(len(contacts))
         rows_n, rows_f = [], []
         for p, n, depth in contacts:
             r = [p[i] - x[i] for i in range(3)]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _physics_restate as R
+import _physics_scenes as S
 from physimglobalpose_amd import LcpScorer
 from physimglobalpose_amd._lib import PgpError
 
@@ -27,9 +28,12 @@ def _ctx():
     cyl = np.concatenate([np.c_[0.03 * np.cos(a), 0.03 * np.sin(a), np.full(24, z)] for z in (-0.04, 0.04)]).astype(np.float32)
     cyl_id = s.physics_add_shape(cyl, margin=0.001)
     cloud = (np.random.default_rng(7).normal(size=(2000, 3)) * [0.04, 0.03, 0.02]).astype(np.float32)
+    # `big` is big in name only: the hull of this cloud has 32 vertices and 60 planes, so with it every pair stays
+    # within one wave of candidates.  `ell` is the real thing: 256 vertices, 508 planes.
     big_id = s.physics_add_shape(cloud, margin=0.001, max_vertices=256)
-    shapes = {i: s.physics_shape_info(i) for i in (0, box, tall, cyl_id, big_id)}
-    return s, dict(box=box, tall=tall, cyl=cyl_id, big=big_id), shapes
+    ell_id = s.physics_add_shape(S.shape_points()["ell256"], margin=0.001)
+    shapes = {i: s.physics_shape_info(i) for i in (0, box, tall, cyl_id, big_id, ell_id)}
+    return s, dict(box=box, tall=tall, cyl=cyl_id, big=big_id, ell=ell_id), shapes
 
 
 def _scenes():
@@ -131,7 +135,7 @@ def _batch(n, seed=0):
         t = t.copy()
         t[12:14] += rng.uniform(-0.02, 0.02, 2).astype(np.float32)
         extra = [(ids["big"], R.pose(t=(0.3, 0.3 * (j + 1) / 16 - 0.15, 0.03))) for j in range(int(rng.integers(0, 4)))]
-        dyn.append(d if i % 5 else ids["big"])
+        dyn.append(d if i % 5 else ids["big" if i % 10 else "ell"])
         T.append(t)
         statics.append(list(st) + extra)
     return np.array(dyn, np.int32), np.array(T, np.float32), statics
