@@ -93,22 +93,38 @@ def scene_pairs(P, N):
     return ppf_map(P, N)
 
 
-def accumulators(P, N, M, Mn, table, refs, n_bins, spairs=None):
+def accumulators(P, N, M, Mn, table, refs, n_bins, spairs=None, dev=None, stats=None):
     """acc (k, n_model, n_bins) int64 and amb (same shape): per cell, the votes within EDGE_EPS of a bin edge that
-    fell into the cell or its neighbour across that edge (the cells whose count float rounding may change)."""
+    fell into the cell or its neighbour across that edge (the cells whose count float rounding may change).
+    dev = (pairs (m, 2) of scene ids (r, j), rows): the table row (m,) -- its index in the table's order, -1: none -- or
+    the key (m, 4) to use for each of these pairs INSTEAD of its restated key (LcpScorer.ppf_features gives both for the
+    device's own key function); pairs that dev does not list do not vote.  stats: a dict that receives the number of
+    votes whose alpha_m - alpha_s was negative ("neg") and not ("nonneg")."""
     P, N, M, Mn = (np.asarray(x, np.float64) for x in (P, N, M, Mn))
-    spairs = scene_pairs(P.astype(np.float32), N.astype(np.float32)) if spairs is None else spairs
     refs = list(refs)
     pos = {r: t for t, r in enumerate(refs)}
+    assert len(pos) == len(refs), "duplicate reference points: restate the distinct ones"
     per_ref = [[] for _ in refs]
-    for key, lst in spairs.items():
-        mp = table.get(key)
-        if mp is None:
-            continue
-        for r, j in lst:
+    if dev is not None:
+        d_pairs, d_rows = np.asarray(dev[0]).reshape(-1, 2), np.asarray(dev[1])
+        lists = list(table.values())
+        for (r, j), row in zip(d_pairs.tolist(), d_rows.tolist()):
             t = pos.get(r)
-            if t is not None:
+            if t is None or r == j:
+                continue
+            mp = table.get(tuple(row)) if d_rows.ndim == 2 else (lists[row] if row >= 0 else None)
+            if mp is not None:
                 per_ref[t].append((j, mp))
+    else:
+        spairs = scene_pairs(P.astype(np.float32), N.astype(np.float32)) if spairs is None else spairs
+        for key, lst in spairs.items():
+            mp = table.get(key)
+            if mp is None:
+                continue
+            for r, j in lst:
+                t = pos.get(r)
+                if t is not None:
+                    per_ref[t].append((j, mp))
     n_model = len(M)
     Rm = frames(M, Mn)
     cache = {}
@@ -121,6 +137,9 @@ def accumulators(P, N, M, Mn, table, refs, n_bins, spairs=None):
                 cache[id(lst)] = (np.asarray(lst).reshape(-1, 2), model_alphas(M, Mn, lst, Rm))
             mp, am = cache[id(lst)]
             d = am - alpha(R, p, P[j])
+            if stats is not None:
+                stats["neg"] = stats.get("neg", 0) + int((d < 0).sum())
+                stats["nonneg"] = stats.get("nonneg", 0) + int((d >= 0).sum())
             b = bin_of(d, n_bins)
             cell = mp[:, 0] * n_bins + b
             np.add.at(acc[t], cell, 1)
@@ -132,6 +151,11 @@ def accumulators(P, N, M, Mn, table, refs, n_bins, spairs=None):
                 np.add.at(amb[t], cell[e], 1)
                 np.add.at(amb[t], mp[e, 0] * n_bins + other, 1)
     return acc.reshape(len(refs), n_model, n_bins), amb.reshape(len(refs), n_model, n_bins)
+
+
+def vote_totals(acc):
+    """Votes per (reference point, model point): independent of the binning, so of the bin-edge ambiguity too."""
+    return np.asarray(acc).sum(axis=-1)
 
 
 def peaks(acc, peaks_per_ref=1, min_vote_fraction=0.9, min_votes=3):
