@@ -687,11 +687,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_refine(IcpArgs a, const doubl
     // Thread t sums the points 4 t .. 4 t + 3 of every block of 4 x 1024 points, in index order (the persistent
     // indexed kernel maps its points the same way, so both add the same numbers in the same order): a cloud of
     // 1756 points then sits on 7 of the 16 waves, and only those pay the 17 wave-level f64 trees.
-#if defined(PGP_REFINE_ABLATE) && PGP_REFINE_ABLATE >= 4   // timing experiments (wrong results): 4 no sums loop
-    for (int b0 = 0; b0 < 0; b0 += kSumR * kIcpThreads) {
-#else
     for (int b0 = 0; b0 < (PART ? 0 : a.n_src); b0 += kSumR * kIcpThreads) {
-#endif
       unsigned key[kSumR];
       float d2v[kSumR];
       bool sel[kSumR];
@@ -776,13 +772,11 @@ __global__ __launch_bounds__(kIcpThreads) void icp_refine(IcpArgs a, const doubl
     // wave butterfly, then the 16 wave results through LDS (aliases the target tile: all reads of
     // the tile finished before the barrier after step 1)
     // point-to-point uses the first 16 sums only (the branch is wave-uniform and folds away for k < 16)
-#if !(defined(PGP_REFINE_ABLATE) && PGP_REFINE_ABLATE >= 3)   // 3: no wave sums
 #pragma unroll
     for (int k = 0; k < kRedPlane; ++k)
       if (k < 16 || a.metric == 1)
         acc[k] = wave_sum_f64(acc[k]);
     e_acc = wave_sum_f64(e_acc);
-#endif
     __syncthreads();
     if (lane == 0) {
       for (int k = 0; k < kRedPlane; ++k) s_red[wave * (kRedPlane + 1) + k] = acc[k];
@@ -810,19 +804,15 @@ __global__ __launch_bounds__(kIcpThreads) void icp_refine(IcpArgs a, const doubl
       const double E = red[0] >= 1.0 ? red[kRedPlane] / red[0] : 0.0;
       // ---- 4. closed-form update, then the progress tests (PCL order: update first) ----------
       for (int k = 0; k < 16; ++k) s_G_old[k] = s_G[k];
-#if !(defined(PGP_REFINE_ABLATE) && PGP_REFINE_ABLATE >= 2)   // 2: no solve
       if (a.metric == 1) solve_plane(red, s_G);
       else solve_rigid(red, s_G);
-#endif
       const double E_old = s_energy_old;
       s_energy = E;
       s_energy_old = E;
       bool go = it + 1 < a.max_iter;
       if (a.ratio > 0.f && !(E / E_old < (double)a.ratio)) go = false;   // TrimmedICP's energy ratio
-#if !(defined(PGP_REFINE_ABLATE) && PGP_REFINE_ABLATE >= 1)   // 1: no stop rules (runs to max_iter)
       if (red[0] < 1.0) go = false;                                        // no correspondences left
       if (converged_extra(stop_rules_of(a), pose, it + 1, s_G_old, s_G, E, E_old)) go = false;
-#endif
       s_continue = go ? 1 : 0;
     }
     __syncthreads();

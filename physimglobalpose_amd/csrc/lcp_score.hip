@@ -43,10 +43,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#if defined(PGP_CAND8) && PGP_CAND8
-#include <hip/hip_fp16.h>
-#include <map>
-#endif
 
 namespace pgp {
 
@@ -54,19 +50,6 @@ namespace {
 
 constexpr int kTile = 256;    // model points per workgroup (512 = 8 waves: +6 us per C2 step at its best hpb)
 constexpr int kMaxHpb = 64;   // hypotheses per workgroup (LDS partial slots)
-
-#if defined(PGP_ABLATE) && PGP_ABLATE == 10
-// timing experiment: where a wave's time goes.  s_memtime stamps around the phases of a trip, summed per wave
-// in SGPRs and added to g_phase at the end (read by pgp_debug_phase_cycles).  The stamps wait for the scalar
-// loads in flight, so the figures are a decomposition, not the undisturbed kernel.
-constexpr int kPhaseWaves = 65536;
-__device__ unsigned long long g_phase[kPhaseWaves][8];   // one row per wave of the launch: no atomics (they would dominate)
-#define PGP_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define PGP_PHASE(idx, t0, t1) ph[idx] += (t1) - (t0)
-#else
-#define PGP_STAMP(var)
-#define PGP_PHASE(idx, t0, t1)
-#endif
 
 struct Xf {  // one hypothesis, wave-uniform (SGPRs)
   float m00, m10, m20, m01, m11, m21, m02, m12, m22, m03, m13, m23;
@@ -319,34 +302,6 @@ struct ScoreArgs {
   const float4* kd_pts;
 };
 
-// Fused finalisation (PGP_FUSED builds, launch_score): the (tile, hypothesis) partials are ADDED to per-hypothesis
-// accumulator words whose upper 16 bits count the tiles that have arrived -- data and ticket in ONE returning atomic --,
-// and whoever arrives last turns the total into the score; no second launch.  The LAST parameter of the flat kernels,
-// read through the kernel-argument pointer at the very end of a workgroup only (fuse_args): as members of ScoreArgs
-// these fields were fetched at the top of the kernel and sat in scalar registers through the whole scoring loop.
-struct FuseArgs {
-  unsigned long long* acc;        // [2][stride]: {arrivals << 48 | inlier count}, {arrivals << 48 | fixed-point weight sum}
-  float* scores;
-  int* counts;                    // nullable
-  unsigned long long* best_key;
-  unsigned long long* runner_key;
-  unsigned int* done;
-  int* best;
-  double fx_inv;                  // 2^-shift
-  float fx_scale;                 // 2^shift of the fixed-point weight sums
-  int acc_stride;
-};
-[[maybe_unused]] constexpr size_t kFuseArgsOffset = ((sizeof(ScoreArgs) + 7) & ~(size_t)7) + 5 * sizeof(void*);
-[[maybe_unused]] __device__ __forceinline__ FuseArgs fuse_args() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned char* kp = (const unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));   // the loads below stay below
-  return *reinterpret_cast<const FuseArgs*>(kp + kFuseArgsOffset);
-#else
-  return FuseArgs{};
-#endif
-}
-
 // KdTree::doQueryRestrictedClosestIndex (kdtree.h:394-459) on the uploaded tree: the same descent (the query's side
 // of a split first, the other side only while its plane is closer than the best so far, strictly), the same
 // inclusive test inside a leaf, so that among equal distances the point the reference visits last is returned.
@@ -419,9 +374,10 @@ __device__ __forceinline__ void chunk_range(const ScoreArgs& a, int chunk, int* 
 // U hypotheses are in flight per lane: their word loads, then their offset loads, then their
 // candidate trips are issued back to back, so a wave keeps U independent dependency chains in
 // the memory system instead of one (the kernel is latency-bound: 79 % of wave cycles were
-// s_waitcnt at U = 1, profiles/r01_a_*).
-template <int MODE, int U>
+// s_waitcnt at U = 1, profiles/r01_a_*).  U = 1, 4, 8 measured within 2 % of U = 2 or slower.
+template <int MODE>
 __global__ __launch_bounds__(kTile) void score_hypotheses(ScoreArgs a) {
+  constexpr int U = 2;
   __shared__ int s_cnt[kTile / 64][kMaxHpb];
   __shared__ float s_sum[kTile / 64][kMaxHpb];
 
@@ -499,45 +455,6 @@ __global__ __launch_bounds__(kTile) void score_hypotheses(ScoreArgs a) {
   }
 }
 
-#if defined(PGP_CAND8) && PGP_CAND8
-// ---- the candidate FORMAT experiment (VERDICT r4 task 4; build knob PGP_CAND8, `make variantf FILE=lcp_score`) ----
-// 8-byte candidates instead of the 16-byte float4 {x, y, z, id}: three fp16 offsets from the CENTRE of the cell whose list the
-// candidate sits in + a 16-bit scene index -- half the candidate footprint (22.6 -> 11.3 MB at C2), so that finer cells fit the
-// footprint the 0.85-delta grid has today.  The query is expressed relative to the same centre (two VALU per axis and trip),
-// a candidate is decoded with three conversions and two shifts.  fp16 offsets carry ~4 um of error at these cell sizes:
-// inlier decisions next to the radius can differ from the exact kernel's, so this is a TIMING AND COUNTER experiment, not a
-// product path (a product would keep this test as a conservative reject and re-test survivors on the float4 array).
-// Scenes of at most 65 535 points, dense block array, flat kernels only.
-__device__ __forceinline__ float4 cand8_fetch(const float4* __restrict__ cand, uint32_t idx) {
-  const uint2 raw = reinterpret_cast<const uint2*>(cand)[idx];
-  const float hx = __half2float(__ushort_as_half((unsigned short)(raw.x & 0xFFFFu)));
-  const float hy = __half2float(__ushort_as_half((unsigned short)(raw.x >> 16)));
-  const float hz = __half2float(__ushort_as_half((unsigned short)(raw.y & 0xFFFFu)));
-  return make_float4(hx, hy, hz, __int_as_float((int)(raw.y >> 16)));
-}
-
-__global__ __launch_bounds__(256) void pack_cand8(GridDesc g, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
-                                                  const float4* __restrict__ cand, uint2* __restrict__ out, uint32_t n_words) {
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t wi = tid >> 5, bit = tid & 31u;
-  if (wi >= n_words) return;
-  const uint2 w = words[wi];
-  if (!((w.x >> bit) & 1u)) return;
-  const uint2 run = occ_run[w.y + __popc(w.x & ((1u << bit) - 1u))];
-  const uint32_t bx = wi % (uint32_t)g.nbx, by = (wi / (uint32_t)g.nbx) % (uint32_t)g.nby, bz = wi / ((uint32_t)g.nbx * (uint32_t)g.nby);
-  // lattice numbers of the cell: round(p * inv_h) for the points inside it (grid_index.hip); the centre is L * h
-  const float Lx = (float)((int)(4u * bx + (bit & 3u)) + g.k0x), Ly = (float)((int)(4u * by + ((bit >> 2) & 3u)) + g.k0y),
-              Lz = (float)((int)(2u * bz + (bit >> 4)) + g.k0z);
-  const float cx = Lx * g.h, cy = Ly * g.h, cz = Lz * g.h;
-  for (uint32_t k = 0; k < run.y; ++k) {
-    const float4 p = cand[run.x + k];
-    const unsigned hx = __half_as_ushort(__float2half_rn(p.x - cx)), hy = __half_as_ushort(__float2half_rn(p.y - cy)),
-                   hz = __half_as_ushort(__float2half_rn(p.z - cz));
-    out[run.x + k] = make_uint2(hx | (hy << 16), hz | ((unsigned)__float_as_int(p.w) << 16));
-  }
-}
-#endif
-
 // ---- wave-flattened candidate phase --------------------------------------------------------------
 // What binds the per-lane kernel above (profiles/r01_c_*): the vector L1 is busy for the whole
 // kernel (TCP_GATE_EN ~ kernel duration) at ~25 busy cycles per vector-memory WAVE-INSTRUCTION,
@@ -601,15 +518,7 @@ __device__ __forceinline__ void flat_batch(const ScoreArgs& a, const float4* __r
 #pragma unroll
   for (int c = 0; c < NC; ++c) en[c] = ent[o[c]];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) {
-#if defined(PGP_ABLATE) && PGP_ABLATE == 1
-    p[c] = cand[lane];            // timing experiment: one contiguous, always-cached 1 KB instead of the gather
-#elif defined(PGP_CAND8) && PGP_CAND8
-    p[c] = cand8_fetch(cand, __float_as_uint(en[c].w) + we[c]);   // the candidate FORMAT experiment (see cand8_fetch)
-#else
-    p[c] = cand[__float_as_uint(en[c].w) + we[c]];
-#endif
-  }
+  for (int c = 0; c < NC; ++c) p[c] = cand[__float_as_uint(en[c].w) + we[c]];
   if (MODE == PGP_MODE_WEIGHTED) {
     // keep the 16-byte loads whole: the id (.w) is only used by lanes with an in-range candidate, and
     // the compiler otherwise narrows the load to 12 bytes and sinks a dependent 4-byte load of the id
@@ -620,11 +529,7 @@ __device__ __forceinline__ void flat_batch(const ScoreArgs& a, const float4* __r
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const float d2 = sqdist(en[c].x, en[c].y, en[c].z, p[c]);
-#if defined(PGP_ABLATE) && PGP_ABLATE == 3
-    if (d2 == -1.0f) {            // timing experiment: no result traffic
-#else
     if (w0 + 64 * c + lane < W && d2 <= a.sq_eps) {
-#endif
       if (MODE == PGP_MODE_PLAIN) {
         res[o[c]] = 1ull;  // benign race: every writer stores the same value
       } else if (!TIES) {
@@ -649,16 +554,12 @@ __device__ __forceinline__ void flat_batch(const ScoreArgs& a, const float4* __r
 // would halve that again, but their 8 KB push the workgroup past 20 KB of LDS = 7 workgroups per CU.)
 constexpr int kSumGroup = 4;
 
-// Build knobs of the flat kernel (A/B through `make variant`, tools/ab_step.sh):
-//   PGP_SHORTRUN  longest run a wave's owner lanes test by themselves (0: every trip takes the flat path)
-//   PGP_PLAIN_NC  widest batch in plain mode, in chunks of 64 slots.  Four chunks used all 64 VGPRs: with the
-//                 short-trip path they spill (plain 84 -> 104 us per step); three leave 60.
-#ifndef PGP_SHORTRUN
-#define PGP_SHORTRUN 1
-#endif
-#ifndef PGP_PLAIN_NC
-#define PGP_PLAIN_NC 3
-#endif
+// Two settled constants of the flat kernel (both were A/B-measured as build knobs; figures here and at kShort):
+//   kShortRun  longest run a wave's owner lanes test by themselves (0: every trip would take the flat path)
+//   kPlainNC   widest batch in plain mode, in chunks of 64 slots.  Four chunks used all 64 VGPRs: with the
+//              short-trip path they spill (plain 84 -> 104 us per step); three leave 60.
+constexpr int kShortRun = 1;
+constexpr int kPlainNC = 3;
 
 // The read-only arrays are separate __restrict__ kernel parameters: inside the by-value struct
 // hipcc could not prove them invariant next to the LDS atomics and fetched the wave-uniform 4x4
@@ -720,22 +621,13 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
   // per-trip bookkeeping is kept to a handful of scalar instructions and off the empty path.
   unsigned long long cnt_pack = 0ull;
   uint32_t wrote = 0u;
-#if defined(PGP_ABLATE) && PGP_ABLATE == 10
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
 
   // one hypothesis (slot hs = h - h0 of the chunk) under its 4x4 `m`
   auto trip = [&](const int hs, const Xf& m) {
     const int gs = hs & (kSumGroup - 1);   // slot in the group
-    PGP_STAMP(t_a);
-#if defined(PGP_ABLATE) && PGP_ABLATE == 7
-    // timing experiment: no transform (and the 8 KB of words of experiment 4)
-    const float x = q.x + m.m03, y = q.y + m.m13, z = q.z + m.m23;
-#else
     const float x = xf_row(m.m00, m.m01, m.m02, m.m03, q.x, q.y, q.z);
     const float y = xf_row(m.m10, m.m11, m.m12, m.m13, q.x, q.y, q.z);
     const float z = xf_row(m.m20, m.m21, m.m22, m.m23, q.x, q.y, q.z);
-#endif
     // cell -> occupancy word (blocked numbering, pgp_internal.h grid_word / grid_bit)
     const uint32_t bx = cell_bits(x, inv_h_v, a.cell_c[0], cell_lo_v, a.cell_hi);
     const uint32_t by = cell_bits(y, inv_h_v, a.cell_c[1], cell_lo_v, a.cell_hi);
@@ -768,15 +660,7 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     } else {
     const uint32_t brow = mad24(__builtin_amdgcn_ubfe(bz, 1, 9), (uint32_t)a.g.nby, __builtin_amdgcn_ubfe(by, 2, 8));
     const uint32_t wi = min(mad24(brow, (uint32_t)a.g.nbx, __builtin_amdgcn_ubfe(bx, 2, 8)), a.last_word);
-#if defined(PGP_ABLATE) && (PGP_ABLATE == 4 || PGP_ABLATE == 7)
-    const unsigned long long wv = words64[wi & 1023u];   // timing experiment: occupancy words from 8 KB
-#elif defined(PGP_ABLATE) && PGP_ABLATE == 6
-    const unsigned long long wv = (unsigned long long)(wi >> 31);   // timing experiment: no word load (all empty)
-#elif defined(PGP_ABLATE) && PGP_ABLATE == 8
-    const unsigned long long wv = words64[wi] & ~0xFFFFFFFFull;    // timing experiment: real word load, all empty
-#else
     const unsigned long long wv = words64[wi];
-#endif
     lo = (uint32_t)wv;
     base = (uint32_t)(wv >> 32);
     }
@@ -784,8 +668,6 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     // lanes whose cell holds a candidate run; the second look-up runs for those lanes only
     const bool occ = __builtin_amdgcn_ubfe(lo, bit, 1) != 0u;
     const unsigned long long am = __ballot(occ);
-    PGP_STAMP(t_b);   // the occupancy word has arrived
-    PGP_PHASE(0, t_a, t_b);
     if (am == 0ull) return;   // 35 % of the wave-iterations at C2 end here: count 0, no row of s_w
     uint32_t s = 0u, len = 0u;
     if (occ) {
@@ -794,36 +676,24 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       s = (uint32_t)rv;
       len = (uint32_t)(rv >> 32);
     }
-#if defined(PGP_CAND8) && PGP_CAND8
-    // the query relative to the centre of its cell: L = round(x * inv_h) sits in the clamped lattice word, centre = L * h
-    const float h_v = a.g.h;
-    const float xq = __fmaf_rn(-__fsub_rn(__uint_as_float(bx), a.cell_c[0]), h_v, x), yq = __fmaf_rn(-__fsub_rn(__uint_as_float(by), a.cell_c[1]), h_v, y),
-                zq = __fmaf_rn(-__fsub_rn(__uint_as_float(bz), a.cell_c[2]), h_v, z);
-#else
-    const float xq = x, yq = y, zq = z;
-#endif
     uint32_t rlo = kW ? 0xFFFFFFFFu : 0u;
     // Short trips (round 3, profiles/r03_ab/shortrun.log): when every run of the wave holds at most
-    // PGP_SHORTRUN candidates, each owner lane tests its own -- no slot scan, no owner table, no LDS round
+    // kShortRun candidates, each owner lane tests its own -- no slot scan, no owner table, no LDS round
     // trips.  With 1: weighted 101.7 -> 99.2 us per step, plain 84.5 -> 83.6 (with three-chunk batches, below);
     // 2: 100.4 / 84.2; 3: 101.8; 4: 109 -- testing N candidates in every owner lane soon costs more than the
     // trips it takes off the flat path.  (Not in the weighted kernel over the sparse table: it would spill.)
-    constexpr int kShort = (SPARSE && kW) ? 0 : PGP_SHORTRUN;
+    constexpr int kShort = (SPARSE && kW) ? 0 : kShortRun;
     const bool short_trip = kShort > 0 && __ballot(len > (uint32_t)kShort) == 0ull;
     if (short_trip) {
       if (occ) {
         const uint32_t last = s + len - 1u;
         float4 pc[kShort > 0 ? kShort : 1];
 #pragma unroll
-#if defined(PGP_CAND8) && PGP_CAND8
-        for (int k = 0; k < kShort; ++k) pc[k] = cand8_fetch(cand, min(s + (uint32_t)k, last));
-#else
         for (int k = 0; k < kShort; ++k) pc[k] = cand[min(s + (uint32_t)k, last)];
-#endif
         unsigned long long best = ~0ull;
 #pragma unroll
         for (int k = 0; k < kShort; ++k) {
-          const float d2 = sqdist(xq, yq, zq, pc[k]);
+          const float d2 = sqdist(x, y, z, pc[k]);
           if (!kW) {
             if (d2 <= a.sq_eps) rlo = 1u;
           } else {
@@ -839,8 +709,6 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     const uint32_t incl = wave_inclusive_scan(len);
     const uint32_t W = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);   // >= 1
     const uint32_t pre = incl - len;
-    PGP_STAMP(t_c);   // run descriptors + scan
-    PGP_PHASE(1, t_b, t_c);
     // result of the candidate phase per owner lane (rlo): plain 0 / 1, weighted the scene id of the nearest
     // candidate within delta (all ones = -1: none)
     if (W <= (uint32_t)kFlatCap) {
@@ -848,27 +716,20 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
       if (occ) {
         // store (start - prefix) so that slot w maps to candidate (start - prefix) + w
-        ent[r] = make_float4(xq, yq, zq, __uint_as_float(s - pre));
+        ent[r] = make_float4(x, y, z, __uint_as_float(s - pre));
         res[r] = kW ? ~0ull : 0ull;
         if (TIES) res_hi[r] = ~0ull;
         atomicOr(&marks[pre >> 6], 1ull << (pre & 63u));
       }
       __builtin_amdgcn_wave_barrier();
-      PGP_STAMP(t_d);   // owner table written
-      PGP_PHASE(2, t_c, t_d);
       const uint32_t start_key = sel_mask(am, pre, 0xFFFFFFFFu);
       // batches of NC chunks of 64 slots: owner resolution, then ALL candidate loads, then tests.
       // Half of the non-empty wave-iterations need a single chunk (median W = 6 at C2), so the
-      // batch width follows what is left instead of always issuing four chunks.
+      // batch width follows what is left instead of always issuing the widest batch.
+      constexpr int kWidest = kW ? NCW : kPlainNC;
       for (uint32_t w0 = 0; w0 < W;) {
         const uint32_t left = W - w0;
-#if PGP_PLAIN_NC >= 4
-        if (!kW && left > 128) {
-          flat_batch<MODE, 4, TIES>(a, cand, ent, res, marks, start_key, W, w0, lane, le_lo, le_hi, res_hi);
-          w0 += 256;
-        } else
-#endif
-        if ((kW || PGP_PLAIN_NC == 3) && NCW >= 3 && left > 128) {
+        if (kWidest >= 3 && left > 128) {
           flat_batch<MODE, 3, TIES>(a, cand, ent, res, marks, start_key, W, w0, lane, le_lo, le_hi, res_hi);
           w0 += 192;
         } else if (left > 64) {
@@ -880,8 +741,6 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
         }
       }
       __builtin_amdgcn_wave_barrier();
-      PGP_STAMP(t_e);   // all batches done
-      PGP_PHASE(3, t_d, t_e);
       if ((uint32_t)lane < ((W + 63u) >> 6)) {   // clear the bits for the next iteration
         // (the zero is made HERE: as an ordinary constant the compiler parked a 64-bit zero in two VGPRs for the whole
         // scoring loop and, at the register ceiling, spilled it to scratch memory and reloaded it on every trip)
@@ -892,12 +751,8 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       // the low word of the owner's result: plain 0 / 1; weighted the id of the minimum key, -1 if none
       if (occ) rlo = reinterpret_cast<const uint32_t*>(res)[2 * r];
       if (TIES && kW) {   // tied candidates at the minimum: the reference's tree decides (rare)
-#if defined(PGP_ABLATE) && PGP_ABLATE == 12   // ties seen (both minima kept) but never resolved: the cost of SEEING them alone
-        if (occ && rlo != 0xFFFFFFFFu && reinterpret_cast<const uint32_t*>(res_hi)[2 * r] != ~rlo) rlo = ~reinterpret_cast<const uint32_t*>(res_hi)[2 * r];
-#else
         if (occ && rlo != 0xFFFFFFFFu && reinterpret_cast<const uint32_t*>(res_hi)[2 * r] != ~rlo)
           rlo = (uint32_t)kd_restricted_nn(a.kd_nodes, a.kd_pts, x, y, z, a.sq_eps);
-#endif
       }
     } else {
       // oversized wave-iteration (very dense scene): per-lane walk
@@ -905,7 +760,6 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       else rlo = TIES ? (uint32_t)nearest_by_rule(a, s, s + len, x, y, z) : (uint32_t)nearest_in_run(a.cand, s, s + len, x, y, z, a.sq_eps);
     }
     }
-    PGP_STAMP(t_f);   // results read back
     unsigned long long hm;   // lanes whose model point registers under this hypothesis
     if (!kW) {
       hm = __ballot(rlo != 0u);
@@ -913,11 +767,7 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       const int nn_id = (int)rlo;
       if (__ballot(nn_id >= 0) == 0ull) return;   // no lane has a neighbour within delta
       float dot = 2.0f, pw = 0.0f;   // dot = 2 fails the gate
-#if defined(PGP_ABLATE) && PGP_ABLATE == 5
-      if (nn_id == -2) {        // timing experiment: no normal gate, no weight gather
-#else
       if (nn_id >= 0) {
-#endif
         const float4 pn = Pnw[nn_id];
         const float4 qn = s_qn[threadIdx.x];
         const float nx = rot_row(m.m00, m.m01, m.m02, qn.x, qn.y, qn.z);
@@ -932,9 +782,6 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       wrote |= 1u << gs;
     }
     cnt_pack |= (unsigned long long)(uint32_t)__popcll(hm) << (8 * gs);
-    PGP_STAMP(t_g);   // gate + weight parked
-    PGP_PHASE(4, t_f, t_g);
-    PGP_PHASE(5, t_b, t_g);   // the whole non-empty part
   };
 
   // after the last hypothesis of a group (slots g0s .. g0s + n - 1 of the chunk): lane 16k publishes slot k
@@ -979,102 +826,8 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     trip(hs, m);
     if (((hs & (kSumGroup - 1)) == kSumGroup - 1) || hs == n_slots - 1) publish(hs & ~(kSumGroup - 1), (hs & (kSumGroup - 1)) + 1);
   }
-#if defined(PGP_ABLATE) && PGP_ABLATE == 10
-  if (lane == 0) {
-    const int wid = (blockIdx.x * (kTile / 64) + wave) % kPhaseWaves;
-    for (int k = 0; k < 8; ++k) g_phase[wid][k] = ph[k];
-    g_phase[wid][7] = 1ull;   // this wave ran
-  }
-#endif
   __syncthreads();
   const int hh = threadIdx.x;
-#if defined(PGP_FUSED) && PGP_FUSED
-  if (threadIdx.x >= 64) return;   // the block's <= 64 hypotheses live in wave 0
-  {
-    const FuseArgs z = fuse_args();
-    unsigned long long key = 0;
-    bool fin = false;
-    if (hh < h1 - h0) {
-      int c = 0;
-#pragma unroll
-      for (int w = 0; w < kTile / 64; ++w) c += s_cnt[w][hh];
-      float f = 0.f;
-      if (kW) {
-#pragma unroll
-        for (int w = 0; w < kTile / 64; ++w) f += s_sum[w][hh];
-      }
-      const int h = h0 + hh;
-      const unsigned long long one = 1ull << 48, low = one - 1ull;
-      const unsigned long long last_mark = (unsigned long long)(a.n_tiles - 1);
-      // both adds are in flight together: ONE round trip to the memory side
-      unsigned long long oldB = 0, oldA = 0;
-      const unsigned long long fx = kW ? (unsigned long long)__float2ll_rn(__fmul_rn(f, z.fx_scale)) : 0ull;
-      if (kW) oldB = __hip_atomic_fetch_add(&z.acc[z.acc_stride + h], one | fx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool want_a = !kW || z.counts != nullptr;
-      if (want_a) oldA = __hip_atomic_fetch_add(&z.acc[h], one | (unsigned long long)(uint32_t)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      float score = 0.f;
-      if (want_a && (oldA >> 48) == last_mark) {
-        const int total = (int)((oldA & low) + (unsigned long long)(uint32_t)c);
-        z.acc[h] = 0ull;   // re-armed for the next launch (nobody else touches it in this one)
-        if (z.counts) z.counts[h] = total;
-        if (!kW) {
-          score = __fdiv_rn((float)total, (float)a.nQ);
-          fin = true;
-        }
-      }
-      if (kW && (oldB >> 48) == last_mark) {
-        const unsigned long long sum = (oldB & low) + fx;
-        z.acc[z.acc_stride + h] = 0ull;
-        score = __fdiv_rn(__double2float_rn((double)sum * z.fx_inv), (float)a.nQ);
-        fin = true;
-      }
-      if (fin) {
-        __hip_atomic_store(&z.scores[h], score, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (score > 0.f) key = ((unsigned long long)__float_as_uint(score) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h);
-      }
-    }
-    const unsigned long long fm = __ballot(fin);
-    if (fm == 0ull) return;      // 19 of 20 blocks end here
-    // the hypotheses this block finalised: their top-2 keys, then the launch's (two atomics + the arrival count)
-    const unsigned long long mykey = key;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      unsigned long long o = __shfl_xor(key, off, 64);
-      key = o > key ? o : key;
-    }
-    unsigned long long key2 = mykey == key ? 0ull : mykey;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      unsigned long long o = __shfl_xor(key2, off, 64);
-      key2 = o > key2 ? o : key2;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the write-through score stores of this wave are complete
-    if (threadIdx.x == 0) {
-      if (key) {
-        const unsigned long long old = atomicMax(z.best_key, key);
-        const unsigned long long push = old < key ? old : key;
-        if (push) atomicMax(z.runner_key, push);
-      }
-      if (key2) atomicMax(z.runner_key, key2);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned n_fin = (unsigned)__popcll(fm);
-      const bool last = atomicAdd(z.done, n_fin) + n_fin == (unsigned)a.n_h;
-      if (last) {
-        const unsigned long long kk = atomicExch(z.best_key, 0ull);
-        atomicExch(z.runner_key, 0ull);
-        atomicExch(z.done, 0u);
-        // (experiment: weighted near-ties are NOT settled here)
-        if (kk == 0) {
-          z.best[0] = -1;
-          z.best[1] = 0;
-        } else {
-          z.best[0] = (int)(0xFFFFFFFFu - (unsigned)(kk & 0xFFFFFFFFull));
-          z.best[1] = (int)(unsigned)(kk >> 32);
-        }
-      }
-    }
-  }
-#else
   if (hh < h1 - h0) {
     int c = 0;
 #pragma unroll
@@ -1086,22 +839,15 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     }
     a.partial[(size_t)tile * a.n_h + h0 + hh] = make_uint2((uint32_t)c, __float_as_uint(f));
   }
-#endif
-#if defined(PGP_ABLATE) && PGP_ABLATE == 9
-  // timing experiment: what a per-block agent-scope release + ticket would cost (fused finalize)
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned int*>(a.partial) + 2 * chunk + 1, 1u);
-#endif
 }
 
 // 8 waves per SIMD: 64 VGPRs, 78 SGPRs, 20 KB of LDS per workgroup.  All three limits were hit while this
-// kernel was shaped (tools/ab_step.sh A/B runs): a 7-wave build with 72 VGPRs is 6 %
+// kernel was shaped (A/B runs of separately built libraries): a 7-wave build with 72 VGPRs is 6 %
 // slower, three-chunk weighted batches with spills 12 % slower, 8 KB more LDS = 7 workgroups per CU 7 %.
 template <int MODE>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
-    const float4* __restrict__ cand, const float4* __restrict__ Pnw, FuseArgs) {
+    const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<MODE, 3, false>(a, Tm, words, occ_run, cand, Pnw);
 }
 
@@ -1109,7 +855,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 template <bool SPARSE>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_ties(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
-    const float4* __restrict__ cand, const float4* __restrict__ Pnw, FuseArgs) {
+    const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<PGP_MODE_WEIGHTED, 3, SPARSE, true>(a, Tm, words, occ_run, cand, Pnw);
 }
 
@@ -1117,7 +863,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 template <int MODE>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_sparse(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
-    const float4* __restrict__ cand, const float4* __restrict__ Pnw, FuseArgs) {
+    const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<MODE, 3, true>(a, Tm, words, occ_run, cand, Pnw);
 }
 
@@ -1584,9 +1330,7 @@ __global__ __launch_bounds__(256) void finalize_scores(ScoreArgs /* read through
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-#if !(defined(PGP_ABLATE) && PGP_ABLATE == 11)   // 11: what the common launch would cost without the settlement in its code object
     settle_and_publish(score_args_in_kernarg(), n_h, mode, refine, scores, kk, best, seq, s_key);
-#endif
     if (hp.scores) {   // (settled values and the best live in device memory: the host copies them back for this call)
       __syncthreads();
       if (threadIdx.x == 0) {
@@ -1909,11 +1653,8 @@ float key2f(int32_t k) {
 // (hipExtLaunchKernelGGL) -- the kernel's own begin / end timestamps, without the two barrier
 // packets that hipEventRecord before and after the launch put on the stream (those cost the
 // C2 step 8 us, 7 % of its throughput, when per-kernel timing was on).
-#if defined(PGP_CAND8) && PGP_CAND8
-const float4* cand8_override = nullptr;   // experiment: the packed candidates of the context being launched
-#endif
 void launch_variant(int mode, int unroll, dim3 grid, hipStream_t stream, const ScoreArgs& a, hipEvent_t ev0,
-                    hipEvent_t ev1, const FuseArgs& fz = FuseArgs{}) {
+                    hipEvent_t ev1) {
   // default by measurement at C2 (tools/tune.py): wave-flattened 112 us plain / 157 us weighted vs
   // per-lane walk (U = 2) 125 / 170 us
   // (a scene so far from the origin that its lattice numbers leave the mantissa trick's range takes the
@@ -1921,40 +1662,35 @@ void launch_variant(int mode, int unroll, dim3 grid, hipStream_t stream, const S
   if (unroll <= 0 && a.g.magic_ok && a.kd_nodes && mode == PGP_MODE_WEIGHTED) {   // exact ties (pgp_set_exact_ties)
     if (a.g.sparse)
       hipExtLaunchKernelGGL(score_hypotheses_flat_ties<true>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T, a.words,
-                            a.occ_run, a.cand, a.Pnw, fz);
+                            a.occ_run, a.cand, a.Pnw);
     else
       hipExtLaunchKernelGGL(score_hypotheses_flat_ties<false>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T, a.words,
-                            a.occ_run, a.cand, a.Pnw, fz);
+                            a.occ_run, a.cand, a.Pnw);
     return;
   }
   if (unroll <= 0 && a.g.magic_ok && a.g.sparse) {  // wave-flattened candidate phase over the sparse block table
     if (mode == PGP_MODE_PLAIN)
       hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a,
-                            a.T, a.words, a.occ_run, a.cand, a.Pnw, fz);
+                            a.T, a.words, a.occ_run, a.cand, a.Pnw);
     else
       hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0,
-                            a, a.T, a.words, a.occ_run, a.cand, a.Pnw, fz);
+                            a, a.T, a.words, a.occ_run, a.cand, a.Pnw);
     return;
   }
   if (unroll <= 0 && a.g.magic_ok) {  // wave-flattened candidate phase (dense block array)
-    const float4* cand_arg = a.cand;
-#if defined(PGP_CAND8) && PGP_CAND8
-    cand_arg = cand8_override ? cand8_override : a.cand;
-#endif
     if (mode == PGP_MODE_PLAIN)
       hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T,
-                            a.words, a.occ_run, cand_arg, a.Pnw, fz);
+                            a.words, a.occ_run, a.cand, a.Pnw);
     else
       hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a,
-                            a.T, a.words, a.occ_run, cand_arg, a.Pnw, fz);
+                            a.T, a.words, a.occ_run, a.cand, a.Pnw);
     return;
   }
-#define PGP_LAUNCH(M, UU) \
-  hipExtLaunchKernelGGL((score_hypotheses<M, UU>), grid, dim3(kTile), 0, stream, ev0, ev1, 0, a)
-  // per-lane walk, two hypotheses unrolled (U = 1, 4, 8 measured within 2 % or slower)
-  if (mode == PGP_MODE_PLAIN) PGP_LAUNCH(PGP_MODE_PLAIN, 2);
-  else PGP_LAUNCH(PGP_MODE_WEIGHTED, 2);
-#undef PGP_LAUNCH
+  // per-lane walk, two hypotheses in flight per lane
+  if (mode == PGP_MODE_PLAIN)
+    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a);
+  else
+    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a);
 }
 
 int fill_args(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg, ScoreArgs* a) {
@@ -2085,30 +1821,6 @@ int launch_score(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_d
     a.partial = ctx->d_partial.as<uint2>();
     int chunks_pad = (a.n_chunks + 7) / 8 * 8;
     dim3 grid((unsigned)(chunks_pad * a.n_tiles));
-#if defined(PGP_CAND8) && PGP_CAND8
-    {
-      // experiment only: the packed copy of this context's candidate lists, rebuilt when the index changed (recognised by
-      // its array, its size and the grid's origin); never freed
-      struct Packed { DevBuf buf; const void* cand = nullptr; long long n = -1; float ox = 0.f, h = 0.f; };
-      static std::map<pgp_ctx*, Packed> packed;
-      Packed& pk = packed[ctx];
-      cand8_override = nullptr;
-      if (!ctx->grid.sparse && ctx->grid.magic_ok && ctx->nP <= 65535 && !(ctx->exact_ties && ctx->kd_valid)) {
-        if (pk.cand != ctx->d_cand.p || pk.n != ctx->n_cand || pk.ox != ctx->grid.ox || pk.h != ctx->grid.h) {
-          if ((rc = finish_index(ctx)) != PGP_OK) return rc;
-          if ((rc = pk.buf.ensure(((size_t)ctx->n_cand + 256) * 8)) != PGP_OK) return rc;
-          const uint32_t n_words = (uint32_t)ctx->grid.nbx * (uint32_t)ctx->grid.nby * (uint32_t)ctx->grid.nbz;
-          hipLaunchKernelGGL(pack_cand8, dim3((unsigned)(((size_t)n_words * 32 + 255) / 256)), dim3(256), 0, stream, ctx->grid,
-                             (const uint2*)a.words, (const uint2*)a.occ_run, (const float4*)a.cand, pk.buf.as<uint2>(), n_words);
-          pk.cand = ctx->d_cand.p;
-          pk.n = ctx->n_cand;
-          pk.ox = ctx->grid.ox;
-          pk.h = ctx->grid.h;
-        }
-        cand8_override = reinterpret_cast<const float4*>(pk.buf.p);
-      }
-    }
-#endif
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ctx->timing > 0 && (ctx->timing_seq++ % (unsigned)ctx->timing) == 0) {
       if (ctx->ev_used + 2 > ctx->ev.size()) {
@@ -2122,29 +1834,7 @@ int launch_score(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_d
       ev1 = ctx->ev[ctx->ev_used + 1];
       ctx->ev_used += 2;
     }
-#if defined(PGP_FUSED) && PGP_FUSED
-    const bool fused = ctx->unroll <= 0 && a.g.magic_ok;
-    FuseArgs fz{};
-    if (fused) {
-      fz.acc = ctx->d_acc.as<unsigned long long>();
-      fz.acc_stride = ctx->cap_h;
-      fz.scores = d_scores;
-      fz.counts = d_counts ? d_counts : (ctx->verify_early_out && mode == PGP_MODE_PLAIN ? ctx->d_counts.as<int>() : nullptr);
-      fz.best_key = key;
-      fz.runner_key = key + 3;
-      fz.done = ticket;
-      fz.best = d_best ? d_best : best_local;
-      // the weight sums in fixed point: nQ * w_max * 2^shift < 2^47 (w_max = 1: probabilities, base.cc:317-324)
-      int shift = 46 - std::ilogb((double)std::max(a.nQ, 1));
-      shift = shift > 40 ? 40 : shift;
-      fz.fx_scale = std::ldexp(1.0f, shift);
-      fz.fx_inv = std::ldexp(1.0, -shift);
-    }
-    launch_variant(mode, ctx->unroll, grid, stream, a, ev0, ev1, fz);
-    if (!fused)
-#else
     launch_variant(mode, ctx->unroll, grid, stream, a, ev0, ev1);
-#endif
     hipLaunchKernelGGL(finalize_scores, dim3((n_h + 255) / 256), dim3(256), 0, stream, a,
                        (const uint2*)a.partial, a.n_tiles, n_h, a.nQ,
                        mode, ctx->refine_best ? 1 : 0, d_scores,
@@ -2320,21 +2010,5 @@ int launch_registered(pgp_ctx* ctx, const float* d_T16, int mode, float gate_deg
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }
-
-#if defined(PGP_ABLATE) && PGP_ABLATE == 10
-extern "C" int pgp_debug_phase_cycles(unsigned long long* out16, int reset) {
-  // sums over the waves of the LAST launch(es) since the last reset: out16[0..6] phase ticks, out16[7] waves
-  std::vector<unsigned long long> h((size_t)kPhaseWaves * 8);
-  if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_phase), h.size() * 8) != hipSuccess) return -1;
-  for (int k = 0; k < 16; ++k) out16[k] = 0;
-  for (int w = 0; w < kPhaseWaves; ++w)
-    for (int k = 0; k < 8; ++k) out16[k] += h[(size_t)w * 8 + k];
-  if (reset) {
-    std::fill(h.begin(), h.end(), 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), h.data(), h.size() * 8) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 }  // namespace pgp

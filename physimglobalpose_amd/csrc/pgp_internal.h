@@ -254,7 +254,6 @@ struct pgp_ctx {
   int cap_h = 0;
   pgp::DevBuf d_T;        // staged transforms (host API)            [cap_h*16] float
   pgp::DevBuf d_partial;  // per (tile, hypothesis) partials          [n_tiles*cap_h] int2/float
-  pgp::DevBuf d_acc;      // fused finalisation (lcp_score.hip FuseArgs): the near word, then one ticket per chunk, zero between launches
   pgp::DevBuf d_scores;   // [cap_h] float
   pgp::DevBuf d_counts;   // [cap_h] int
   pgp::DevBuf d_best;     // 2 x uint64 packed argmax + {index, score bits}

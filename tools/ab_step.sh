@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B of the scoring step on ONE box: every tools/ab/libpgp_*.so (built from other commits or with
-# -DPGP_ABLATE=n timing experiments) against the in-tree library.  Usage (on the GPU box):
+# A/B of the scoring step on ONE box: every tools/ab/libpgp_*.so (built from other commits, or with
+# `make -C physimglobalpose_amd/csrc variantf`) against the in-tree library.  Usage (on the GPU box):
 #   bash tools/ab_step.sh [out_dir] [rounds]
 out=${1:-gpurun_out/ab}
 rounds=${2:-2}
