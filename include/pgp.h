@@ -208,6 +208,36 @@ typedef struct {
 } pgp_index_info;
 int pgp_get_index_info(pgp_ctx* ctx, pgp_index_info* info);
 
+/* Nearest-only candidate lists.  The scoring paths ask a cell's list for the NEAREST scene point within delta (weighted)
+ * or for ANY (plain); many entries of a list can be neither for any position inside the cell, because another entry of the
+ * list is closer everywhere in it.  The index therefore keeps a pruned twin of its lists for those paths (what it keeps
+ * of a scene is reported by pgp_get_nn_lists_info; DESIGN.md section 5 has the measured figures); the full lists stay for
+ * pgp_radius_outlier_filter, which counts every neighbour.  Scores, counts, registered points and records are the same
+ * bits with either: the rule's margin covers the float rounding of the distance test (csrc/nn_prune.h).
+ *   mode 0  off.
+ *   mode 1  (default) behind the calls: the twin is built on a side stream when the SECOND scoring launch against a
+ *           scene is issued, and later launches take it once it is complete.  No call waits for it; a scene that is
+ *           scored once pays nothing.  Launches captured into a graph neither start nor take it (a graph keeps the
+ *           lists it was captured with; both stay valid until the next pgp_set_scene).
+ *   mode 2  with the index: built, waited for and taken before the first scoring launch of a scene (callers who
+ *           know they will score many batches; tests).
+ * Takes effect at once (0 returns to the full lists; 1 and 2 apply from the next scoring launch or scene set-up).  A twin
+ * that the current scene already has is kept across mode changes and taken up again, never rebuilt: its buffers are written
+ * once per scene, so a graph captured with them may replay at any time.  The launch that starts the pass allocates its
+ * memory (once per context; a larger scene than any before grows it, which synchronises the device).
+ * The environment variable PGP_NN_PRUNE=0|1|2 sets the mode a new context starts with. */
+int pgp_set_nn_pruning(pgp_ctx* ctx, int mode);
+enum {
+  PGP_NN_LISTS_FULL = 0,     /* the scoring paths read the full lists (no twin yet, or mode 0) */
+  PGP_NN_LISTS_QUEUED = 1,   /* the twin is being built; the full lists are still in use */
+  PGP_NN_LISTS_ADOPTED = 2   /* the scoring paths read the twin */
+};
+/* state: PGP_NN_LISTS_*; entries_full / entries_kept: entries of all lists, and of the twin (0 until adopted);
+ * lists_emptied: occupied cells whose twin list came out empty (0 by the rule); pass_ms: device time of the pruning
+ * pass (0 until adopted).  Any pointer may be NULL.  Never waits. */
+int pgp_get_nn_lists_info(pgp_ctx* ctx, int* state, long long* entries_full, long long* entries_kept, long long* lists_emptied,
+                          float* pass_ms);
+
 /* Replaces `sampled_Q_3D_ = Q` (base.cc:236): the sparse search model whose points the
  * congruent quads index.  Host pointer, synchronous. */
 int pgp_set_search_model(pgp_ctx* ctx, const float* xyz, int n);

@@ -263,6 +263,9 @@ SIGNATURES = {
     "pgp_set_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "pgp_get_kernel_timing": (C.c_int, [C.c_void_p, _i, _f, C.c_int]),
     "pgp_get_index_info": (C.c_int, [C.c_void_p, C.POINTER(IndexInfo)]),
+    "pgp_set_nn_pruning": (C.c_int, [C.c_void_p, C.c_int]),
+    "pgp_get_nn_lists_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_longlong), C.POINTER(C.c_float)]),
     "pgp_plane_default_options": (C.c_int, [C.POINTER(PlaneOptions)]),
     "pgp_fit_plane": (C.c_int, [C.c_void_p, _f, C.c_int, C.POINTER(PlaneOptions), _i, C.c_int, _f, C.POINTER(C.c_ubyte), _i,
                                 C.POINTER(PlaneInfo)]),

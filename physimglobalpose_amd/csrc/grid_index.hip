@@ -28,11 +28,27 @@
 //
 // HBM layout: 28 copies of each point on average (h = 0.85 delta, two dilation rings) = 22.6 MB at
 // |P| = 50 k; the index trades capacity (288 GB) for one-run locality.
+//
+// TWIN lists.  The scoring paths only ever ask a list for the NEAREST point within delta (weighted) or for ANY
+// (plain); the neighbour count of pgp_radius_outlier_filter asks for ALL.  So the index keeps two sets of lists
+// over the same words and ranks:
+//   occ_run / cand        every point within reach of the cell (above): count_neighbours
+//   occ_run_nn / cand_nn  the entries no other entry of the same list DOMINATES -- b dominates a when b is closer
+//                         than a at every position of the (slightly inflated) cell by more than a margin that
+//                         covers the float rounding of the distance test (nn_prune.h: the rule, the margin and
+//                         why nearest / any / the tie flags come out the same bits) -- compacted in rank order:
+//                         every ScoreArgs consumer (lcp_score.hip fill_args, launch_registered_model)
+// A scene and its index stay the same over every scoring call against it, so the twin is made once per scene,
+// and BEHIND the calls: the second scoring launch against an index queues the pass (nn_mark, scan, nn_compact)
+// on the build stream, and a later launch hands out the twin once the pass's event is complete (nn_lists) --
+// no call waits, a scene scored once pays nothing, launches queued earlier keep the full lists, which stay.
+// pgp_set_nn_pruning: 0 off, 1 this, 2 with the index build.
 
 #include <mutex>
 
 #include "pgp_internal.h"
 #include "host_worker.h"
+#include "nn_prune.h"
 
 #include <cfloat>
 #include <cmath>
@@ -537,6 +553,264 @@ int await_index(pgp_ctx* ctx, hipStream_t stream) {
   return PGP_OK;
 }
 
+// The context's side stream (pgp_ctx::build_stream), created at first need.
+static int ensure_build_stream(pgp_ctx* ctx) {
+  if (ctx->build_stream) return PGP_OK;
+  // ONE side stream per device for the builds of all contexts: the runtime gives a process four hardware queues
+  // (GPU_MAX_HW_QUEUES), and a second context's own side stream came to share a queue with that context's main stream --
+  // its build then ran IN FRONT of the congruent-set search instead of beside it (the drop-in's second object: 0.75 ms
+  // per call instead of 0.55, profiles/r05_ab/hardware_queues.log).  PGP_BUILD_STREAM_PER_CONTEXT=1: a stream per context.
+  if (getenv("PGP_BUILD_STREAM_PER_CONTEXT")) {
+    PGP_HIP(hipStreamCreateWithFlags(&ctx->build_stream, hipStreamNonBlocking));
+    ctx->build_stream_own = true;
+    return PGP_OK;
+  }
+  static PerDeviceTable<hipStream_t> shared;   // (host_worker.h; never destroyed)
+  hipStream_t got = nullptr;
+  if (shared.get(ctx->device, [](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess; }, &got)) {
+    ctx->build_stream = got;
+    ctx->build_stream_own = false;
+    return PGP_OK;
+  }
+  // a device id beyond the table (or a stream that could not be created there): a stream of the context's own, never
+  // another device's
+  (void)hipGetLastError();
+  PGP_HIP(hipStreamCreateWithFlags(&ctx->build_stream, hipStreamNonBlocking));
+  ctx->build_stream_own = true;
+  return PGP_OK;
+}
+
+// ---- the nearest-only twin of the lists (nn_prune.h has the rule and why it is exact) ----------------------------
+// Three steps on the build stream: mark the survivors of every list and count them per occupied cell; exclusive scan
+// of the counts; compact the survivors, in list order, behind one another in cell-rank order and write each cell's
+// {start, count}.  Both kernels walk the occupancy WORDS (dense array or sparse table: a word knows its block's
+// coordinates, a rank does not), one wave per word, one occupied cell of the word after the other; a cell's list is
+// spread over the wave's lanes.  The occupancy words and the ranks are shared with the full lists.
+namespace {
+
+constexpr int kNnWaves = 4;   // waves per workgroup of the two kernels
+
+// occupancy word `w` of either form: {bits, rank base} and the coordinates of the block's first cell
+__device__ __forceinline__ bool nn_word(const GridDesc& g, const uint2* __restrict__ words, size_t w, uint32_t* bits,
+                                        uint32_t* base, int* x0, int* y0, int* z0) {
+  if (g.sparse) {
+    const uint4 e = reinterpret_cast<const uint4*>(words)[w];
+    if (e.x == kBlockEmpty || e.y == 0u) return false;
+    *bits = e.y;
+    *base = e.z;
+    *x0 = (int)((e.x & ((1u << g.key_sy) - 1u)) << 2);
+    *y0 = (int)(((e.x >> g.key_sy) & ((1u << (g.key_sz - g.key_sy)) - 1u)) << 2);
+    *z0 = (int)((e.x >> g.key_sz) << 1);
+    return true;
+  }
+  const uint2 e = words[w];
+  if (e.x == 0u) return false;
+  *bits = e.x;
+  *base = e.y;
+  const uint32_t bx = (uint32_t)(w % (size_t)g.nbx), by = (uint32_t)((w / (size_t)g.nbx) % (size_t)g.nby),
+                 bz = (uint32_t)(w / ((size_t)g.nbx * (size_t)g.nby));   // (pgp_internal.h grid_word)
+  *x0 = (int)(bx << 2);
+  *y0 = (int)(by << 2);
+  *z0 = (int)(bz << 1);
+  return true;
+}
+
+__device__ __forceinline__ double lane_value(float v, int j) {   // lane j's v (j wave-uniform)
+  return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
+}
+
+// keep[j] = 1 for the entries of each list that no other entry dominates; kept[rank] = how many
+__global__ __launch_bounds__(64 * kNnWaves) void nn_mark(GridDesc g, float delta, const uint2* __restrict__ words,
+                                                          size_t n_words, const uint2* __restrict__ occ_run,
+                                                          const float4* __restrict__ cand, unsigned char* __restrict__ keep,
+                                                          uint32_t* __restrict__ kept) {
+  const int lane = threadIdx.x & 63;
+  const size_t n_waves = (size_t)gridDim.x * kNnWaves;
+  for (size_t w = (size_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6); w < n_words; w += n_waves) {
+    uint32_t bits, base;
+    int x0, y0, z0;
+    if (!nn_word(g, words, w, &bits, &base, &x0, &y0, &z0)) continue;   // (wave-uniform)
+    uint32_t rank = base;
+    for (uint32_t left = bits; left; left &= left - 1u, ++rank) {
+      const int b = __ffs(left) - 1;   // pgp_internal.h grid_bit: x | y << 2 | z << 4
+      const nnp::CellBox box = nnp::cell_box(g.ox, g.oy, g.oz, g.h, g.reach, delta, x0 + (b & 3), y0 + ((b >> 2) & 3), z0 + (b >> 4));
+      const uint2 run = occ_run[rank];   // {start, count}
+      uint32_t n_kept = 0;
+      for (uint32_t a0 = 0; a0 < run.y; a0 += 64) {
+        const bool a_live = a0 + lane < run.y;
+        const float4 a = cand[run.x + min(a0 + (uint32_t)lane, run.y - 1u)];
+        const double ax = a.x, ay = a.y, az = a.z;
+        bool dominated = false;
+        for (uint32_t b0 = 0; b0 < run.y; b0 += 64) {
+          const float4 o = cand[run.x + min(b0 + (uint32_t)lane, run.y - 1u)];
+          const int nb = (int)min(64u, run.y - b0);
+          for (int j = 0; j < nb; ++j)   // (an entry never dominates itself: the margin is positive)
+            dominated |= nnp::dominated_by(box, ax, ay, az, lane_value(o.x, j), lane_value(o.y, j), lane_value(o.z, j));
+        }
+        const bool k = a_live && !dominated;
+        if (a_live) keep[run.x + a0 + lane] = k ? 1 : 0;
+        n_kept += (uint32_t)__popcll(__ballot(k));
+      }
+      if (lane == 0) kept[rank] = n_kept;
+    }
+  }
+}
+
+// the survivors of each list, in list order, at new_start[rank] of the twin; {start, count} per occupied cell
+__global__ __launch_bounds__(64 * kNnWaves) void nn_compact(GridDesc g, const uint2* __restrict__ words, size_t n_words,
+                                                             const uint2* __restrict__ occ_run, const float4* __restrict__ cand,
+                                                             const unsigned char* __restrict__ keep,
+                                                             const uint32_t* __restrict__ new_start, uint2* __restrict__ occ_nn,
+                                                             float4* __restrict__ cand_nn, uint32_t* __restrict__ n_emptied) {
+  const int lane = threadIdx.x & 63;
+  const size_t n_waves = (size_t)gridDim.x * kNnWaves;
+  for (size_t w = (size_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6); w < n_words; w += n_waves) {
+    uint32_t bits, base;
+    int x0, y0, z0;
+    if (!nn_word(g, words, w, &bits, &base, &x0, &y0, &z0)) continue;
+    uint32_t rank = base;
+    for (uint32_t left = bits; left; left &= left - 1u, ++rank) {
+      const uint2 run = occ_run[rank];
+      const uint32_t s = new_start[rank];
+      uint32_t done = 0;
+      for (uint32_t a0 = 0; a0 < run.y; a0 += 64) {
+        const bool k = a0 + lane < run.y && keep[run.x + a0 + lane] != 0;
+        const unsigned long long m = __ballot(k);
+        if (k) cand_nn[s + done + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = cand[run.x + a0 + lane];
+        done += (uint32_t)__popcll(m);
+      }
+      if (lane == 0) {
+        occ_nn[rank] = make_uint2(s, done);
+        if (done == 0u) atomicAdd(n_emptied, 1u);   // never, by the rule (nn_prune.h): counted so that a test can say so
+      }
+    }
+  }
+}
+
+bool stream_is_capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+
+void nn_adopt(pgp_ctx* ctx) {
+  ctx->nn_state = PGP_NN_LISTS_ADOPTED;
+  ctx->nn_kept = (long long)ctx->h_nn_kept[0];
+  ctx->nn_emptied = (long long)ctx->h_nn_kept[1];
+  if (hipEventElapsedTime(&ctx->nn_ms, ctx->ev_nn0, ctx->ev_nn) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->nn_ms = 0.f;
+  }
+}
+
+// Queues the pass over the finished index of the current scene on the build stream, an event behind it.
+int nn_start(pgp_ctx* ctx) {
+  if (ctx->n_occ <= 0 || ctx->n_cand <= 0) return PGP_OK;   // nothing to prune: the full lists serve
+  int rc;
+  if ((rc = ensure_build_stream(ctx)) != PGP_OK) return rc;
+  if (!ctx->ev_nn0) PGP_HIP(hipEventCreate(&ctx->ev_nn0));
+  if (!ctx->ev_nn) PGP_HIP(hipEventCreate(&ctx->ev_nn));
+  if (!ctx->h_nn_kept) PGP_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_nn_kept), 64, hipHostMallocDefault));
+  const size_t n_occ = (size_t)ctx->n_occ, n_cand = (size_t)ctx->n_cand;
+  const GridDesc g = ctx->grid;
+  const size_t n_words = g.sparse ? (size_t)g.tab_mask + 1 : (size_t)g.nbx * g.nby * g.nbz;
+  Carve ws;
+  const auto kept = ws.add<uint32_t>(n_occ + 2, 16);   // per rank, + the scan's sentinel (then the twin's starts and its
+                                                       // total), + the count of lists left empty
+  const auto tiles = ws.add<uint32_t>((n_occ + 1) / kScanTile + 4, 16);
+  const auto keep = ws.add<unsigned char>(n_cand, 16);
+  // the twin is as large as the full lists at most, and no count comes back before it is filled (same slack behind the
+  // last entry as d_cand)
+  if ((rc = ws.ensure(ctx->d_nn_ws)) != PGP_OK) return rc;
+  if ((rc = ctx->d_cand_nn.ensure((n_cand + 1 + 256) * sizeof(float4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_occ_nn.ensure((n_occ + 2) * 8)) != PGP_OK) return rc;
+  const uint2* words = g.sparse ? ctx->d_blocktab.as<uint2>() : ctx->d_bitmap.as<uint2>();
+  const uint2* occ = ctx->d_occ_start.as<uint2>();
+  const float4* cand = ctx->d_cand.as<float4>();
+  hipStream_t st = ctx->build_stream;
+  // a wave per word, up to 32 workgroups per compute unit; beyond, the waves stride over the words
+  const unsigned blocks = (unsigned)std::min<size_t>((n_words + kNnWaves - 1) / kNnWaves, (size_t)32 * (ctx->n_cus > 0 ? ctx->n_cus : 256));
+  PGP_HIP(hipEventRecord(ctx->ev_nn0, st));
+  PGP_HIP(hipMemsetAsync(ws.at(kept), 0, kept.bytes(), st));
+  hipLaunchKernelGGL(nn_mark, dim3(blocks), dim3(64 * kNnWaves), 0, st, g, ctx->delta, words, n_words, occ, cand, ws.at(keep),
+                     ws.at(kept));
+  if ((rc = device_exclusive_scan(ws.at(kept), ws.at(kept), n_occ + 1, ws.at(tiles), st)) == PGP_OK) {
+    hipLaunchKernelGGL(nn_compact, dim3(blocks), dim3(64 * kNnWaves), 0, st, g, words, n_words, occ, cand,
+                       (const unsigned char*)ws.at(keep), (const uint32_t*)ws.at(kept), ctx->d_occ_nn.as<uint2>(),
+                       ctx->d_cand_nn.as<float4>(), ws.at(kept) + n_occ + 1);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(ctx->h_nn_kept, ws.at(kept) + n_occ, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipEventRecord(ctx->ev_nn, st) != hipSuccess) {
+      set_error("nearest-only lists: the pruning pass could not be queued");
+      rc = PGP_EHIP;
+    }
+  }
+  if (rc != PGP_OK) {   // a step failed half way: nothing of it may keep running over the context's buffers
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  ctx->nn_state = PGP_NN_LISTS_QUEUED;
+  return PGP_OK;
+}
+
+// mode 2: the twin of a finished index, built, waited for and adopted
+int nn_build_now(pgp_ctx* ctx) {
+  int rc = nn_start(ctx);
+  if (rc != PGP_OK || ctx->nn_state != PGP_NN_LISTS_QUEUED) return rc;
+  PGP_HIP(hipEventSynchronize(ctx->ev_nn));
+  nn_adopt(ctx);
+  return PGP_OK;
+}
+
+}  // namespace
+
+// The launch that starts the pass also pays for its memory, once per context: the scratch, the twin (the size of the full
+// lists) and a pinned word are allocated here and kept; a scene LARGER than every one before makes the buffers grow, and
+// freeing the old ones synchronises the device.  That is host time in front of that one launch -- the pass itself is
+// waited for by nobody.
+int nn_on_scoring_launch(pgp_ctx* ctx, hipStream_t stream) {
+  ++ctx->nn_launches;
+  if (ctx->nn_mode == 0 || ctx->nn_state != PGP_NN_LISTS_FULL || !ctx->has_index) return PGP_OK;
+  if (ctx->nn_mode == 1 && (ctx->nn_launches < 2 || ctx->index_pending)) return PGP_OK;
+  if (stream_is_capturing(stream)) return PGP_OK;   // a later launch outside the capture starts it
+  if (ctx->nn_mode == 1) return nn_start(ctx);
+  const int rc = finish_index(ctx);   // mode 2 may wait: a build still running on the side stream first
+  return rc != PGP_OK ? rc : nn_build_now(ctx);
+}
+
+void nn_lists(pgp_ctx* ctx, hipStream_t stream, const uint2** occ_run, const float4** cand) {
+  if (ctx->nn_state == PGP_NN_LISTS_QUEUED && !stream_is_capturing(stream)) {
+    if (hipEventQuery(ctx->ev_nn) == hipSuccess) nn_adopt(ctx);
+    else (void)hipGetLastError();   // hipErrorNotReady is not an error
+  }
+  const bool twin = ctx->nn_mode != 0 && ctx->nn_state == PGP_NN_LISTS_ADOPTED;   // (mode 0 keeps a twin it has, unused)
+  *occ_run = twin ? ctx->d_occ_nn.as<uint2>() : ctx->d_occ_start.as<uint2>();
+  *cand = twin ? ctx->d_cand_nn.as<float4>() : ctx->d_cand.as<float4>();
+}
+
+void nn_reset(pgp_ctx* ctx) {
+  if (ctx->nn_state == PGP_NN_LISTS_QUEUED) {   // the pass reads the index buffers that are about to be rewritten
+    if (hipEventSynchronize(ctx->ev_nn) != hipSuccess) (void)hipGetLastError();
+  }
+  ctx->nn_state = PGP_NN_LISTS_FULL;
+  ctx->nn_launches = 0;
+  ctx->nn_kept = ctx->nn_emptied = 0;
+  ctx->nn_ms = 0.f;
+}
+
+void nn_destroy(pgp_ctx* ctx) {
+  nn_reset(ctx);
+  hipError_t e = hipSuccess;
+  if (ctx->ev_nn0) e = hipEventDestroy(ctx->ev_nn0);
+  if (ctx->ev_nn) e = hipEventDestroy(ctx->ev_nn);
+  if (ctx->h_nn_kept) e = hipHostFree(ctx->h_nn_kept);
+  (void)e;
+  ctx->ev_nn0 = ctx->ev_nn = nullptr;
+  ctx->h_nn_kept = nullptr;
+  ctx->d_cand_nn.release();
+  ctx->d_occ_nn.release();
+  ctx->d_nn_ws.release();
+}
+
 // The dense index of a SMALL scene, queued on ctx->build_stream and left running (see pgp_ctx::build_stream): the
 // candidate array and the occupied-cell table are sized by what nP points can reach at most, so no count has to come
 // back before the next launch.  The points are resident, or on their way (the build waits for pgp_set_scene's upload event on its stream).
@@ -544,29 +818,7 @@ static int build_index_async(pgp_ctx* ctx, const GridDesc& g, int r, float delta
   const int nP = ctx->nP;
   int rc;
   // (each on its own: a failure half way leaves what exists, and the next call goes on from there)
-  if (!ctx->build_stream) {
-    // ONE side stream per device for the builds of all contexts: the runtime gives a process four hardware queues
-    // (GPU_MAX_HW_QUEUES), and a second context's own side stream came to share a queue with that context's main stream --
-    // its build then ran IN FRONT of the congruent-set search instead of beside it (the drop-in's second object: 0.75 ms
-    // per call instead of 0.55, profiles/r05_ab/hardware_queues.log).  PGP_BUILD_STREAM_PER_CONTEXT=1: a stream per context.
-    if (getenv("PGP_BUILD_STREAM_PER_CONTEXT")) {
-      PGP_HIP(hipStreamCreateWithFlags(&ctx->build_stream, hipStreamNonBlocking));
-      ctx->build_stream_own = true;
-    } else {
-      static PerDeviceTable<hipStream_t> shared;   // (host_worker.h; never destroyed)
-      hipStream_t got = nullptr;
-      if (shared.get(ctx->device, [](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess; }, &got)) {
-        ctx->build_stream = got;
-        ctx->build_stream_own = false;
-      } else {
-        // a device id beyond the table (or a stream that could not be created there): a stream of the context's own, never
-        // another device's
-        (void)hipGetLastError();
-        PGP_HIP(hipStreamCreateWithFlags(&ctx->build_stream, hipStreamNonBlocking));
-        ctx->build_stream_own = true;
-      }
-    }
-  }
+  if ((rc = ensure_build_stream(ctx)) != PGP_OK) return rc;
   if (!ctx->ev_index) PGP_HIP(hipEventCreate(&ctx->ev_index));
   if (!ctx->ev_build0) PGP_HIP(hipEventCreate(&ctx->ev_build0));
   if (!ctx->h_build_counts) PGP_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_build_counts), 64, hipHostMallocDefault));
@@ -638,6 +890,7 @@ int build_index_bbox(pgp_ctx* ctx, const float mn[3], const float mx[3], float d
   const int nP = ctx->nP;
   hipStream_t st = ctx->stream;
   ctx->has_index = false;
+  nn_reset(ctx);   // the previous scene's twin lists go with its index; a pruning pass still running reads that index
   if (ctx->deferred_build) {   // the previous scene's build was never queued: nobody asked for its index
     ctx->deferred_build = nullptr;
     ctx->index_pending = false;
@@ -771,7 +1024,8 @@ int build_index_bbox(pgp_ctx* ctx, const float mn[3], const float mx[3], float d
   ctx->n_cand = (long long)total;
   ctx->delta = delta;
   ctx->has_index = true;
-  return PGP_OK;
+  // (a small scene's side-stream build gets its twin at the first scoring launch instead: nn_on_scoring_launch)
+  return ctx->nn_mode == 2 ? nn_build_now(ctx) : PGP_OK;
 }
 
 }  // namespace pgp

@@ -1693,7 +1693,8 @@ void launch_variant(int mode, int unroll, dim3 grid, hipStream_t stream, const S
     hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a);
 }
 
-int fill_args(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg, ScoreArgs* a) {
+// `stream`: the one the launch goes to -- which lists it reads is decided here (grid_index.hip nn_lists)
+int fill_args(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg, hipStream_t stream, ScoreArgs* a) {
   if (!ctx->has_index) {
     set_error("no scene index: call pgp_set_scene first");
     return PGP_ESTATE;
@@ -1721,11 +1722,10 @@ int fill_args(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg,
   a->cell_hi = kMagicBits + std::max(ctx->grid.nx, std::max(ctx->grid.ny, ctx->grid.nz)) - 1;
   a->last_word = (uint32_t)ctx->grid.nbx * (uint32_t)ctx->grid.nby * (uint32_t)ctx->grid.nbz - 1u;
   a->words = ctx->grid.sparse ? ctx->d_blocktab.as<uint2>() : ctx->d_bitmap.as<uint2>();
-  a->occ_run = ctx->d_occ_start.as<uint2>();
+  nn_lists(ctx, stream, &a->occ_run, &a->cand);
   const bool ties = ctx->exact_ties && ctx->kd_valid;
   a->kd_nodes = ties ? ctx->d_kd_nodes.as<int4>() : nullptr;
   a->kd_pts = ties ? ctx->d_kd_pts.as<float4>() : nullptr;
-  a->cand = ctx->d_cand.as<float4>();
   a->Pnw = ctx->d_Pnw.as<float4>();
   a->Q = ctx->d_Q.as<float4>();
   a->Qn = ctx->d_Qn.as<float4>();
@@ -1782,7 +1782,8 @@ int launch_score(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_d
   ScoreArgs a{};
   if (host) host->published = false;
   int rc = await_index(ctx, stream);
-  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, &a);
+  if (rc == PGP_OK) rc = nn_on_scoring_launch(ctx, stream);
+  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, stream, &a);
   if (rc != PGP_OK) return rc;
   if (n_h > ctx->cap_h) {
     set_error("n_h %d exceeds reserved capacity %d (pgp_reserve)", n_h, ctx->cap_h);
@@ -1859,7 +1860,7 @@ int launch_verify_early_out(pgp_ctx* ctx, const float* d_T, int n_h, float* d_sc
   if (n_h <= 0) return PGP_OK;
   ScoreArgs a{};
   int rc = await_index(ctx, stream);
-  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, PGP_MODE_PLAIN, 30.f, &a);
+  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, PGP_MODE_PLAIN, 30.f, stream, &a);
   if (rc != PGP_OK) return rc;
   if (ctx->d_eo_ws.cap < (size_t)n_h * sizeof(int) || !ctx->d_Qpos.p) {
     set_error("verify early-out: workspace not reserved (pgp_reserve / pgp_set_model)");
@@ -1882,7 +1883,7 @@ int launch_settle_best(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float 
   }
   ScoreArgs a{};
   int rc = await_index(ctx, stream);
-  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, &a);
+  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, stream, &a);
   if (rc != PGP_OK) return rc;
   hipLaunchKernelGGL(settle_best_kernel, dim3(1), dim3(256), 0, stream, a, n_h, mode, ctx->refine_best ? 1 : 0,
                      d_scores, d_best, seq_ws ? seq_ws : ctx->d_seq.as<float>(), a.nQ);
@@ -1897,7 +1898,7 @@ int launch_settle_records(pgp_ctx* ctx, const float* d_T, int n_h, int mode, flo
   if (n_h <= 0 || mode != PGP_MODE_WEIGHTED) return PGP_OK;   // plain counts are exact already
   ScoreArgs a{};
   int rc = await_index(ctx, stream);
-  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, &a);
+  if (rc == PGP_OK) rc = fill_args(ctx, d_T, n_h, mode, gate_deg, stream, &a);
   if (rc != PGP_OK) return rc;
   if (ctx->d_rec_ws.cap < (size_t)records_workspace_bytes(ctx->nQ)) {
     set_error("exact records: workspace not reserved (pgp_set_exact_records after pgp_set_model)");
@@ -1981,8 +1982,7 @@ int launch_registered_model(pgp_ctx* ctx, const float* d_T16, const float4* d_q,
   ScoreArgs a{};
   a.g = ctx->grid;
   a.words = ctx->grid.sparse ? ctx->d_blocktab.as<uint2>() : ctx->d_bitmap.as<uint2>();
-  a.occ_run = ctx->d_occ_start.as<uint2>();
-  a.cand = ctx->d_cand.as<float4>();
+  nn_lists(ctx, stream, &a.occ_run, &a.cand);
   a.Pnw = ctx->d_Pnw.as<float4>();
   a.T = d_T16;
   a.n_h = 1;
@@ -1999,7 +1999,7 @@ int launch_registered(pgp_ctx* ctx, const float* d_T16, int mode, float gate_deg
                       hipStream_t stream) {
   ScoreArgs a{};
   int rc = await_index(ctx, stream);
-  if (rc == PGP_OK) rc = fill_args(ctx, d_T16, 1, mode, gate_deg, &a);
+  if (rc == PGP_OK) rc = fill_args(ctx, d_T16, 1, mode, gate_deg, stream, &a);
   if (rc != PGP_OK) return rc;
   if (ctx->nQ == 0) return PGP_OK;
   dim3 grid((ctx->nQ + 255) / 256);

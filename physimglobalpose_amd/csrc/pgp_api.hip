@@ -165,6 +165,10 @@ int pgp_create(pgp_ctx** out, int device_id) {
   if (const char* v = getenv("PGP_UNROLL")) ctx->unroll = atoi(v);
   if (const char* v = getenv("PGP_HPB")) ctx->hpb_override = atoi(v);
   if (const char* v = getenv("PGP_REFINE")) ctx->refine_best = atoi(v) != 0;
+  if (const char* v = getenv("PGP_NN_PRUNE")) {
+    const int m = atoi(v);
+    if (m >= 0 && m <= 2) ctx->nn_mode = m;
+  }
   e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -191,6 +195,7 @@ int pgp_destroy(pgp_ctx* ctx) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
     (void)e;
   }
+  nn_destroy(ctx);   // (awaits a pruning pass still on the build stream)
   {
     hipError_t e = hipSuccess;
     if (ctx->build_stream) {
@@ -733,6 +738,35 @@ int pgp_set_exact_ties(pgp_ctx* ctx, int on) {
   CtxGuard guard(ctx);
   ctx->exact_ties = on != 0;
   if (!ctx->exact_ties) ctx->kd_valid = false;   // the next pgp_set_scene builds the tree again if asked to
+  return PGP_OK;
+}
+
+int pgp_set_nn_pruning(pgp_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) {
+    set_error("pgp_set_nn_pruning: bad argument (mode 0, 1 or 2)");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  ctx->nn_mode = mode;   // (0: a twin this scene already has stays as it is, unused -- a graph captured with it may still replay)
+  return PGP_OK;
+}
+
+int pgp_get_nn_lists_info(pgp_ctx* ctx, int* state, long long* entries_full, long long* entries_kept, long long* lists_emptied,
+                          float* pass_ms) {
+  if (!ctx) {
+    set_error("pgp_get_nn_lists_info: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  DeviceGuard guard(ctx->device);
+  const uint2* occ;
+  const float4* cand;
+  nn_lists(ctx, ctx->stream, &occ, &cand);   // (notices a finished pass)
+  const bool twin = ctx->nn_mode != 0 && ctx->nn_state == PGP_NN_LISTS_ADOPTED;
+  if (state) *state = ctx->nn_mode != 0 ? ctx->nn_state : PGP_NN_LISTS_FULL;
+  if (entries_full) *entries_full = ctx->has_index && !ctx->index_pending ? ctx->n_cand : 0;
+  if (entries_kept) *entries_kept = twin ? ctx->nn_kept : 0;
+  if (lists_emptied) *lists_emptied = twin ? ctx->nn_emptied : 0;
+  if (pass_ms) *pass_ms = twin ? ctx->nn_ms : 0.f;
   return PGP_OK;
 }
 

@@ -165,6 +165,20 @@ struct pgp_ctx {
   std::function<int()> deferred_build;
   uint32_t* h_build_counts = nullptr;   // pinned {candidates, occupied cells} of the pending build
   pgp::DevBuf d_build_scan;             // the build's own scan scratch (d_scan_tmp serves the congruent sets meanwhile)
+  // Nearest-only twin of the lists (grid_index.hip, nn_prune.h): the entries of each list that can be the NEAREST point of
+  // some query of the cell, compacted in cell-rank order, with their own {start, count} array.  Words and ranks are shared
+  // with the full lists, which stay (count_neighbours counts ALL neighbours).  Built on build_stream behind the calls
+  // (nn_on_scoring_launch) and handed out by nn_lists once ev_nn is complete.
+  int nn_mode = 1;                      // pgp_set_nn_pruning: 0 off, 1 behind the calls, 2 with the index build
+  int nn_state = PGP_NN_LISTS_FULL;     // PGP_NN_LISTS_*: full lists in use, twin queued, twin adopted
+  int nn_launches = 0;                  // scoring launches issued against the current index
+  pgp::DevBuf d_cand_nn;                // float4 {x,y,z,bits(i)} [nn_kept], room for n_cand (no count comes back first)
+  pgp::DevBuf d_occ_nn;                 // uint2 {start, count} per occupied cell [n_occ]
+  pgp::DevBuf d_nn_ws;                  // the pass's scratch: kept counts / their scan | scan tiles | keep flags
+  hipEvent_t ev_nn0 = nullptr, ev_nn = nullptr;
+  uint32_t* h_nn_kept = nullptr;        // pinned: {entries kept, lists left empty}, written behind the pass
+  long long nn_kept = 0, nn_emptied = 0;   // ... taken over at adoption
+  float nn_ms = 0.f;                    // device time of the pass
 
   // model
   int nQ = 0;
@@ -498,6 +512,14 @@ int launch_settle_best(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float 
 // ctx->build_stream (a no-op otherwise); finish_index() waits for it on the host and takes over its counts
 int await_index(pgp_ctx* ctx, hipStream_t stream);
 int finish_index(pgp_ctx* ctx);
+// grid_index.hip, the nearest-only twin of the lists (pgp_ctx::nn_mode).  A scoring launch on `stream` announces itself
+// (the second one against an index queues the pruning pass on the build stream; nobody waits for it); every launch that asks
+// "nearest" or "any" then takes its {start, count} array and its candidates from nn_lists -- the twin once its event is
+// complete, the full lists until then.  Neither starts nor adopts while `stream` is being captured into a graph.
+int nn_on_scoring_launch(pgp_ctx* ctx, hipStream_t stream);
+void nn_lists(pgp_ctx* ctx, hipStream_t stream, const uint2** occ_run, const float4** cand);
+void nn_reset(pgp_ctx* ctx);     // the index is about to change (or the mode went to 0): awaits a pass in flight, back to the full lists
+void nn_destroy(pgp_ctx* ctx);   // pgp_destroy: the above + events, pinned word and buffers
 int launch_settle_records(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg, float* d_scores,
                           hipStream_t stream);
 int launch_verify_early_out(pgp_ctx* ctx, const float* d_T, int n_h, float* d_scores, int* d_counts, hipStream_t stream);

@@ -1027,6 +1027,20 @@ class LcpScorer:
         _lib.check(self._lib.pgp_get_index_info(self._h, C.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
+    def set_nn_pruning(self, mode=1):
+        """Nearest-only twin of the index's candidate lists (pgp_set_nn_pruning): 0 off, 1 built behind the calls from the
+        second scoring launch against a scene on, 2 built with the index and in use from the first launch."""
+        _lib.check(self._lib.pgp_set_nn_pruning(self._h, int(mode)))
+
+    def nn_lists_info(self):
+        """{"state": 0 full lists / 1 twin queued / 2 twin adopted, "entries_full", "entries_kept", "lists_emptied",
+        "pass_ms"}; never waits."""
+        st, full, kept, emptied, ms = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_float(0)
+        _lib.check(self._lib.pgp_get_nn_lists_info(self._h, C.byref(st), C.byref(full), C.byref(kept), C.byref(emptied),
+                                                   C.byref(ms)))
+        return {"state": st.value, "entries_full": full.value, "entries_kept": kept.value, "lists_emptied": emptied.value,
+                "pass_ms": float(ms.value)}
+
     # ---- physics settling: UCTState::correctPhysics (csrc/physics.hip) ----------------------------------------------
     @staticmethod
     def physics_options(**kw):
