@@ -428,6 +428,83 @@ int pgp_congruent_batch_sample_fit_score_list(pgp_ctx* ctx, unsigned long long s
 /* Host helper: the picks that call draws, from the quad counts alone.  picks (nullable: count only) [sum][2] = (base, quad). */
 int pgp_sample_quads(unsigned long long seed, const int* n_quads, int n_bases, int max_per_base, int* picks, int* n_picks);
 
+/* ---- The matcher's tetrahedron-base mode (operMode 2, "V4PCS"): pose hypotheses from POSITIONS ALONE ----------------------
+ * Needs the scene (pgp_set_scene, positions), the search model (pgp_set_search_model) and, for the scores of
+ * pgp_v4pcs_hypotheses, the validation model (pgp_set_model); no normals, no pair-feature table, no probability image.
+ * Its workspaces are its own: a resident pgp_find_congruent_batch batch survives these calls and the other way round.
+ *
+ * LIMIT: the widest-triangle rule places bases on the EXTREME points of the scene cloud, so the mode wants a clean segment.
+ * In a CPU prototype of the rule (300-point search model, 155-point clean segment) all 100 bases lay on the object; with 40
+ * clutter points in a box padded by 5 cm around the segment, none of 100 did.
+ *
+ * pgp_select_tetrahedron_bases replaces n_attempts calls of Match4PCSBase::SelectTetrahedronBase (base.cc:466-503, over
+ * SelectRandomTriangle :377-410) on the scene: a random first point; over triangle_trials (reference: 1000) random
+ * (second, third) draws the triangle with the largest |u x w| (strict `>` from 0: the first maximum in trial order) whose
+ * two edges from the first point are both shorter than max_base_diameter; over fourth_trials (reference: 100) random fourth
+ * points the one with the largest |(v1 x v2) . v3| / 6 (strict `>` from 0: a zero volume never wins).  One attempt is one
+ * (triangle, fourth point) trial: a caller who wants 100 bases asks for more attempts and keeps the first 100 with status 1.
+ * max_base_diameter (> 0): the reference takes the largest of 1000 random pair distances of the search model
+ * (base.cc:274-287); the model's diameter or any such estimate serves.
+ * The reference draws from rand() seeded from the clock; here attempt a draws from the counter-based generator of
+ * pgp_sample_quads: with st = state(seed, a) and r(i) = variate(st, i) % n: first = r(0); trial i: second = r(1 + 2 i),
+ * third = r(2 + 2 i); fourth draw k: r(1 + 2 triangle_trials + k).  Floats: every operation rounded on its own, cross products
+ * as (a.y b.z - a.z b.y, ...), dot products and squared norms as (x x + y y) + z z, correctly rounded sqrt and divide.
+ * ids[n_attempts][4] (scene ids; -1 where status is 0), dist[n_attempts][6] = |b0 b1|, |b0 b2|, |b0 b3|, |b1 b2|, |b1 b3|,
+ * |b2 b3| (d1 .. d6 of FindCongruentQuadrilateralsV4PCS; 0 where status is 0), status[n_attempts]: 1 = base, 0 = none (no
+ * triangle within the diameter, or every fourth point coplanar).  The same bits from call to call.  Host pointers, synchronous. */
+int pgp_select_tetrahedron_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, int fourth_trials,
+                                 float max_base_diameter, int* ids, float* dist, int* status);
+
+/* Replaces FindCongruentQuadrilateralsV4PCS (base.cc:978-1044) and the six ExtractPairs calls that feed it (:1963-1969,
+ * :1998-2020) for one base, over the search model (4 .. PGP_V4PCS_MAX_POINTS points, else PGP_EINVAL; none: PGP_ESTATE):
+ * (v1, v2, v3, v4) is a quad iff (v1,v2)~d1, (v1,v3)~d2, (v1,v4)~d3, (v2,v3)~d4, (v2,v4)~d5 and (v3,v4)~d6, where (a,b)~d
+ * is pgp_extract_pairs' predicate: a != b and not (| |q_a - q_b| - d | > eps), float distance, comparison in double,
+ * inclusive; symmetric in (a, b).  dist[6] = d1 .. d6 as pgp_select_tetrahedron_bases returns them, eps = distance_factor *
+ * delta, un-normalised.  If any of the six pair sets is empty there is no quad (:2022-2024).
+ * Quads come out in ASCENDING (v1, v2, v3, v4) order (the reference's goes through an unordered_set and is unspecified).
+ * quads: cap x 4 ints, the first min(*n_quads, cap) quads in that order; *n_quads = the full count.
+ * COST: the count visits every (v1, v2, v3) that passes its three predicates, so the time grows with the number of QUADS, not
+ * with cap / per_base_cap (which bound only what is written): 100 bases on a 4096-point surface with eps = 5 mm hold 164 M
+ * quads and take 186 ms; an eps as large as the model makes the count cubic in the model's size, seconds per base. */
+#define PGP_V4PCS_MAX_POINTS 4096
+int pgp_find_congruent_v4pcs(pgp_ctx* ctx, const float dist[6], float eps, int* quads, int cap, long long* n_quads);
+/* The same for n_bases bases at once (dist[n_bases][6]; at most 65535).  n_quads[n_bases] (nullable): every base's full
+ * count; n_stored[n_bases] (nullable): min(n_quads, per_base_cap) -- a base KEEPS its first per_base_cap quads in ascending
+ * order, on the device, until the next batch call or pgp_set_search_model; whoever samples quads afterwards draws from that
+ * kept prefix.  pgp_v4pcs_batch_quads copies picked quads to the host: picks[m][2] = (base, j), the j-th kept quad of that
+ * base, quads[m][4]; a pick at or past n_stored is PGP_EINVAL, no resident batch PGP_ESTATE. */
+int pgp_find_congruent_v4pcs_batch(pgp_ctx* ctx, const float* dist, int n_bases, float eps, int per_base_cap, long long* n_quads,
+                                   int* n_stored);
+int pgp_v4pcs_batch_quads(pgp_ctx* ctx, const int* picks, int m, int* quads);
+
+/* The mode as one call (Perform_N_steps in operMode 2, base.cc:1837-1842, :1855-1874, :1494-1499):
+ *   1. max_attempts attempts of pgp_select_tetrahedron_bases(seed, ...); the first n_bases with status 1 are the bases
+ *      (fewer when the attempts run out);
+ *   2. pgp_find_congruent_v4pcs_batch(their dist, eps, per_base_cap);
+ *   3. the picks pgp_sample_quads(seed, n_stored, max_per_base) draws (at most max_per_base <= 128 kept quads per base);
+ *   4. the fit of pgp_rigid_from_congruent: the base's four scene ids against the quad's four model ids;
+ *   5. the plain score of pgp_score_lcp (PGP_MODE_PLAIN; plain Verify, base.cc:1498-1499).  A fit with status != 1 scores 0.
+ * Outputs, with room for n_bases x max_per_base hypotheses: T[.][16], pose[.][16] (nullable), status[.], scores[.],
+ * picks[.][2] (nullable); *n_hyp = how many there are; *n_bases / base_ids[n_bases][4] (nullable): the bases found.
+ * best_index (nullable) = the lowest index of the greatest score, -1 when no hypothesis scores above 0 (best_T / best_pose
+ * are then left alone); best_score, best_T[16], best_pose[16] nullable.  The join's quads stay resident as after step 2.
+ * Host pointers, synchronous. */
+typedef struct pgp_v4pcs_options {
+  unsigned long long seed;
+  int n_bases;             /* 100 */
+  int max_attempts;        /* 200 */
+  int triangle_trials;     /* 1000 */
+  int fourth_trials;       /* 100 */
+  float max_base_diameter; /* no default: the model's diameter or an estimate of it, > 0 */
+  float eps;               /* 0.005 */
+  int max_per_base;        /* 100 */
+  int per_base_cap;        /* 4096 */
+} pgp_v4pcs_options;
+int pgp_v4pcs_default_options(pgp_v4pcs_options* opt);
+int pgp_v4pcs_hypotheses(pgp_ctx* ctx, const pgp_v4pcs_options* opt, const float centroid_P[3], const float centroid_Q[3],
+                         int* n_bases, int* base_ids, int* n_hyp, float* T, double* pose, int* status, float* scores, int* picks,
+                         int* best_index, float* best_score, float* best_T, double* best_pose);
+
 /* ICP refinement.  Replaces the inner loop behind pcl::recognition::TrimmedICP::align
  * (PPE/hypothesis_verification/mcts/UCTState.cpp:137-139,194; PPE/misc/utilities.cpp:666-676) and
  * pcl::IterativeClosestPoint::align (utilities.cpp:697-703; PPE/data_layer/SceneCfg.cpp:101,135-141)

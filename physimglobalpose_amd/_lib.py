@@ -81,6 +81,12 @@ class PpfOptions(C.Structure):
                 ("min_votes", C.c_int)]
 
 
+class V4pcsOptions(C.Structure):
+    _fields_ = [("seed", C.c_ulonglong), ("n_bases", C.c_int), ("max_attempts", C.c_int), ("triangle_trials", C.c_int),
+                ("fourth_trials", C.c_int), ("max_base_diameter", C.c_float), ("eps", C.c_float), ("max_per_base", C.c_int),
+                ("per_base_cap", C.c_int)]
+
+
 class PhysicsOptions(C.Structure):
     _fields_ = [("dt", C.c_float), ("steps", C.c_int), ("gravity", C.c_float * 3), ("linear_damping", C.c_float),
                 ("angular_damping", C.c_float), ("friction", C.c_float), ("iterations", C.c_int), ("erp", C.c_float)]
@@ -285,6 +291,13 @@ SIGNATURES = {
                                      _f]),
     "pgp_ppf_accumulator": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), _i, C.c_int, _i]),
     "pgp_ppf_model_angles": (C.c_int, [C.c_void_p, _f, C.c_longlong]),
+    "pgp_select_tetrahedron_bases": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_float, _i, _f, _i]),
+    "pgp_find_congruent_v4pcs": (C.c_int, [C.c_void_p, _f, C.c_float, _i, C.c_int, C.POINTER(C.c_longlong)]),
+    "pgp_find_congruent_v4pcs_batch": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_longlong), _i]),
+    "pgp_v4pcs_batch_quads": (C.c_int, [C.c_void_p, _i, C.c_int, _i]),
+    "pgp_v4pcs_default_options": (C.c_int, [C.POINTER(V4pcsOptions)]),
+    "pgp_v4pcs_hypotheses": (C.c_int, [C.c_void_p, C.POINTER(V4pcsOptions), _f, _f, _i, _i, _i, _f, C.POINTER(C.c_double), _i, _f,
+                                       _i, _i, _f, _f, C.POINTER(C.c_double)]),
     "pgp_physics_default_options": (C.c_int, [C.POINTER(PhysicsOptions)]),
     "pgp_convex_hull": (C.c_int, [_f, C.c_int, C.c_int, _f, _i, _f, _i]),
     "pgp_physics_add_shape": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, _i]),

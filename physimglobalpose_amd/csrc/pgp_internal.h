@@ -197,6 +197,16 @@ struct pgp_ctx {
   float cs_ratio = 1.f;
   pgp::DevBuf d_cs_cnt, d_cs_entries, d_cs_keys;   // congruent-set workspaces
   pgp::DevBuf d_cs_pairs, d_cs_out;                // host-API staging
+  // tetrahedron-base mode (v4pcs.hip): workspaces of its own, so that a resident congruent batch (d_cs_*) and a resident
+  // V4PCS batch survive each other's calls
+  pgp::DevBuf d_v4_sel;                 // base selection: ids | distances | status
+  pgp::DevBuf d_v4_mat;                 // the six bit matrices of one chunk of bases
+  pgp::DevBuf d_v4_ws;                  // base distances | totals | row counts | row starts
+  pgp::DevBuf d_v4_quads;               // resident quads of the last batch: int4 [v4_nb][v4_cap]
+  pgp::DevBuf d_v4_picks, d_v4_io;      // staged picks; host-API staging (single-base quads, the chain's ids and results)
+  int v4_nb = 0;                        // bases of the last pgp_find_congruent_v4pcs_batch; 0 once the search model is rewritten
+  int v4_cap = 0;                       // its per_base_cap
+  std::vector<int> v4_stored;           // quads kept per base (v4_nb), host copy: picks are checked here
   pgp::DevBuf d_ids;     // staged int4 base / quad ids (host API)
   pgp::DevBuf d_rig;     // staged rigid-fit outputs (host API)
 
@@ -488,6 +498,15 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
 int launch_congruent_batch_gather(pgp_ctx* ctx, const int* h_picks, int m, int4* d_quads, hipStream_t st,
                                   const int2* d_picks_there = nullptr);
 const uint32_t* congruent_batch_starts_device(pgp_ctx* ctx);
+
+// v4pcs.hip
+int launch_tetrahedron_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, int fourth_trials,
+                             float max_base_diameter, int* h_ids, float* h_dist, int* h_status, hipStream_t st);
+int launch_v4pcs_join(pgp_ctx* ctx, const float* h_dist, int nb, float eps, long long cap, int4* d_quads, long long* h_counts,
+                      hipStream_t st);
+int launch_v4pcs_batch(pgp_ctx* ctx, const float* h_dist, int nb, float eps, int per_base_cap, long long* h_n_quads, int* h_n_stored,
+                       hipStream_t st);
+int launch_v4pcs_gather(pgp_ctx* ctx, const int* h_picks, int m, int4* d_out, hipStream_t st);
 
 // lcp_score.hip
 int tiles_for(int nQ);

@@ -376,6 +376,79 @@ class LcpScorer:
             pose.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(_i), _fp(rms)))
         return T[:n], pose[:n], status[:n], rms[:n]
 
+    # ---- tetrahedron-base mode, "V4PCS" (base.cc:466-503, 978-1044): positions alone ------------------
+    def select_tetrahedron_bases(self, seed, n_attempts, max_base_diameter, triangle_trials=1000, fourth_trials=100):
+        """pgp_select_tetrahedron_bases on the scene: (ids (n,4) int32, dist (n,6) f32 = d1..d6, status (n,) int32)."""
+        n = int(n_attempts)
+        ids = np.zeros((max(n, 1), 4), np.int32)
+        dist = np.zeros((max(n, 1), 6), np.float32)
+        status = np.zeros(max(n, 1), np.int32)
+        _lib.check(self._lib.pgp_select_tetrahedron_bases(self._h, C.c_ulonglong(int(seed)), n, int(triangle_trials), int(fourth_trials),
+                                                          C.c_float(max_base_diameter), ids.ctypes.data_as(_i), _fp(dist),
+                                                          status.ctypes.data_as(_i)))
+        return ids[:n], dist[:n], status[:n]
+
+    def find_congruent_v4pcs(self, dist, eps, cap=None):
+        """One base's quads over the search model, ascending (v1, v2, v3, v4): ((min(n, cap), 4) int32, the full count n)."""
+        d = _f32(dist).reshape(6)
+        n = C.c_longlong(0)
+        if cap is None:
+            _lib.check(self._lib.pgp_find_congruent_v4pcs(self._h, _fp(d), C.c_float(eps), None, 0, C.byref(n)))
+            cap = n.value
+        out = np.zeros((max(int(cap), 1), 4), np.int32)
+        _lib.check(self._lib.pgp_find_congruent_v4pcs(self._h, _fp(d), C.c_float(eps), out.ctypes.data_as(_i), int(cap), C.byref(n)))
+        return out[: min(n.value, int(cap))].copy(), n.value
+
+    def find_congruent_v4pcs_batch(self, dist, eps, per_base_cap=4096):
+        """All bases at once (dist (nb,6)); the kept quads stay on the device.  Returns (n_quads (nb,) int64, n_stored (nb,) int32)."""
+        d = _f32(dist).reshape(-1, 6)
+        nq = np.zeros(max(len(d), 1), np.int64)
+        ns = np.zeros(max(len(d), 1), np.int32)
+        _lib.check(self._lib.pgp_find_congruent_v4pcs_batch(self._h, _fp(d), len(d), C.c_float(eps), int(per_base_cap),
+                                                            nq.ctypes.data_as(C.POINTER(C.c_longlong)), ns.ctypes.data_as(_i)))
+        return nq[: len(d)], ns[: len(d)]
+
+    def v4pcs_batch_quads(self, picks):
+        pk = np.ascontiguousarray(picks, np.int32).reshape(-1, 2)
+        out = np.zeros((max(len(pk), 1), 4), np.int32)
+        _lib.check(self._lib.pgp_v4pcs_batch_quads(self._h, pk.ctypes.data_as(_i), len(pk), out.ctypes.data_as(_i)))
+        return out[: len(pk)]
+
+    @staticmethod
+    def v4pcs_options(max_base_diameter, **kw):
+        o = _lib.V4pcsOptions()
+        _lib.check(_lib.load().pgp_v4pcs_default_options(C.byref(o)))
+        o.max_base_diameter = float(max_base_diameter)
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError(f"pgp_v4pcs_options has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def v4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), **opt):
+        """pgp_v4pcs_hypotheses: bases, join, sampling, fits and plain scores in one call.  Returns a dict: base_ids, T, pose,
+        status, scores, picks (of the n_hyp hypotheses), best_index, best_score, best_T, best_pose."""
+        o = self.v4pcs_options(max_base_diameter, **opt)
+        cP, cQ = _f32(centroid_P).reshape(3), _f32(centroid_Q).reshape(3)
+        cap = max(int(o.n_bases) * int(o.max_per_base), 1)
+        bids = np.zeros((max(int(o.n_bases), 1), 4), np.int32)
+        T = np.zeros((cap, 16), np.float32)
+        pose = np.zeros((cap, 16), np.float64)
+        status = np.zeros(cap, np.int32)
+        scores = np.zeros(cap, np.float32)
+        picks = np.zeros((cap, 2), np.int32)
+        bT, bp = np.zeros(16, np.float32), np.zeros(16, np.float64)
+        nb, nh, best = C.c_int(0), C.c_int(0), C.c_int(-1)
+        bs = C.c_float(0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(self._lib.pgp_v4pcs_hypotheses(
+            self._h, C.byref(o), _fp(cP), _fp(cQ), C.byref(nb), bids.ctypes.data_as(_i), C.byref(nh), _fp(T), pose.ctypes.data_as(dp),
+            status.ctypes.data_as(_i), _fp(scores), picks.ctypes.data_as(_i), C.byref(best), C.byref(bs), _fp(bT), bp.ctypes.data_as(dp)))
+        k = nh.value
+        return dict(base_ids=bids[: nb.value].copy(), T=T[:k].copy(), pose=pose[:k].copy(), status=status[:k].copy(),
+                    scores=scores[:k].copy(), picks=picks[:k].copy(), best_index=best.value, best_score=float(np.float32(bs.value)),
+                    best_T=bT, best_pose=bp)
+
     # ---- segment pre-processing (ObjectPoseCandidateSet.cpp:28-51) -----------------------------------
     def radius_outlier_filter(self, xyz, nrm=None, radius=0.03, min_neighbors=10):
         """Returns (keep mask (n,) bool, flipped + re-normalised normals (n,3) or None)."""

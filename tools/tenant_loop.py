@@ -5,6 +5,7 @@ resident workgroups (the table alignment, SceneCfg.cpp:101,135-141) -- for `seco
 result against the first call's bits.  Two of these side by side on ONE device are the node beside another libpgp user (or the
 segmentation CNN): tests/test_two_tenants_gpu.py.  Prints one JSON line.
 usage: python tools/tenant_loop.py seconds [tag]"""
+import gc
 import hashlib
 import json
 import os
@@ -42,6 +43,8 @@ def main():
     first = {k: digest(f()) for k, f in calls.items()}
     for f in calls.values():   # warm
         f()
+    gc.collect()
+    gc.disable()   # a full collector pass (45-80 ms over torch's and numpy's objects, due about 2200 loops in) is not the library's time: tools/icp_hiccup_probe.py
     times = {k: [] for k in calls}
     bad = {k: 0 for k in calls}
     # the other tenant starts at about the same time: a barrier through the file system
