@@ -1079,8 +1079,9 @@ int pgp_mcts_default_options(pgp_mcts_options* opt);
  * receive the best leaf state (bestState): its hypothesis ids and its settled poses (camera frame); *best_score its
  * renderScore (bestRenderScore).  info (nullable).  trace (nullable, trace_cap records): one record per descent in
  * order; *n_trace (nullable) the number of descents, which may exceed trace_cap (the list is then truncated).
- * PGP_EINVAL: n_obj outside 1..17, n_hyp < 1, a NaN or negative score, a non-finite pose, an unknown shape id, a bad
- * mesh, leaves_per_step outside 1..256, alpha not finite, max_iterations <= 0, bad physics options, NULL observed.
+ * PGP_EINVAL: n_obj outside 1..17, n_hyp < 1, a NaN, infinite or negative score, a non-finite pose, an unknown shape
+ * id, a bad mesh, leaves_per_step outside 1..256, alpha not finite, max_iterations <= 0, bad physics options, NULL
+ * observed.
  * Synchronous; the context stays usable after an error. */
 int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_object* objs, int n_obj,
                     const float table_params[12], const float cam_pose[16], const pgp_camera* cam, const float* observed,

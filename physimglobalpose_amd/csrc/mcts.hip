@@ -191,7 +191,7 @@ int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_o
       return PGP_EINVAL;
     }
     for (int h = 0; h < o.n_hyp; ++h)
-      if (!(o.scores[h] >= 0.f)) {   // NaN or negative
+      if (!std::isfinite(o.scores[h]) || o.scores[h] < 0.f) {   // NaN, +-inf or negative
         set_error("%s: object %d hypothesis %d has score %g (finite, >= 0 expected)", who, l, h, (double)o.scores[h]);
         return PGP_EINVAL;
       }

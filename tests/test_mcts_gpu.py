@@ -2,117 +2,17 @@
 through the single-stage host calls (physics_settle, render_depth under the parent image, depth_cost): traces, best
 states and settled poses bit for bit at B = 1, 8 and 64; recovery of a settled ground-truth stack; determinism; the
 stop rules; the error cases."""
-import functools
-
 import numpy as np
 import pytest
 
 import _mcts_restate as M
 import _physics_restate as R
-from physimglobalpose_amd import LcpScorer, PGP_MODE_PLAIN, synth
+from _mcts_scenes import (BOX_TRIS, CAM_POSE, SIZES, TABLE, HostEvaluator, _check_parity, _ctx, _objects, _observed,
+                          cam_T)
+from physimglobalpose_amd import PGP_MODE_PLAIN, synth
 from physimglobalpose_amd._lib import PgpError
 
 pytestmark = pytest.mark.gpu
-f32 = np.float32
-TABLE = R.table_params(0.0)
-# a camera 0.8 m above the table top, looking straight down (column-major; its own rigid inverse)
-CAM_POSE = np.array([1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0.8, 1], np.float32)
-ROWS, COLS = 240, 320
-K = np.array([[500, 0, 160], [0, 500, 120], [0, 0, 1]], np.float32)
-BOX_TRIS = np.array([[0, 1, 3], [0, 3, 2], [4, 5, 7], [4, 7, 6], [0, 1, 5], [0, 5, 4], [2, 3, 7], [2, 7, 6],
-                     [0, 2, 6], [0, 6, 4], [1, 3, 7], [1, 7, 5]], np.int32)
-SIZES = [(0.06, 0.05, 0.03), (0.035, 0.03, 0.025), (0.03, 0.045, 0.03)]
-
-
-def cam_T(yaw_deg, x, y, z):
-    """Camera-frame column-major pose of a world pose (yaw about +z, translation)."""
-    W = np.eye(4)
-    W[:3, :3] = R.rot("z", yaw_deg)
-    W[:3, 3] = (x, y, z)
-    C = CAM_POSE.reshape(4, 4).T.astype(np.float64)
-    return (C @ W).astype(np.float32).T.reshape(16).copy()
-
-
-@functools.lru_cache(maxsize=None)
-def _ctx():
-    s = LcpScorer()
-    ids = [s.physics_add_shape(R.box_points(*h), margin=0.001) for h in SIZES]
-    return s, ids
-
-
-def _objects(n_hyp, seed):
-    """Boxes with n_hyp[i] hypotheses each, scattered above the table around a ground-truth arrangement."""
-    s, ids = _ctx()
-    rng = np.random.default_rng(seed)
-    objs = []
-    centres = [(0.0, 0.0), (0.09, 0.02), (-0.08, -0.03)]
-    for i, n in enumerate(n_hyp):
-        hx, hy, hz = SIZES[i]
-        T = np.stack([cam_T(rng.uniform(-40, 40), centres[i][0] + rng.uniform(-0.03, 0.03),
-                            centres[i][1] + rng.uniform(-0.03, 0.03), hz + rng.uniform(0.005, 0.02)) for _ in range(n)])
-        sc = rng.uniform(0.1, 1.0, n).astype(np.float32)
-        sc[rng.integers(n)] = sc.max()   # a tie: the last maximum is expanded first
-        objs.append(dict(shape_id=ids[i], vertices=R.box_points(hx, hy, hz), triangles=BOX_TRIS, T=T, scores=sc))
-    return objs
-
-
-class HostEvaluator:
-    """Evaluates leaf states with one host call per stage: the pose of a state is settled once per prefix of hypothesis
-    ids (physics depends on the state's objects only), its image is the parent's image with the newest object drawn."""
-
-    def __init__(self, objs, cam, observed):
-        self.s, _ = _ctx()
-        self.objs, self.cam, self.obs = objs, cam, observed
-        self.poses, self.images = {}, {}
-
-    def pose(self, prefix):
-        if prefix not in self.poses:
-            l = len(prefix) - 1
-            ob = self.objs[l]
-            statics = [(self.objs[j]["shape_id"], self.pose(prefix[:j + 1])) for j in range(l)]
-            out, _ = self.s.physics_settle([ob["shape_id"]], ob["T"][prefix[-1]][None], TABLE, cam_pose=CAM_POSE,
-                                           statics=[statics])
-            self.poses[prefix] = out[0]
-        return self.poses[prefix]
-
-    def image(self, prefix):
-        if prefix not in self.images:
-            ob = self.objs[len(prefix) - 1]
-            parent = self.image(prefix[:-1]) if len(prefix) > 1 else None
-            self.images[prefix] = self.s.render_depth(ob["vertices"], ob["triangles"], self.pose(prefix)[None], self.cam,
-                                                      parent=parent)[0]
-        return self.images[prefix]
-
-    def __call__(self, states):
-        return [self.s.depth_cost(self.obs, self.image(st)[None], 0.01)[0][0] for st in states]
-
-
-def _observed(objs, hyp):
-    cam = LcpScorer.camera(K, ROWS, COLS)
-    ev = HostEvaluator(objs, cam, np.zeros((ROWS, COLS), np.float32))
-    return cam, ev.image(tuple(hyp)), ev
-
-
-def _check_parity(objs, cam, observed, **opt):
-    s, _ = _ctx()
-    got = s.mcts_search(objs, TABLE, cam, observed, cam_pose=CAM_POSE, **opt)
-    ev = HostEvaluator(objs, cam, observed)
-    ref = M.search([o["scores"] for o in objs], ev, max_expansions=opt.get("max_expansions", 0),
-                   max_iterations=opt["max_iterations"], alpha=opt.get("alpha", 5000.0), rollout=opt.get("rollout", 0),
-                   seed=opt.get("seed", 0), leaves_per_step=opt.get("leaves_per_step", 1), n_pix=ROWS * COLS)
-    tr = got["trace"]
-    assert len(tr) == len(ref["trace"]) == got["n_trace"]
-    for a, b in zip(tr, ref["trace"]):
-        assert (a["step"], a["t"], a["depth"], tuple(a["hyp"]), a["evaluated"]) == \
-               (b["step"], b["t"], b["depth"], b["hyp"], b["evaluated"]), b["t"]
-        assert a["render_score"] == b["render_score"] and a["reward"] == b["reward"], b["t"]
-    assert tuple(got["best_hyp"]) == ref["best_hyp"]
-    assert got["best_score"] == ref["best_score"]
-    best_T = np.stack([ev.pose(ref["best_hyp"][:l + 1]) for l in range(len(objs))])
-    np.testing.assert_array_equal(got["best_T"].view(np.uint32), best_T.view(np.uint32))
-    for k in ("descents", "steps", "expansions", "settle_evaluations", "stop_reason"):
-        assert got["info"][k] == ref["info"][k], k
-    return got, ref
 
 
 @pytest.mark.parametrize("rollout", [0, 1])
