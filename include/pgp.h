@@ -505,6 +505,75 @@ int pgp_v4pcs_hypotheses(pgp_ctx* ctx, const pgp_v4pcs_options* opt, const float
                          int* n_bases, int* base_ids, int* n_hyp, float* T, double* pose, int* status, float* scores, int* picks,
                          int* best_index, float* best_score, float* best_T, double* best_pose);
 
+/* ---- The matcher's classic mode (operMode 0, "Super4PCS"): wide planar bases, two pair lists per base -----------------------
+ * Needs the scene (pgp_set_scene, positions), the search model (pgp_set_search_model) and, for the scores of
+ * pgp_super4pcs_hypotheses, the validation model (pgp_set_model); no normals, no pair-feature table, no probability image.
+ *
+ * pgp_select_wide_bases replaces n_attempts calls of Match4PCSBase::SelectQuadrilateral (base.cc:505-580, over
+ * SelectRandomTriangle :377-410 and TryQuadrilateral :415-464) on the scene.  One attempt is one triangle and one search for
+ * the fourth point; the reference's retry loop becomes "ask for more attempts and keep the first n with status 1".
+ * Triangle: the rule, the draw and the rounding of pgp_select_tetrahedron_bases (first = r(0); trial i: second = r(1 + 2 i),
+ * third = r(2 + 2 i); the widest |u x w|, strict `>` from 0, both edges from the first point shorter than max_base_diameter).
+ * Fourth point (:527-565): with the nine coordinates of the triangle as doubles, denom = -x3 y2 z1 + x2 y3 z1 + x3 y1 z2 -
+ * x1 y3 z2 - x2 y1 z3 + x1 y2 z3 (left to right, products as (a b) c), narrowed to float; denom == 0: status 0.  A, B, C =
+ * (their double numerators, :542-547) / (double)denom, narrowed to float.  too_small = (float)pow((double)(max_base_diameter *
+ * 0.1f), 2).  Scene point i qualifies when its squared distances to the three, (x x + y y) + z z in float, are all >= too_small;
+ * its distance = (float)fabs((double)((A x + B y) + C z) - 1.0) with float products and sums.  The smallest distance wins,
+ * strict `<` from FLT_MAX walking i upward: the lowest index among equals, never a NaN or an infinite one; no winner: status 0.
+ * TryQuadrilateral then reorders the four ids and gives the invariants, as pgp_base_invariants does.
+ * ids[n_attempts][4] (scene ids in their final order; -1 where status is 0), invariants[n_attempts][2], dist[n_attempts][2] =
+ * |b0 b1|, |b2 b3| of the reordered base (distance1 / distance6 of :1952-1953; norms as x x + (y y + z z), correctly rounded
+ * sqrt; 0 where status is 0), status[n_attempts]: 1 = base, 0 = none.  max_base_diameter <= 0 or a negative count: PGP_EINVAL;
+ * no scene: PGP_ESTATE.  The same bits from call to call.  Host pointers, synchronous. */
+int pgp_select_wide_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, float max_base_diameter,
+                          int* ids, float* invariants, float* dist, int* status);
+
+/* pgp_extract_pairs for n_lists distances at once (the two ExtractPairs calls per base of :1963-1969): list k is exactly what
+ * pgp_extract_pairs(dist[k], eps) returns -- the same predicate, the same order ((j, i) then (i, j) for i > j, in (i, j)
+ * order) -- and all lists STAY ON THE DEVICE, in a buffer of the context's own, until the next pgp_extract_pairs_batch or
+ * pgp_set_search_model.  n_pairs[n_lists] (nullable): pairs per list.  A list of 2^24 pairs or more, or 2^31 in all:
+ * PGP_EINVAL (the join's keys hold a pair index in 24 bits); at most 131070 lists over at most 65536 points; no search model:
+ * PGP_ESTATE.  pgp_extract_pairs_batch_fetch copies list `list` to the host: *n_pairs = its full count, pairs[cap][2] receives
+ * the first min(count, cap); a list out of range: PGP_EINVAL, no resident lists: PGP_ESTATE. */
+int pgp_extract_pairs_batch(pgp_ctx* ctx, const float* dist, int n_lists, float eps, int* n_pairs);
+int pgp_extract_pairs_batch_fetch(pgp_ctx* ctx, int list, int* pairs, int cap, int* n_pairs);
+
+/* pgp_find_congruent_batch with every base's pair lists taken from the lists of pgp_extract_pairs_batch instead of the
+ * pair-feature table: lists[n_bases][2] = (pairs1, pairs6) list numbers, base_xyz[n_bases][4][3], invariants[n_bases][2],
+ * n_quads[n_bases].  Per base the quads and their order are those of pgp_find_congruent on the two fetched lists; a base with
+ * an empty list has none (:1984).  The result is THE resident quad batch of the context (there is one): pgp_congruent_batch_quads,
+ * _fit, _fit_score, _fit_score_list, _sample_fit_score_list and _fetch work on it unchanged; it replaces a batch of
+ * pgp_find_congruent_batch and is replaced by one; a new pgp_extract_pairs_batch or pgp_set_search_model discards it
+ * (PGP_ESTATE from the calls above).  A list number out of range: PGP_EINVAL; no resident lists: PGP_ESTATE. */
+int pgp_find_congruent_batch_lists(pgp_ctx* ctx, const float* base_xyz, const float* invariants, const int* lists, int n_bases,
+                                   float threshold, int* n_quads);
+
+/* The mode as one call (Perform_N_steps in operMode 0, base.cc:1837-1842, :1855-1874, :1494-1499):
+ *   1. max_attempts attempts of pgp_select_wide_bases(seed, ...); the first n_bases with status 1 are the bases (fewer when
+ *      the attempts run out);
+ *   2. pgp_extract_pairs_batch over their 2 n distances (base b: lists 2 b and 2 b + 1), with eps;
+ *   3. pgp_find_congruent_batch_lists, threshold = eps (distance_factor is 1);
+ *   4. the picks pgp_sample_quads(seed, n_quads, max_per_base) draws (max_per_base <= 128);
+ *   5. the fit of pgp_rigid_from_congruent: the base's four scene ids against the quad's four model ids;
+ *   6. the plain score of pgp_score_lcp (PGP_MODE_PLAIN; plain Verify, :1494-1499).  A fit with status != 1 scores 0.
+ * Outputs as pgp_v4pcs_hypotheses, with room for n_bases x max_per_base hypotheses, plus base_invariants[n_bases][2]
+ * (nullable).  best_index = the lowest index of the greatest score, -1 when no hypothesis scores above 0.  No base found: zero
+ * hypotheses, best_index -1, PGP_OK.  The pair lists and the quad batch stay resident as after steps 2 and 3.
+ * Host pointers, synchronous. */
+typedef struct pgp_super4pcs_options {
+  unsigned long long seed;
+  int n_bases;             /* 100 */
+  int max_attempts;        /* 200 */
+  int triangle_trials;     /* 1000 */
+  float max_base_diameter; /* no default: the model's diameter or an estimate of it, > 0 */
+  float eps;               /* 0.005 */
+  int max_per_base;        /* 100 */
+} pgp_super4pcs_options;
+int pgp_super4pcs_default_options(pgp_super4pcs_options* opt);
+int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const float centroid_P[3], const float centroid_Q[3],
+                             int* n_bases, int* base_ids, float* base_invariants, int* n_hyp, float* T, double* pose, int* status,
+                             float* scores, int* picks, int* best_index, float* best_score, float* best_T, double* best_pose);
+
 /* ICP refinement.  Replaces the inner loop behind pcl::recognition::TrimmedICP::align
  * (PPE/hypothesis_verification/mcts/UCTState.cpp:137-139,194; PPE/misc/utilities.cpp:666-676) and
  * pcl::IterativeClosestPoint::align (utilities.cpp:697-703; PPE/data_layer/SceneCfg.cpp:101,135-141)

@@ -87,6 +87,11 @@ class V4pcsOptions(C.Structure):
                 ("per_base_cap", C.c_int)]
 
 
+class Super4pcsOptions(C.Structure):
+    _fields_ = [("seed", C.c_ulonglong), ("n_bases", C.c_int), ("max_attempts", C.c_int), ("triangle_trials", C.c_int),
+                ("max_base_diameter", C.c_float), ("eps", C.c_float), ("max_per_base", C.c_int)]
+
+
 class PhysicsOptions(C.Structure):
     _fields_ = [("dt", C.c_float), ("steps", C.c_int), ("gravity", C.c_float * 3), ("linear_damping", C.c_float),
                 ("angular_damping", C.c_float), ("friction", C.c_float), ("iterations", C.c_int), ("erp", C.c_float)]
@@ -298,6 +303,13 @@ SIGNATURES = {
     "pgp_v4pcs_default_options": (C.c_int, [C.POINTER(V4pcsOptions)]),
     "pgp_v4pcs_hypotheses": (C.c_int, [C.c_void_p, C.POINTER(V4pcsOptions), _f, _f, _i, _i, _i, _f, C.POINTER(C.c_double), _i, _f,
                                        _i, _i, _f, _f, C.POINTER(C.c_double)]),
+    "pgp_select_wide_bases": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_int, C.c_float, _i, _f, _f, _i]),
+    "pgp_extract_pairs_batch": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, _i]),
+    "pgp_extract_pairs_batch_fetch": (C.c_int, [C.c_void_p, C.c_int, _i, C.c_int, _i]),
+    "pgp_find_congruent_batch_lists": (C.c_int, [C.c_void_p, _f, _f, _i, C.c_int, C.c_float, _i]),
+    "pgp_super4pcs_default_options": (C.c_int, [C.POINTER(Super4pcsOptions)]),
+    "pgp_super4pcs_hypotheses": (C.c_int, [C.c_void_p, C.POINTER(Super4pcsOptions), _f, _f, _i, _i, _f, _i, _f, C.POINTER(C.c_double),
+                                           _i, _f, _i, _i, _f, _f, C.POINTER(C.c_double)]),
     "pgp_physics_default_options": (C.c_int, [C.POINTER(PhysicsOptions)]),
     "pgp_convex_hull": (C.c_int, [_f, C.c_int, C.c_int, _f, _i, _f, _i]),
     "pgp_physics_add_shape": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, _i]),

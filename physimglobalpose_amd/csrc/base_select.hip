@@ -4,7 +4,7 @@
 // call, base.cc:613-614, so attempts do not share state):
 //   Match4PCSBase::SelectQuadrilateralStoCS   S4/algorithms/match4pcsBase.cc:600-792
 //   Match4PCSBase::computePPF                 :582-598        approximate_bin  :150-160
-//   Match4PCSBase::TryQuadrilateral           :415-464        distSegmentToSegment  :81-148
+//   Match4PCSBase::TryQuadrilateral           :415-464        distSegmentToSegment  :81-148     (base_device.h: shared with super4pcs.hip)
 //   the presence test PPFMap->find(ppf_) of the model's pair-feature table (PPE/data_layer/Objects.cpp:31-49)
 //
 // Mapping: one 256-thread workgroup per attempt walks the three weighting loops -- a lane per scene
@@ -31,6 +31,7 @@
 
 #include "pgp_internal.h"
 #include "ppf_key.h"
+#include "base_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -79,20 +80,6 @@ __device__ __forceinline__ float stage3_weight(const SelectArgs& a, int i, float
   const unsigned long long key = ppf_key(a.tab, pb, nb, ld3(a.P, i), {pn.x, pn.y, pn.z}, nullptr);
   const float edge = table_find(a.tab, key) >= 0 ? 1.f : 0.f;
   return mul(mul(cur_i, prob_b), edge);  // cur[i] * orig[base2] * edge
-}
-
-struct Plane {
-  float denom, A, B, C;
-};
-__device__ __forceinline__ Plane fit_plane(V3 q1, V3 q2, V3 q3) {  // base.cc:731-745, double arithmetic
-  const double x1 = q1.x, y1 = q1.y, z1 = q1.z, x2 = q2.x, y2 = q2.y, z2 = q2.z, x3 = q3.x, y3 = q3.y, z3 = q3.z;
-  Plane p;
-  p.denom = (float)(-x3 * y2 * z1 + x2 * y3 * z1 + x3 * y1 * z2 - x1 * y3 * z2 - x2 * y1 * z3 + x1 * y2 * z3);
-  const double dd = (double)p.denom;
-  p.A = (float)((-y2 * z1 + y3 * z1 + y1 * z2 - y3 * z2 - y1 * z3 + y2 * z3) / dd);
-  p.B = (float)((x2 * z1 - x3 * z1 - x1 * z2 + x3 * z2 + x1 * z3 - x2 * z3) / dd);
-  p.C = (float)((-x2 * y1 + x3 * y1 + x1 * y2 - x3 * y2 - x1 * y3 + x2 * y3) / dd);
-  return p;
 }
 
 __device__ __forceinline__ float stage4_weight(const SelectArgs& a, int i, float cur_i, int b1, int b2, int b3,
@@ -196,111 +183,6 @@ __device__ int draw_index(const float* __restrict__ w, int n, double u, double* 
   const int r = *s_pick;
   __syncthreads();
   return r;
-}
-
-// Closest approach of the segments P(s) = p1 + s u and Q(t) = q1 + t v, s, t in [0, 1]: the parameters
-// are kept as fractions sN / sD and tN / tD of the 2 x 2 system's determinant and clamped edge by edge
-// (the classic closed form the reference's distSegmentToSegment follows, base.cc:81-148).  Arithmetic
-// as TryQuadrilateral instantiates it: float dot products widened to double, double fractions, the
-// invariants narrowed to float before the residual vector is formed.  Returns |w + s u - t v|.
-__device__ float seg_seg(V3 p1, V3 p2, V3 q1, V3 q2, double* invariant1, double* invariant2) {
-  const double tiny = 0.0001;
-  const V3 u = vsub(p2, p1), v = vsub(q2, q1), w = vsub(p1, q1);
-  const double uu = dot(u, u), uv = dot(u, v), vv = dot(v, v), uw = dot(u, w), vw = dot(v, w);
-  const double det = uu * vv - uv * uv;
-  double sN, sD = det, tN, tD = det;
-  if (det < tiny) {            // (almost) parallel: pin s = 0 and project q-side only
-    sN = 0.0;
-    sD = 1.0;
-    tN = vw;
-    tD = vv;
-  } else {                      // interior solution of the unconstrained problem, then the s-edges
-    sN = uv * vw - vv * uw;
-    tN = uu * vw - uv * uw;
-    if (sN < 0.0) {
-      sN = 0.0;
-      tN = vw;
-      tD = vv;
-    } else if (sN > sD) {
-      sN = sD;
-      tN = vw + uv;
-      tD = vv;
-    }
-  }
-  if (tN < 0.0) {               // t-edges: re-solve s on the edge t = 0 or t = 1
-    tN = 0.0;
-    const double m = -uw;
-    if (m < 0.0) sN = 0.0;
-    else if (m > uu) sN = sD;
-    else {
-      sN = m;
-      sD = uu;
-    }
-  } else if (tN > tD) {
-    tN = tD;
-    const double m = -uw + uv;
-    if (m < 0.0) sN = 0;
-    else if (m > uu) sN = sD;
-    else {
-      sN = m;
-      sD = uu;
-    }
-  }
-  *invariant1 = fabs(sN) < tiny ? 0.0 : sN / sD;
-  *invariant2 = fabs(tN) < tiny ? 0.0 : tN / tD;
-  const float fs = (float)*invariant1, ft = (float)*invariant2;   // Eigen narrows the double scalars
-  const V3 r = {sub(add(w.x, mul(fs, u.x)), mul(ft, v.x)), sub(add(w.y, mul(fs, u.y)), mul(ft, v.y)),
-                sub(add(w.z, mul(fs, u.z)), mul(ft, v.z))};
-  return norm(r);
-}
-
-// TryQuadrilateral on lanes 0..11 of the calling wave (all 64 lanes call): pairing p enumerates
-// (i, j) in the reference's loop order; the first minimum wins (strict <).
-__device__ void try_quadrilateral(const float4* __restrict__ P, int ids[4], float* inv1, float* inv2) {
-  const int lane = threadIdx.x & 63;
-  const int p = lane < 12 ? lane : 0;
-  const int i = p / 3;
-  int j = p % 3;
-  j += j >= i ? 1 : 0;
-  int k = 0;
-  while (k == i || k == j) k++;
-  int l = 0;
-  while (l == i || l == j || l == k) l++;
-  V3 q[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) q[t] = ld3(P, ids[t]);
-  auto pick = [&](int t) { return t == 0 ? q[0] : (t == 1 ? q[1] : (t == 2 ? q[2] : q[3])); };
-  double li1, li2;
-  float sd = seg_seg(pick(i), pick(j), pick(k), pick(l), &li1, &li2);
-  if (lane >= 12 || !(sd == sd)) sd = __int_as_float(0x7F800000);   // NaN never passes `<`
-  // arg-min with the lowest pairing index on ties: key = (distance bits, pairing)
-  unsigned long long key = ((unsigned long long)__float_as_uint(sd) << 8) | (unsigned)p;   // sd >= 0
-#pragma unroll
-  for (int off = 8; off >= 1; off >>= 1) {
-    const unsigned long long o = __shfl_xor(key, off, 64);
-    key = o < key ? o : key;
-  }
-  key = __shfl(key, 0, 64);   // lanes 0..15 hold the minimum of lanes 0..15
-  const int bp = (int)(key & 0xFFu);
-  const bool valid = (key >> 8) < 0x7F800000ull && (key >> 8) < (unsigned long long)__float_as_uint(3.4028234663852886e38f);
-  const float f1 = __shfl((float)li1, bp, 64), f2 = __shfl((float)li2, bp, 64);
-  if (valid) {   // min_distance starts at FLT_MAX: a pairing at exactly FLT_MAX or beyond never wins
-    const int bi = bp / 3;
-    int bj = bp % 3;
-    bj += bj >= bi ? 1 : 0;
-    int bk = 0;
-    while (bk == bi || bk == bj) bk++;
-    int bl = 0;
-    while (bl == bi || bl == bj || bl == bk) bl++;
-    const int t0 = ids[0], t1 = ids[1], t2 = ids[2], t3 = ids[3];
-    auto sel = [&](int t) { return t == 0 ? t0 : (t == 1 ? t1 : (t == 2 ? t2 : t3)); };
-    ids[0] = sel(bi);
-    ids[1] = sel(bj);
-    ids[2] = sel(bk);
-    ids[3] = sel(bl);
-    *inv1 = f1;
-    *inv2 = f2;
-  }
 }
 
 // kSelLdsPoints: an attempt's stage weights live in LDS up to this many points (the sequential sums are one wave's 64-wide

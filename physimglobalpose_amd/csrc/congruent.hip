@@ -870,82 +870,45 @@ int cone_for_base(const float base[12], float* cone /*[56][3]*/) {
 
 }  // namespace
 
-// Phase 1 + 2 for all bases: leaves the sorted match keys and the per-base starts in the context.
-int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float* h_base_xyz, const float* h_inv,
-                                const int* h_rows, int nb, float threshold, int* h_n_quads, hipStream_t st) {
-  ctx->csb_fit_m = 0;
-  ctx->csb_nb = 0;
-  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
-    set_error("no search model: call pgp_set_search_model first");
-    return PGP_ESTATE;
+namespace {
+
+// PGP_CS_TIMING=1: host time of a batch call's stages on stderr (each stage then ends with a stream synchronisation)
+struct StageClock {
+  hipStream_t st;
+  bool on;
+  std::chrono::steady_clock::time_point last;
+  explicit StageClock(hipStream_t s) : st(s), last(std::chrono::steady_clock::now()) {
+    static const bool timing = getenv("PGP_CS_TIMING") && atoi(getenv("PGP_CS_TIMING")) != 0;
+    on = timing;
   }
-  if (!ctx->ppf_ready || ctx->ppf_n_pairs <= 0) {
-    set_error("no pair-feature table with pair lists: call pgp_set_ppf_map(keys, counts, pairs) first");
-    return PGP_ESTATE;
-  }
-  if (nb > 65535) {
-    set_error("pgp_find_congruent_batch: at most 65535 bases per call");
-    return PGP_EINVAL;
-  }
-  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
-  if (nb == 0) return PGP_OK;
-  // PGP_CS_TIMING=1: host time of the call's stages on stderr (each stage then ends with a stream synchronisation)
-  static const bool timing = getenv("PGP_CS_TIMING") && atoi(getenv("PGP_CS_TIMING")) != 0;
-  auto t_last = std::chrono::steady_clock::now();
-  auto stage = [&](const char* what) {
-    if (!timing) return;
+  void operator()(const char* what) {
+    if (!on) return;
     (void)hipStreamSynchronize(st);
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[congruent batch] %-28s %7.1f us\n", what, std::chrono::duration<double, std::micro>(now - t_last).count());
-    t_last = now;
-  };
-  // ---- which rows of the table are pairs1 / pairs6 of every base: computePPF on the device
-  std::vector<int> edge_pairs((size_t)nb * 4), rows((size_t)nb * 2);
-  for (int b = 0; b < nb; ++b) {
-    edge_pairs[4 * b] = h_base_ids[4 * b];       // computePPF(base_id1, base_id2)
-    edge_pairs[4 * b + 1] = h_base_ids[4 * b + 1];
-    edge_pairs[4 * b + 2] = h_base_ids[4 * b + 2];   // computePPF(base_id3, base_id4)
-    edge_pairs[4 * b + 3] = h_base_ids[4 * b + 3];
+    fprintf(stderr, "[congruent batch] %-28s %7.1f us\n", what, std::chrono::duration<double, std::micro>(now - last).count());
+    last = now;
   }
+};
+
+// The join for nb bases whose pair lists are the ranges (p_off, p_cnt) / (q_off, q_cnt) of d_pairs, filled in by a front
+// below (both counts 0: no quads for that base): leaves the sorted match keys and the per-base starts in the context.
+// from_lists: d_pairs is the context's d_s4_pairs (pgp_extract_pairs_batch), else the pair-feature table's d_ppf_pairs.
+int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std::vector<BatchBase>& hb, const float* h_base_xyz,
+                         const float* h_inv, int nb, float threshold, int* h_n_quads, hipStream_t st, StageClock& stage) {
+  const bool timing = stage.on;
   int rc = PGP_OK;
-  if (h_rows) {   // the caller holds them already (pgp_select_bases_rows): one launch and one round trip less
-    const int n_rows = (int)ctx->ppf_off_host.size() - 1;
-    for (int k = 0; k < 2 * nb; ++k) {
-      if (h_rows[k] < -1 || h_rows[k] >= n_rows) {
-        set_error("pgp_find_congruent_batch_rows: row %d of base %d is not a row of the table (%d rows)", h_rows[k], k / 2, n_rows);
-        return PGP_EINVAL;
-      }
-      rows[(size_t)k] = h_rows[k];
-    }
-  } else {
-    rc = launch_ppf_features(ctx, edge_pairs.data(), 2 * nb, nullptr, rows.data(), st);
-    if (rc != PGP_OK) return rc;
-  }
-  stage("pair features of the bases");
   const float eps = threshold / ctx->cs_ratio;          // getNormalizedEpsilon
   const int gridDepth = (int)(-std::log2(eps));          // normalset.h:116
   if (!(eps > 0.f) || gridDepth < 0 || gridDepth > 20) {
     set_error("find_congruent: threshold %g gives an unusable grid depth %d", (double)threshold, gridDepth);
     return PGP_EINVAL;
   }
-  std::vector<BatchBase> hb((size_t)nb);
   std::vector<float> cones((size_t)nb * 168, 0.f);
   uint64_t tp = 0, tq = 0;
   for (int b = 0; b < nb; ++b) {
     BatchBase& B = hb[b];
     B.inv1 = h_inv[2 * b];
     B.inv2 = h_inv[2 * b + 1];
-    const int r1 = rows[2 * b], r6 = rows[2 * b + 1];
-    B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
-    if (r1 >= 0 && r6 >= 0) {   // pairs1.size() == 0 || pairs6.size() == 0 -> no quads for this base
-      const uint32_t c1 = ctx->ppf_off_host[r1 + 1] - ctx->ppf_off_host[r1], c6 = ctx->ppf_off_host[r6 + 1] - ctx->ppf_off_host[r6];
-      if (c1 > 0 && c6 > 0) {
-        B.p_off = ctx->ppf_off_host[r1];
-        B.p_cnt = c1;
-        B.q_off = ctx->ppf_off_host[r6];
-        B.q_cnt = c6;
-      }
-    }
     if (B.p_cnt >= (1u << 24) || B.q_cnt >= (1u << 24)) {
       set_error("pgp_find_congruent_batch: a pair list exceeds 2^24 entries");
       return PGP_EINVAL;
@@ -1004,7 +967,7 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
   a.Qw = ctx->d_Qs.as<float4>();
   a.Qu = ctx->d_Qs_unit.as<float4>();
   a.nQs = ctx->nQs;
-  a.pairs = ctx->d_ppf_pairs.as<int2>();
+  a.pairs = d_pairs;
   a.bases = d_bases;
   a.nb = nb;
   a.cones = d_cones;
@@ -1064,6 +1027,7 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
   if (total == 0) {   // a valid, empty batch: every pick is out of range
     ctx->csb_starts = starts;
     ctx->csb_nb = nb;
+    ctx->csb_lists = from_lists;
     ctx->csb_total = 0;
     return PGP_OK;
   }
@@ -1083,8 +1047,113 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
   // only now do the sorted keys exist: the batch becomes visible to pgp_congruent_batch_quads / _fit
   ctx->csb_starts = starts;
   ctx->csb_nb = nb;
+  ctx->csb_lists = from_lists;
   ctx->csb_total = total;
   return PGP_OK;
+}
+
+}  // namespace
+
+// Phase 1 + 2 for all bases whose pair lists are rows of the pair-feature table (mode 1): the front that turns those rows into
+// ranges of d_ppf_pairs, then the body above.
+int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float* h_base_xyz, const float* h_inv,
+                                const int* h_rows, int nb, float threshold, int* h_n_quads, hipStream_t st) {
+  ctx->csb_fit_m = 0;
+  ctx->csb_nb = 0;
+  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
+    set_error("no search model: call pgp_set_search_model first");
+    return PGP_ESTATE;
+  }
+  if (!ctx->ppf_ready || ctx->ppf_n_pairs <= 0) {
+    set_error("no pair-feature table with pair lists: call pgp_set_ppf_map(keys, counts, pairs) first");
+    return PGP_ESTATE;
+  }
+  if (nb > 65535) {
+    set_error("pgp_find_congruent_batch: at most 65535 bases per call");
+    return PGP_EINVAL;
+  }
+  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
+  if (nb == 0) return PGP_OK;
+  StageClock stage(st);
+  // ---- which rows of the table are pairs1 / pairs6 of every base: computePPF on the device
+  std::vector<int> edge_pairs((size_t)nb * 4), rows((size_t)nb * 2);
+  for (int b = 0; b < nb; ++b) {
+    edge_pairs[4 * b] = h_base_ids[4 * b];       // computePPF(base_id1, base_id2)
+    edge_pairs[4 * b + 1] = h_base_ids[4 * b + 1];
+    edge_pairs[4 * b + 2] = h_base_ids[4 * b + 2];   // computePPF(base_id3, base_id4)
+    edge_pairs[4 * b + 3] = h_base_ids[4 * b + 3];
+  }
+  int rc = PGP_OK;
+  if (h_rows) {   // the caller holds them already (pgp_select_bases_rows): one launch and one round trip less
+    const int n_rows = (int)ctx->ppf_off_host.size() - 1;
+    for (int k = 0; k < 2 * nb; ++k) {
+      if (h_rows[k] < -1 || h_rows[k] >= n_rows) {
+        set_error("pgp_find_congruent_batch_rows: row %d of base %d is not a row of the table (%d rows)", h_rows[k], k / 2, n_rows);
+        return PGP_EINVAL;
+      }
+      rows[(size_t)k] = h_rows[k];
+    }
+  } else {
+    rc = launch_ppf_features(ctx, edge_pairs.data(), 2 * nb, nullptr, rows.data(), st);
+    if (rc != PGP_OK) return rc;
+  }
+  stage("pair features of the bases");
+  std::vector<BatchBase> hb((size_t)nb);
+  for (int b = 0; b < nb; ++b) {
+    BatchBase& B = hb[b];
+    const int r1 = rows[2 * b], r6 = rows[2 * b + 1];
+    B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
+    if (r1 >= 0 && r6 >= 0) {   // pairs1.size() == 0 || pairs6.size() == 0 -> no quads for this base
+      const uint32_t c1 = ctx->ppf_off_host[r1 + 1] - ctx->ppf_off_host[r1], c6 = ctx->ppf_off_host[r6 + 1] - ctx->ppf_off_host[r6];
+      if (c1 > 0 && c6 > 0) {
+        B.p_off = ctx->ppf_off_host[r1];
+        B.p_cnt = c1;
+        B.q_off = ctx->ppf_off_host[r6];
+        B.q_cnt = c6;
+      }
+    }
+  }
+  return congruent_batch_body(ctx, ctx->d_ppf_pairs.as<int2>(), false, hb, h_base_xyz, h_inv, nb, threshold, h_n_quads, st, stage);
+}
+
+// The same for bases whose pair lists are lists of the last pgp_extract_pairs_batch (mode 0): h_lists[nb][2] = (pairs1, pairs6).
+int launch_find_congruent_batch_lists(pgp_ctx* ctx, const float* h_base_xyz, const float* h_inv, const int* h_lists, int nb,
+                                      float threshold, int* h_n_quads, hipStream_t st) {
+  ctx->csb_fit_m = 0;
+  ctx->csb_nb = 0;
+  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
+    set_error("no search model: call pgp_set_search_model first");
+    return PGP_ESTATE;
+  }
+  if (ctx->s4_nl <= 0 || (int)ctx->s4_off.size() != ctx->s4_nl + 1) {
+    set_error("no pair lists: call pgp_extract_pairs_batch first (pgp_set_search_model discards them)");
+    return PGP_ESTATE;
+  }
+  if (nb > 65535) {
+    set_error("pgp_find_congruent_batch_lists: at most 65535 bases per call");
+    return PGP_EINVAL;
+  }
+  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
+  if (nb == 0) return PGP_OK;
+  StageClock stage(st);
+  std::vector<BatchBase> hb((size_t)nb);
+  for (int b = 0; b < nb; ++b) {
+    BatchBase& B = hb[b];
+    const int l1 = h_lists[2 * b], l6 = h_lists[2 * b + 1];
+    if (l1 < 0 || l1 >= ctx->s4_nl || l6 < 0 || l6 >= ctx->s4_nl) {
+      set_error("pgp_find_congruent_batch_lists: base %d names lists %d and %d of %d", b, l1, l6, ctx->s4_nl);
+      return PGP_EINVAL;
+    }
+    B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
+    const uint32_t c1 = ctx->s4_off[l1 + 1] - ctx->s4_off[l1], c6 = ctx->s4_off[l6 + 1] - ctx->s4_off[l6];
+    if (c1 > 0 && c6 > 0) {   // pairs1.size() == 0 || pairs6.size() == 0 -> no quads for this base (base.cc:1984)
+      B.p_off = ctx->s4_off[l1];
+      B.p_cnt = c1;
+      B.q_off = ctx->s4_off[l6];
+      B.q_cnt = c6;
+    }
+  }
+  return congruent_batch_body(ctx, ctx->d_s4_pairs.as<int2>(), true, hb, h_base_xyz, h_inv, nb, threshold, h_n_quads, st, stage);
 }
 
 // picks[m][2] = (base, j) -> d_quads[m] (int4), on the sorted keys left by the call above
@@ -1126,7 +1195,7 @@ int launch_congruent_batch_gather(pgp_ctx* ctx, const int* h_picks, int m, int4*
   const uint32_t* d_base_start = reinterpret_cast<const uint32_t*>(sb + bb + cb);
   const unsigned long long* keys_out = ctx->d_cs_keys.as<unsigned long long>() + ctx->csb_keys_off;
   hipLaunchKernelGGL(batch_gather, dim3((m + 255) / 256), dim3(256), 0, st, keys_out, d_base_start, d_bases,
-                     (const int2*)ctx->d_ppf_pairs.as<int2>(), d_picks, m, d_quads);
+                     (const int2*)(ctx->csb_lists ? ctx->d_s4_pairs : ctx->d_ppf_pairs).as<int2>(), d_picks, m, d_quads);
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }

@@ -216,7 +216,8 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
                     &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
-                    &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io};
+                    &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
+                    &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   if (ctx->h_pin) {
@@ -1086,6 +1087,8 @@ int pgp_set_search_model(pgp_ctx* ctx, const float* xyz, int n) {
   ctx->csb_fit_m = 0;
   ctx->csb_nb = 0;   // a resident congruent batch belongs to the old search model
   ctx->v4_nb = 0;    // and so does a resident V4PCS batch
+  ctx->s4_nl = 0;    // and the pair lists of pgp_extract_pairs_batch
+  ctx->s4_off.clear();
   std::vector<float4> hq((size_t)std::max(n, 1));
   for (int i = 0; i < n; ++i)
     hq[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2],
@@ -3604,6 +3607,178 @@ int pgp_v4pcs_hypotheses(pgp_ctx* ctx, const pgp_v4pcs_options* opt, const float
   for (size_t k = 0; k < N; ++k) std::memcpy(&hb[4 * k], &b_ids[4 * (size_t)pk[2 * k]], 16);
   PGP_HIP(hipMemcpyAsync(c.at(p_base), hb.data(), N * 16, hipMemcpyHostToDevice, st));
   if ((rc = launch_v4pcs_gather(ctx, pk.data(), m, c.at(p_quad), st)) != PGP_OK) return rc;
+  if ((rc = launch_rigid(ctx, reinterpret_cast<const int*>(c.at(p_base)), reinterpret_cast<const int*>(c.at(p_quad)), m, centroid_P,
+                         centroid_Q, c.at(p_T), c.at(p_pose), c.at(p_status), c.at(p_rms), st)) != PGP_OK)
+    return rc;
+  // (the caller's transforms are the fits as pgp_rigid_from_congruent returns them; the scored copy has the failed ones masked)
+  PGP_HIP(hipMemcpyAsync(T, c.at(p_T), N * 64, hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(mask_failed_fits, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const int*)c.at(p_status), m, c.at(p_T));
+  if ((rc = launch_score(ctx, c.at(p_T), m, PGP_MODE_PLAIN, 0.f, c.at(p_scores), nullptr, nullptr, st)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(scores, c.at(p_scores), N * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(status, c.at(p_status), N * 4, hipMemcpyDeviceToHost, st));
+  std::vector<double> h_pose;
+  double* pose_dst = pose;
+  if (!pose_dst && best_pose) {
+    h_pose.resize(16 * N);
+    pose_dst = h_pose.data();
+  }
+  if (pose_dst) PGP_HIP(hipMemcpyAsync(pose_dst, c.at(p_pose), N * 128, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  if (int rc2 = index_settled(ctx)) return rc2;
+  if (picks) std::memcpy(picks, pk.data(), N * 8);
+  // the lowest index of the maximum; no hypothesis above 0: none
+  int bi = -1;
+  float bs = 0.f;
+  for (int k = 0; k < m; ++k)
+    if (scores[k] > bs) {
+      bs = scores[k];
+      bi = k;
+    }
+  *n_hyp = m;
+  if (best_index) *best_index = bi;
+  if (best_score) *best_score = bs;
+  if (bi >= 0 && best_T) std::memcpy(best_T, T + 16 * (size_t)bi, 64);
+  if (bi >= 0 && best_pose) std::memcpy(best_pose, pose_dst + 16 * (size_t)bi, 128);
+  return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- classic mode, "Super4PCS" (super4pcs.hip) ------------------------------------------------------------------------
+extern "C" {
+
+int pgp_select_wide_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, float max_base_diameter,
+                          int* ids, float* invariants, float* dist, int* status) {
+  if (!ctx || n_attempts < 0 || n_attempts > kV4MaxAttempts || triangle_trials < 0 || triangle_trials > kV4MaxTrials ||
+      !(max_base_diameter > 0.f) || !std::isfinite(max_base_diameter) ||
+      (n_attempts > 0 && (!ids || !invariants || !dist || !status))) {
+    set_error("pgp_select_wide_bases: bad argument (attempts %d, trials %d, diameter %g)", n_attempts, triangle_trials,
+              (double)max_base_diameter);
+    return PGP_EINVAL;
+  }
+  if (n_attempts == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  return launch_wide_bases(ctx, seed, n_attempts, triangle_trials, max_base_diameter, ids, invariants, dist, status, nullptr,
+                           ctx->stream);
+}
+
+int pgp_extract_pairs_batch(pgp_ctx* ctx, const float* dist, int n_lists, float eps, int* n_pairs) {
+  if (!ctx || n_lists < 0 || n_lists > 2 * 65535 || (n_lists > 0 && !dist) || !(eps >= 0.f) || !std::isfinite(eps)) {
+    set_error("pgp_extract_pairs_batch: bad argument (%d lists)", n_lists);
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  return launch_extract_pairs_batch(ctx, dist, n_lists, eps, n_pairs, ctx->stream);
+}
+
+int pgp_extract_pairs_batch_fetch(pgp_ctx* ctx, int list, int* pairs, int cap, int* n_pairs) {
+  if (!ctx || !n_pairs || cap < 0 || (cap > 0 && !pairs)) {
+    set_error("pgp_extract_pairs_batch_fetch: bad argument");
+    return PGP_EINVAL;
+  }
+  *n_pairs = 0;
+  CtxGuard guard(ctx);
+  return extract_pairs_batch_fetch(ctx, list, pairs, cap, n_pairs, ctx->stream);
+}
+
+int pgp_find_congruent_batch_lists(pgp_ctx* ctx, const float* base_xyz, const float* invariants, const int* lists, int n_bases,
+                                   float threshold, int* n_quads) {
+  if (!ctx || n_bases < 0 || (n_bases > 0 && (!base_xyz || !invariants || !lists || !n_quads))) {
+    set_error("pgp_find_congruent_batch_lists: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  return launch_find_congruent_batch_lists(ctx, base_xyz, invariants, lists, n_bases, threshold, n_quads, ctx->stream);
+}
+
+int pgp_super4pcs_default_options(pgp_super4pcs_options* opt) {
+  if (!opt) {
+    set_error("pgp_super4pcs_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->seed = 0;
+  opt->n_bases = 100;           // base.cc:1837-1842
+  opt->max_attempts = 200;
+  opt->triangle_trials = 1000;  // kNumberOfDiameterTrials
+  opt->max_base_diameter = 0.f; // the caller's: the model's diameter or an estimate of it
+  opt->eps = 0.005f;            // distance_factor * delta
+  opt->max_per_base = 100;      // base.cc:1858-1874
+  return PGP_OK;
+}
+
+int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const float centroid_P[3], const float centroid_Q[3],
+                             int* n_bases, int* base_ids, float* base_invariants, int* n_hyp, float* T, double* pose, int* status,
+                             float* scores, int* picks, int* best_index, float* best_score, float* best_T, double* best_pose) {
+  if (!ctx || !opt || !centroid_P || !centroid_Q || !n_hyp || !T || !status || !scores) {
+    set_error("pgp_super4pcs_hypotheses: bad argument");
+    return PGP_EINVAL;
+  }
+  if (opt->n_bases < 1 || opt->n_bases > 65535 || opt->max_attempts < 1 || opt->max_attempts > kV4MaxAttempts ||
+      opt->triangle_trials < 0 || opt->triangle_trials > kV4MaxTrials || !(opt->max_base_diameter > 0.f) ||
+      !std::isfinite(opt->max_base_diameter) || !(opt->eps >= 0.f) || !std::isfinite(opt->eps) || opt->max_per_base < 1 ||
+      opt->max_per_base > kSampleMax) {
+    set_error("pgp_super4pcs_hypotheses: bad options (n_bases %d, max_attempts %d, trials %d, diameter %g, eps %g, max_per_base %d of "
+              "at most %d)", opt->n_bases, opt->max_attempts, opt->triangle_trials, (double)opt->max_base_diameter, (double)opt->eps,
+              opt->max_per_base, kSampleMax);
+    return PGP_EINVAL;
+  }
+  *n_hyp = 0;
+  if (n_bases) *n_bases = 0;
+  if (best_index) *best_index = -1;
+  if (best_score) *best_score = 0.f;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  // 1. attempts, the first n_bases successes kept in attempt order
+  const size_t A = (size_t)opt->max_attempts;
+  std::vector<int> a_ids(4 * A), a_status(A);
+  std::vector<float> a_inv(2 * A), a_dist(2 * A), a_xyz(12 * A);
+  int rc = launch_wide_bases(ctx, opt->seed, opt->max_attempts, opt->triangle_trials, opt->max_base_diameter, a_ids.data(), a_inv.data(),
+                             a_dist.data(), a_status.data(), a_xyz.data(), st);
+  if (rc != PGP_OK) return rc;
+  std::vector<int> b_ids, b_lists;
+  std::vector<float> b_inv, b_dist, b_xyz;
+  int nb = 0;
+  for (size_t a = 0; a < A && nb < opt->n_bases; ++a)
+    if (a_status[a] == 1) {
+      b_ids.insert(b_ids.end(), a_ids.begin() + 4 * a, a_ids.begin() + 4 * a + 4);
+      b_inv.insert(b_inv.end(), a_inv.begin() + 2 * a, a_inv.begin() + 2 * a + 2);
+      b_dist.insert(b_dist.end(), a_dist.begin() + 2 * a, a_dist.begin() + 2 * a + 2);
+      b_xyz.insert(b_xyz.end(), a_xyz.begin() + 12 * a, a_xyz.begin() + 12 * a + 12);
+      b_lists.push_back(2 * nb);       // pairs1: the list of |b0 b1|
+      b_lists.push_back(2 * nb + 1);   // pairs6: the list of |b2 b3|
+      ++nb;
+    }
+  if (n_bases) *n_bases = nb;
+  if (base_ids && nb > 0) std::memcpy(base_ids, b_ids.data(), (size_t)nb * 16);
+  if (base_invariants && nb > 0) std::memcpy(base_invariants, b_inv.data(), (size_t)nb * 8);
+  if (nb == 0) return PGP_OK;
+  // 2. the pair lists of the bases' 2 nb distances, resident
+  if ((rc = launch_extract_pairs_batch(ctx, b_dist.data(), 2 * nb, opt->eps, nullptr, st)) != PGP_OK) return rc;
+  // 3. the join, fed from those lists
+  std::vector<int> nq((size_t)nb);
+  if ((rc = launch_find_congruent_batch_lists(ctx, b_xyz.data(), b_inv.data(), b_lists.data(), nb, opt->eps, nq.data(), st)) != PGP_OK)
+    return rc;
+  // 4. at most max_per_base of every base's quads
+  std::vector<int> pk((size_t)nb * (size_t)opt->max_per_base * 2);
+  int m = 0;
+  if ((rc = pgp_sample_quads(opt->seed, nq.data(), nb, opt->max_per_base, pk.data(), &m)) != PGP_OK) return rc;
+  if (m == 0) return PGP_OK;
+  // 5. + 6. fit and plain score, on the device
+  if ((rc = reserve_impl(ctx, m)) != PGP_OK) return rc;
+  const size_t N = (size_t)m;
+  Carve c;
+  const auto p_pose = c.add<double>(16 * N, 16);
+  const auto p_base = c.add<int4>(N, 16);
+  const auto p_quad = c.add<int4>(N, 16);
+  const auto p_T = c.add<float>(16 * N, 16);
+  const auto p_rms = c.add<float>(N, 16);
+  const auto p_status = c.add<int>(N, 16);
+  const auto p_scores = c.add<float>(N, 16);
+  if ((rc = c.ensure(ctx->d_s4_io)) != PGP_OK) return rc;
+  std::vector<int> hb(4 * N);
+  for (size_t k = 0; k < N; ++k) std::memcpy(&hb[4 * k], &b_ids[4 * (size_t)pk[2 * k]], 16);
+  PGP_HIP(hipMemcpyAsync(c.at(p_base), hb.data(), N * 16, hipMemcpyHostToDevice, st));
+  if ((rc = launch_congruent_batch_gather(ctx, pk.data(), m, c.at(p_quad), st)) != PGP_OK) return rc;
   if ((rc = launch_rigid(ctx, reinterpret_cast<const int*>(c.at(p_base)), reinterpret_cast<const int*>(c.at(p_quad)), m, centroid_P,
                          centroid_Q, c.at(p_T), c.at(p_pose), c.at(p_status), c.at(p_rms), st)) != PGP_OK)
     return rc;

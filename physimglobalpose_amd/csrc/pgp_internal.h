@@ -207,6 +207,14 @@ struct pgp_ctx {
   int v4_nb = 0;                        // bases of the last pgp_find_congruent_v4pcs_batch; 0 once the search model is rewritten
   int v4_cap = 0;                       // its per_base_cap
   std::vector<int> v4_stored;           // quads kept per base (v4_nb), host copy: picks are checked here
+  // classic mode (super4pcs.hip): the pair lists of the last pgp_extract_pairs_batch stay on the device, in a buffer of their
+  // own (d_ppf_pairs belongs to the pair-feature table), with their offsets on the host
+  pgp::DevBuf d_s4_sel;                 // base selection: ids | invariants | distances | status
+  pgp::DevBuf d_s4_ws;                  // distances | list totals | list offsets | row counts | row starts
+  pgp::DevBuf d_s4_pairs;               // int2 pairs of all lists, list k at [s4_off[k], s4_off[k + 1])
+  pgp::DevBuf d_s4_io;                  // the chain's ids and results
+  int s4_nl = 0;                        // lists of the last batch; 0 once the search model is rewritten
+  std::vector<uint32_t> s4_off;         // s4_nl + 1 offsets into d_s4_pairs, in pairs
   pgp::DevBuf d_ids;     // staged int4 base / quad ids (host API)
   pgp::DevBuf d_rig;     // staged rigid-fit outputs (host API)
 
@@ -221,6 +229,8 @@ struct pgp_ctx {
   pgp::DevBuf d_csb, d_csb_picks;       // batched congruent sets: bases | cones | per-base starts; staged picks
   int csb_nb = 0;                       // bases of the last pgp_find_congruent_batch (its keys are still resident);
                                         // 0 as soon as d_cs_keys / d_ppf_pairs / the search model are rewritten
+  bool csb_lists = false;               // the resident batch's pair ranges index d_s4_pairs (pgp_find_congruent_batch_lists), not
+                                        // d_ppf_pairs: a new pgp_extract_pairs_batch then discards it as a new table does otherwise
   int csb_fit_m = 0;                    // fits of the last pgp_congruent_batch_fit_score, resident in d_rig
   uint32_t csb_total = 0;
   uint32_t csb_keys_off = 0;            // the sorted keys start this many keys into d_cs_keys (the capacity of the unsorted ones)
@@ -495,6 +505,8 @@ int launch_find_congruent_4pcs(pgp_ctx* ctx, float inv1, float inv2, float thres
                                const int* d_Qp, int nQ, int* d_quads, int cap, int* n_quads_host, hipStream_t st);
 int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float* h_base_xyz, const float* h_inv,
                                 const int* h_rows /* nullable */, int nb, float threshold, int* h_n_quads, hipStream_t st);
+int launch_find_congruent_batch_lists(pgp_ctx* ctx, const float* h_base_xyz, const float* h_inv, const int* h_lists, int nb,
+                                      float threshold, int* h_n_quads, hipStream_t st);
 int launch_congruent_batch_gather(pgp_ctx* ctx, const int* h_picks, int m, int4* d_quads, hipStream_t st,
                                   const int2* d_picks_there = nullptr);
 const uint32_t* congruent_batch_starts_device(pgp_ctx* ctx);
@@ -507,6 +519,12 @@ int launch_v4pcs_join(pgp_ctx* ctx, const float* h_dist, int nb, float eps, long
 int launch_v4pcs_batch(pgp_ctx* ctx, const float* h_dist, int nb, float eps, int per_base_cap, long long* h_n_quads, int* h_n_stored,
                        hipStream_t st);
 int launch_v4pcs_gather(pgp_ctx* ctx, const int* h_picks, int m, int4* d_out, hipStream_t st);
+
+// super4pcs.hip
+int launch_wide_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, float max_base_diameter,
+                      int* h_ids, float* h_inv, float* h_dist, int* h_status, float* h_xyz /* nullable: [n][4][3] */, hipStream_t st);
+int launch_extract_pairs_batch(pgp_ctx* ctx, const float* h_dist, int nl, float eps, int* h_n_pairs, hipStream_t st);
+int extract_pairs_batch_fetch(pgp_ctx* ctx, int list, int* h_pairs, int cap, int* h_n_pairs, hipStream_t st);
 
 // lcp_score.hip
 int tiles_for(int nQ);

@@ -25,6 +25,7 @@
 // Plain launches, no waiting between workgroups.  Every result is an integer.
 
 #include "pgp_internal.h"
+#include "base_device.h"
 
 #include <algorithm>
 #include <vector>
@@ -33,36 +34,10 @@ namespace pgp {
 
 namespace {
 
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-// correctly rounded float sqrt (see rigid_fit.hip)
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
+using namespace v4dev;   // base_device.h: the float helpers and the triangle rule shared with super4pcs.hip
 
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 ld3(const float4* __restrict__ a, int i) {
-  float4 v = a[i];
-  return {v.x, v.y, v.z};
-}
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
-// base selection: (x x + y y) + z z
-__device__ __forceinline__ float dot(V3 a, V3 b) { return add(add(mul(a.x, b.x), mul(a.y, b.y)), mul(a.z, b.z)); }
 // the pair predicate's squared norm, as pair_rows has it: x x + (y y + z z)
 __device__ __forceinline__ float sqnorm_pair(V3 v) { return add(mul(v.x, v.x), add(mul(v.y, v.y), mul(v.z, v.z))); }
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o, 64);
-    k = other > k ? other : k;
-  }
-  return k;
-}
 
 // ---------------- SelectTetrahedronBase: a wave per attempt ----------------
 __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, int n, unsigned long long seed, int T, int F,
@@ -74,24 +49,14 @@ __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, 
   const int i0 = (int)(sample_variate(st, 0) % un);
   const V3 p0 = ld3(P, i0);
   const float DD = mul(D, D);
-  // the widest triangle: key = how_wide bits << 32 | ~trial (how_wide > 0: its bits order as the floats do)
-  unsigned long long best = 0ull;
-  for (int i = lane; i < T; i += 64) {
-    const int s = (int)(sample_variate(st, 1 + 2 * i) % un), t = (int)(sample_variate(st, 2 + 2 * i) % un);
-    const V3 u = vsub(ld3(P, s), p0), w = vsub(ld3(P, t), p0);
-    const V3 c = cross(u, w);
-    const float how_wide = sqrt_rn(dot(c, c));
-    if (how_wide > 0.f && dot(u, u) < DD && dot(w, w) < DD) {
-      const unsigned long long key = ((unsigned long long)__float_as_uint(how_wide) << 32) | (0xFFFFFFFFu - (unsigned)i);
-      best = key > best ? key : best;
-    }
-  }
+  // the widest triangle (base_device.h): trials strided over the lanes
+  unsigned long long best = widest_triangle(P, un, st, T, DD, p0, lane, 64);
   best = wave_max(best);
   int4 out = make_int4(-1, -1, -1, -1);
   int ok = 0;
   float d[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (best != 0ull) {
-    const int i = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+    const int i = triangle_trial(best);
     const int i1 = (int)(sample_variate(st, 1 + 2 * i) % un), i2 = (int)(sample_variate(st, 2 + 2 * i) % un);
     const V3 p1 = ld3(P, i1), p2 = ld3(P, i2);
     const V3 n12 = cross(vsub(p1, p0), vsub(p2, p0));

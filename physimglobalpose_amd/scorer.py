@@ -449,6 +449,87 @@ class LcpScorer:
                     scores=scores[:k].copy(), picks=picks[:k].copy(), best_index=best.value, best_score=float(np.float32(bs.value)),
                     best_T=bT, best_pose=bp)
 
+    # ---- classic mode, "Super4PCS" (base.cc:505-580, 1963-1969): positions alone, two pair lists per base ----
+    def select_wide_bases(self, seed, n_attempts, max_base_diameter, triangle_trials=1000):
+        """pgp_select_wide_bases on the scene: (ids (n,4) int32, invariants (n,2) f32, dist (n,2) f32 = |b0 b1|, |b2 b3|,
+        status (n,) int32)."""
+        n = int(n_attempts)
+        ids = np.zeros((max(n, 1), 4), np.int32)
+        inv = np.zeros((max(n, 1), 2), np.float32)
+        dist = np.zeros((max(n, 1), 2), np.float32)
+        status = np.zeros(max(n, 1), np.int32)
+        _lib.check(self._lib.pgp_select_wide_bases(self._h, C.c_ulonglong(int(seed)), n, int(triangle_trials),
+                                                   C.c_float(max_base_diameter), ids.ctypes.data_as(_i), _fp(inv), _fp(dist),
+                                                   status.ctypes.data_as(_i)))
+        return ids[:n], inv[:n], dist[:n], status[:n]
+
+    def extract_pairs_batch(self, dist, eps):
+        """pgp_extract_pairs_batch: one resident pair list per distance; returns the pairs per list (n_lists,) int32."""
+        d = _f32(dist).reshape(-1)
+        n = np.zeros(max(len(d), 1), np.int32)
+        _lib.check(self._lib.pgp_extract_pairs_batch(self._h, _fp(d), len(d), C.c_float(eps), n.ctypes.data_as(_i)))
+        return n[: len(d)]
+
+    def extract_pairs_batch_fetch(self, k, cap=None):
+        """List k of the resident batch: ((min(count, cap), 2) int32, the full count)."""
+        n = C.c_int(0)
+        if cap is None:
+            _lib.check(self._lib.pgp_extract_pairs_batch_fetch(self._h, int(k), None, 0, C.byref(n)))
+            cap = n.value
+        out = np.zeros((max(int(cap), 1), 2), np.int32)
+        _lib.check(self._lib.pgp_extract_pairs_batch_fetch(self._h, int(k), out.ctypes.data_as(_i), int(cap), C.byref(n)))
+        return out[: min(n.value, int(cap))].copy(), n.value
+
+    def find_congruent_batch_lists(self, base_xyz, invariants, lists, threshold):
+        """pgp_find_congruent_batch_lists: the resident join fed from the lists of extract_pairs_batch (lists (nb,2) =
+        (pairs1, pairs6) list numbers); returns the quad counts (nb,)."""
+        x = _f32(base_xyz).reshape(-1, 12)
+        v = _f32(invariants).reshape(-1, 2)
+        ls = np.ascontiguousarray(lists, np.int32).reshape(-1, 2)
+        assert len(x) == len(v) == len(ls)
+        n = np.zeros(max(len(x), 1), np.int32)
+        _lib.check(self._lib.pgp_find_congruent_batch_lists(self._h, _fp(x), _fp(v), ls.ctypes.data_as(_i), len(x),
+                                                            C.c_float(threshold), n.ctypes.data_as(_i)))
+        return n[: len(x)]
+
+    @staticmethod
+    def super4pcs_options(max_base_diameter, **kw):
+        o = _lib.Super4pcsOptions()
+        _lib.check(_lib.load().pgp_super4pcs_default_options(C.byref(o)))
+        o.max_base_diameter = float(max_base_diameter)
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError(f"pgp_super4pcs_options has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def super4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), **opt):
+        """pgp_super4pcs_hypotheses: wide bases, pair lists, join, sampling, fits and plain scores in one call.  Returns the
+        dict of v4pcs_hypotheses (base_ids, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose) plus
+        base_invariants."""
+        o = self.super4pcs_options(max_base_diameter, **opt)
+        cP, cQ = _f32(centroid_P).reshape(3), _f32(centroid_Q).reshape(3)
+        cap = max(int(o.n_bases) * int(o.max_per_base), 1)
+        bids = np.zeros((max(int(o.n_bases), 1), 4), np.int32)
+        binv = np.zeros((max(int(o.n_bases), 1), 2), np.float32)
+        T = np.zeros((cap, 16), np.float32)
+        pose = np.zeros((cap, 16), np.float64)
+        status = np.zeros(cap, np.int32)
+        scores = np.zeros(cap, np.float32)
+        picks = np.zeros((cap, 2), np.int32)
+        bT, bp = np.zeros(16, np.float32), np.zeros(16, np.float64)
+        nb, nh, best = C.c_int(0), C.c_int(0), C.c_int(-1)
+        bs = C.c_float(0)
+        dp = C.POINTER(C.c_double)
+        _lib.check(self._lib.pgp_super4pcs_hypotheses(
+            self._h, C.byref(o), _fp(cP), _fp(cQ), C.byref(nb), bids.ctypes.data_as(_i), _fp(binv), C.byref(nh), _fp(T),
+            pose.ctypes.data_as(dp), status.ctypes.data_as(_i), _fp(scores), picks.ctypes.data_as(_i), C.byref(best), C.byref(bs),
+            _fp(bT), bp.ctypes.data_as(dp)))
+        k = nh.value
+        return dict(base_ids=bids[: nb.value].copy(), base_invariants=binv[: nb.value].copy(), T=T[:k].copy(), pose=pose[:k].copy(),
+                    status=status[:k].copy(), scores=scores[:k].copy(), picks=picks[:k].copy(), best_index=best.value,
+                    best_score=float(np.float32(bs.value)), best_T=bT, best_pose=bp)
+
     # ---- segment pre-processing (ObjectPoseCandidateSet.cpp:28-51) -----------------------------------
     def radius_outlier_filter(self, xyz, nrm=None, radius=0.03, min_neighbors=10):
         """Returns (keep mask (n,) bool, flipped + re-normalised normals (n,3) or None)."""
