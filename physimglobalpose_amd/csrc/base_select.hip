@@ -638,14 +638,8 @@ int launch_select_bases(pgp_ctx* ctx, const double* h_u, int n_attempts, int* h_
     unsigned char* up = nullptr;
     if (phase == 1) {
       // (an image that outlives this call: the stage kernel may run after it has returned)
-      if (ctx->h_sel_cap < A * 32) {
-        if (ctx->h_sel_pin) (void)hipHostFree(ctx->h_sel_pin);
-        ctx->h_sel_pin = nullptr;
-        ctx->h_sel_cap = 0;
-        PGP_HIP(hipHostMalloc(&ctx->h_sel_pin, A * 32 + 4096, hipHostMallocDefault));
-        ctx->h_sel_cap = A * 32 + 4096;
-      }
-      up = static_cast<unsigned char*>(ctx->h_sel_pin);
+      if ((rc = ctx->h_sel_pin.ensure(A * 32)) != PGP_OK) return rc;
+      up = ctx->h_sel_pin.as<unsigned char>();
     } else {
       up = out.room(A * 32);
     }

@@ -154,8 +154,7 @@ struct pgp_multi {
   // {scores | counts} vector over the FLAT (object, hypothesis) space
   std::vector<DevBuf> d_T, d_all, d_best;
   std::vector<int> off{0, 0};   // uploaded hypotheses: object o owns flat positions off[o] .. off[o + 1] - 1
-  void* h_pin = nullptr;  // portable pinned staging: transforms in, scores | counts | best out
-  size_t h_pin_cap = 0;
+  PinBuf h_pin{hipHostMallocPortable};   // portable pinned staging: transforms in, scores | counts | best out
   float last_ms[3] = {0.f, 0.f, 0.f};  // host wall clock of the last call: upload, enqueue, total
   // ICP pose shards: per member one context per job slot (a context keeps ONE target index, icp.hip)
   std::vector<std::vector<pgp_ctx*>> ictx;
@@ -261,19 +260,6 @@ int run_all(pgp_multi* m, const std::function<int(int)>& fn) {
   return rc;
 }
 
-int ensure_pin(pgp_multi* m, size_t bytes) {
-  if (bytes <= m->h_pin_cap) return PGP_OK;
-  if (m->h_pin) {
-    (void)hipHostFree(m->h_pin);
-    m->h_pin = nullptr;
-    m->h_pin_cap = 0;
-  }
-  const size_t want = bytes + bytes / 4 + 256;
-  PGP_HIP(hipHostMalloc(&m->h_pin, want, hipHostMallocPortable));
-  m->h_pin_cap = want;
-  return PGP_OK;
-}
-
 bool bad_object(const pgp_multi* m, int obj, const char* who) {
   if (!m) {
     set_error("%s: handle is NULL", who);
@@ -332,9 +318,9 @@ int shm_exchange(pgp_multi* m, float* d_s, int N, hipStream_t st) {
 int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* counts, int* best_index, float* best_score) {
   const int N = m->total(), n_obj = (int)m->off.size() - 1;
   const double t0 = now_ms();
-  int rc = ensure_pin(m, (size_t)N * 72 + (size_t)n_obj * 8 + 256);   // nothing uploaded yet: an empty batch still returns {-1, 0}
+  int rc = m->h_pin.ensure((size_t)N * 72 + (size_t)n_obj * 8 + 256);   // nothing uploaded yet: an empty batch still returns {-1, 0}
   if (rc != PGP_OK) return rc;
-  unsigned char* pin_out = static_cast<unsigned char*>(m->h_pin) + (((size_t)N * 64 + 63) & ~(size_t)63);
+  unsigned char* pin_out = m->h_pin.as<unsigned char>() + (((size_t)N * 64 + 63) & ~(size_t)63);
   std::vector<int> fail((size_t)m->n, 0);   // emulate: a member that failed to queue its slice (the others still meet it)
   double t_enq = t0;
 
@@ -523,10 +509,10 @@ int upload_flat(pgp_multi* m, const float* const* T, const int* n_h, int n_obj) 
     PGP_HIP(hipEventSynchronize(m->ev_rest));
     m->rest_pending = false;
   }
-  int rc = ensure_pin(m, nT + (size_t)N * 8 + (size_t)n_obj * 8 + 256);
+  int rc = m->h_pin.ensure(nT + (size_t)N * 8 + (size_t)n_obj * 8 + 256);
   if (rc != PGP_OK) return rc;
   for (int o = 0; o < n_obj; ++o)
-    if (n_h[o]) std::memcpy(static_cast<unsigned char*>(m->h_pin) + (size_t)off[o] * 64, T[o], (size_t)n_h[o] * 64);
+    if (n_h[o]) std::memcpy(m->h_pin.as<unsigned char>() + (size_t)off[o] * 64, T[o], (size_t)n_h[o] * 64);
   m->off = off;
   rc = run_all(m, [m, nT, N, n_obj](int k) -> int {
     int lo, hi, r;
@@ -544,7 +530,7 @@ int upload_flat(pgp_multi* m, const float* const* T, const int* n_h, int n_obj) 
     // place it has in the flat list (64 B per hypothesis: 4 MB at 65 536 -- every device over its own PCIe link)
     const size_t a = (size_t)lo * 64, b = (size_t)hi * 64;
     unsigned char* dst = m->d_T[k].as<unsigned char>();
-    unsigned char* src = static_cast<unsigned char*>(m->h_pin);
+    unsigned char* src = m->h_pin.as<unsigned char>();
     // (out of the portable pinned image by a kernel on the member's stream: no copy-engine hand-over in front of the scoring)
     if (b > a && (r = stage_to_device(m->stream[k], dst + a, src + a, b - a)) != PGP_OK) return r;
     if (k == 0 && (a > 0 || b < nT)) {
@@ -899,7 +885,7 @@ int pgp_multi_destroy(pgp_multi* m) {
     (void)munmap(m->shm.h, m->shm.total);
     if (m->rank0 == 0) (void)shm_unlink(m->shm.name.c_str());
   }
-  if (m->h_pin) (void)hipHostFree(m->h_pin);
+  m->h_pin.release();
   // the RCCL handle stays loaded for the life of the process (its own teardown runs at exit)
   delete m;
   return PGP_OK;
@@ -1130,9 +1116,9 @@ int pgp_multi_upload_slot(pgp_multi* m, int slot, const float* T, int n_h) {
   }
   const int N = n_h;
   const size_t nT = (size_t)N * 64;
-  int rc = ensure_pin(m, nT + (size_t)N * 8 + 256);
+  int rc = m->h_pin.ensure(nT + (size_t)N * 8 + 256);
   if (rc != PGP_OK) return rc;
-  if (nT) std::memcpy(m->h_pin, T, nT);
+  if (nT) std::memcpy(m->h_pin.p, T, nT);
   rc = run_all(m, [m, slot, N, nT](int k) -> int {
     int lo, hi, r;
     slice_of(N, m->rank0 + k, m->world, &lo, &hi);
@@ -1148,7 +1134,7 @@ int pgp_multi_upload_slot(pgp_multi* m, int slot, const float* T, int n_h) {
     if ((r = pgp_reserve(m->octx[0][(size_t)k], k == 0 ? N : hi - lo)) != PGP_OK) return r;
     const size_t a = k == 0 ? 0 : (size_t)lo * 64, b = k == 0 ? nT : (size_t)hi * 64;
     if (b > a)
-      PGP_HIP(hipMemcpyAsync(dT.as<unsigned char>() + a, static_cast<unsigned char*>(m->h_pin) + a, b - a,
+      PGP_HIP(hipMemcpyAsync(dT.as<unsigned char>() + a, m->h_pin.as<unsigned char>() + a, b - a,
                              hipMemcpyHostToDevice, m->stream[k]));
     PGP_HIP(hipStreamSynchronize(m->stream[k]));   // the pinned image is free again when this call returns
     return PGP_OK;
@@ -1274,7 +1260,7 @@ int pgp_multi_collect(pgp_multi* m, float* scores, int* counts, int* best_index,
   }
   const int b = (int)((m->step - 1) & 1);
   const int N = m->pend_n[b];
-  unsigned char* pin_out = static_cast<unsigned char*>(m->h_pin);   // (sized by pgp_multi_upload_slot; no upload is in flight)
+  unsigned char* pin_out = m->h_pin.as<unsigned char>();   // (sized by pgp_multi_upload_slot; no upload is in flight)
   const int rc = run_all(m, [&, m](int k) -> int {
     Streaming& z = m->s2[(size_t)k];
     hipStream_t S = m->stream[k];
@@ -1377,7 +1363,7 @@ int pgp_multi_icp_refine(pgp_multi* m, const pgp_multi_icp_job* jobs, int n_jobs
     for (int p = 0; p < np; ++p) {
       const IcpHostStage& g = stage[(size_t)p];
       pgp_ctx* c = dj[(size_t)p].ctx;
-      const int* it = reinterpret_cast<const int*>(static_cast<const unsigned char*>(c->h_pin) + g.off_i);
+      const int* it = reinterpret_cast<const int*>(c->h_pin.as<const unsigned char>() + g.off_i);
       bool lost = false;
       for (int i = 0; i < dj[(size_t)p].n; ++i) lost = lost || it[i] < 0;
       if (!lost) continue;

@@ -2,6 +2,7 @@
 // No CPU fallback anywhere: every scoring entry point ends in a HIP kernel launch or an error.
 
 #include "pgp_internal.h"
+#include "match_plan.h"
 
 #include <chrono>
 
@@ -49,6 +50,24 @@ int DevBuf::ensure(size_t bytes) {
 void DevBuf::release() {
   if (p) {
     hipError_t e = hipFree(p);
+    (void)e;
+  }
+  p = nullptr;
+  cap = 0;
+}
+
+int PinBuf::ensure(size_t bytes) {
+  if (bytes <= cap) return PGP_OK;
+  release();
+  const size_t want = bytes + bytes / 4;
+  PGP_HIP(hipHostMalloc(&p, want, flags));
+  cap = want;
+  return PGP_OK;
+}
+
+void PinBuf::release() {
+  if (p) {
+    hipError_t e = hipHostFree(p);
     (void)e;
   }
   p = nullptr;
@@ -108,6 +127,33 @@ inline void note_device_work(pgp_ctx* ctx, hipStream_t stream) {
 // the build is through, so its flag is cleared and its counts are taken over here -- a *_device call that follows
 // (possibly on a capturing stream, which can neither query nor wait for the build's event) then finds nothing pending
 inline int index_settled(pgp_ctx* ctx) { return ctx->index_pending ? finish_index(ctx) : PGP_OK; }
+
+// The N staged fits of ctx->d_rig: pose (double, first for alignment) | T | rms | status.  The four calls that write them
+// size the buffer by `bytes` and launch into these pointers (read AFTER d_rig.ensure: it may move the buffer), and
+// pgp_congruent_batch_fetch, which reads the resident fits back later, finds them through the same function.
+struct RigFits {
+  double* pose;
+  float* T;
+  float* rms;
+  int* status;
+  size_t bytes;
+};
+inline RigFits rig_fits(const pgp_ctx* ctx, size_t N) {
+  double* pose = ctx->d_rig.as<double>();
+  float* T = reinterpret_cast<float*>(pose + 16 * N);
+  float* rms = T + 16 * N;
+  return RigFits{pose, T, rms, reinterpret_cast<int*>(rms + N), N * (128 + 64 + 4 + 4)};
+}
+// ... and their way to the caller's arrays (rms, pose: nullable): through the pinned landing area where there is room, one
+// wait for all (pgp::HostOut)
+inline int fits_home(pgp_ctx* ctx, const RigFits& fit, size_t N, float* T, double* pose, int* status, float* rms, hipStream_t st) {
+  HostOut out(ctx, st);
+  int rc;
+  if ((rc = out.to(status, fit.status, N * 4)) != PGP_OK || (rms && (rc = out.to(rms, fit.rms, N * 4)) != PGP_OK) ||
+      (rc = out.to(T, fit.T, N * 64)) != PGP_OK || (pose && (rc = out.to(pose, fit.pose, N * 128)) != PGP_OK))
+    return rc;
+  return out.sync();
+}
 
 inline uint32_t spread10(uint32_t v) {
   v &= 1023u;
@@ -220,16 +266,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
-  if (ctx->h_pin) {
-    hipError_t e = hipHostFree(ctx->h_pin);
-    (void)e;
-    ctx->h_pin = nullptr;
-  }
-  if (ctx->h_sel_pin) {
-    hipError_t e = hipHostFree(ctx->h_sel_pin);
-    (void)e;
-    ctx->h_sel_pin = nullptr;
-  }
+  for (PinBuf* b : {&ctx->h_pin, &ctx->h_sel_pin, &ctx->h_w_pin, &ctx->h_s_pin}) b->release();
   if (ctx->h_flag) {
     hipError_t e = hipHostFree(ctx->h_flag);
     (void)e;
@@ -239,16 +276,6 @@ int pgp_destroy(pgp_ctx* ctx) {
     hipError_t e = hipHostFree(ctx->h_out);
     (void)e;
     ctx->h_out = nullptr;
-  }
-  if (ctx->h_w_pin) {
-    hipError_t e = hipHostFree(ctx->h_w_pin);
-    (void)e;
-    ctx->h_w_pin = nullptr;
-  }
-  if (ctx->h_s_pin) {
-    hipError_t e = hipHostFree(ctx->h_s_pin);
-    (void)e;
-    ctx->h_s_pin = nullptr;
   }
   if (ctx->ev_s) {
     hipError_t e = hipEventDestroy(ctx->ev_s);
@@ -383,17 +410,8 @@ int pgp_set_scene(pgp_ctx* ctx, const float* xyz, const float* nrm, const float*
   if (staged) {
     if (ctx->ev_s) PGP_HIP(hipEventSynchronize(ctx->ev_s));   // the previous scene's copies out of the staging buffer
     else PGP_HIP(hipEventCreateWithFlags(&ctx->ev_s, hipEventDisableTiming));
-    if (2 * bytes > ctx->h_s_cap) {
-      if (ctx->h_s_pin) {
-        hipError_t e = hipHostFree(ctx->h_s_pin);
-        (void)e;
-        ctx->h_s_pin = nullptr;
-        ctx->h_s_cap = 0;
-      }
-      PGP_HIP(hipHostMalloc(&ctx->h_s_pin, 2 * bytes + bytes / 2, hipHostMallocDefault));
-      ctx->h_s_cap = 2 * bytes + bytes / 2;
-    }
-    hp = static_cast<float4*>(ctx->h_s_pin);
+    if ((rc = ctx->h_s_pin.ensure(2 * bytes)) != PGP_OK) return rc;
+    hp = ctx->h_s_pin.as<float4>();
     hn = hp + N;
   } else {
     tmp.resize(2 * N);
@@ -459,17 +477,8 @@ int pgp_set_scene_weights(pgp_ctx* ctx, const float* weight, int n) {
   const size_t off_cdf = ((size_t)n * 4 + 63) & ~(size_t)63, need = off_cdf + (size_t)n * 8;
   if (ctx->ev_w) PGP_HIP(hipEventSynchronize(ctx->ev_w));   // the previous call's copies out of the staging buffer
   else PGP_HIP(hipEventCreateWithFlags(&ctx->ev_w, hipEventDisableTiming));
-  if (need > ctx->h_w_cap) {
-    if (ctx->h_w_pin) {
-      hipError_t e = hipHostFree(ctx->h_w_pin);
-      (void)e;
-      ctx->h_w_pin = nullptr;
-      ctx->h_w_cap = 0;
-    }
-    PGP_HIP(hipHostMalloc(&ctx->h_w_pin, need + need / 4, hipHostMallocDefault));
-    ctx->h_w_cap = need + need / 4;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_w_pin);
+  if ((rc = ctx->h_w_pin.ensure(need)) != PGP_OK) return rc;
+  unsigned char* pin = ctx->h_w_pin.as<unsigned char>();
   std::memcpy(pin, weight, (size_t)n * 4);
   double* cdf = reinterpret_cast<double*>(pin + off_cdf);
   double run = 0.0;
@@ -873,19 +882,9 @@ int pgp_score_lcp(pgp_ctx* ctx, const float* T, int n_h, int mode, float gate_de
   const size_t nT = (size_t)n_h * 16 * sizeof(float);
   const size_t out_bytes = (size_t)n_h * 8 + 8;
   const size_t pin_need = nT + out_bytes + 64 + 256;   // + {index, score bits, near, spare} and the completion word
-  if (pin_need > ctx->h_pin_cap) {
-    if (ctx->h_pin) {
-      hipError_t e = hipHostFree(ctx->h_pin);
-      (void)e;
-      ctx->h_pin = nullptr;
-      ctx->h_pin_cap = 0;
-    }
-    const size_t want = pin_need + pin_need / 4;
-    PGP_HIP(hipHostMalloc(&ctx->h_pin, want, hipHostMallocDefault));
-    ctx->h_pin_cap = want;
-  }
+  if ((rc = ctx->h_pin.ensure(pin_need)) != PGP_OK) return rc;
   if ((rc = ctx->d_out.ensure(out_bytes)) != PGP_OK) return rc;
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   unsigned char* pin_out = pin + ((nT + 63) & ~(size_t)63);
   float* d_scores = ctx->d_out.as<float>();
   int* d_counts = reinterpret_cast<int*>(d_scores + n_h);
@@ -1243,29 +1242,16 @@ int pgp_rigid_from_congruent(pgp_ctx* ctx, const int* base_ids, const int* quad_
   const size_t N = (size_t)n;
   int rc;
   if ((rc = ctx->d_ids.ensure(N * 32)) != PGP_OK) return rc;
-  // layout of the staged outputs: pose (double, first for alignment) | T | rms | status
   ctx->csb_fit_m = 0;   // d_rig is rewritten below: the fits a pgp_congruent_batch_fetch could name are gone
-  if ((rc = ctx->d_rig.ensure(N * (128 + 64 + 4 + 4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_rig.ensure(rig_fits(ctx, N).bytes)) != PGP_OK) return rc;
   int* d_b = ctx->d_ids.as<int>();
   int* d_q = d_b + 4 * N;
-  double* d_pose = ctx->d_rig.as<double>();
-  float* d_T = reinterpret_cast<float*>(d_pose + 16 * N);
-  float* d_rms = d_T + 16 * N;
-  int* d_status = reinterpret_cast<int*>(d_rms + N);
+  const RigFits fit = rig_fits(ctx, N);
   PGP_HIP(hipMemcpyAsync(d_b, base_ids, N * 16, hipMemcpyHostToDevice, st));
   PGP_HIP(hipMemcpyAsync(d_q, quad_ids, N * 16, hipMemcpyHostToDevice, st));
-  rc = launch_rigid(ctx, d_b, d_q, n, centroid_P, centroid_Q, d_T, d_pose, d_status, d_rms, st);
+  rc = launch_rigid(ctx, d_b, d_q, n, centroid_P, centroid_Q, fit.T, fit.pose, fit.status, fit.rms, st);
   if (rc != PGP_OK) return rc;
-  {
-    // (through the pinned landing area where there is room, one wait for all: pgp::HostOut)
-    HostOut out(ctx, st);
-    int rc_out;
-    if ((rc_out = out.to(status, d_status, N * 4)) != PGP_OK || (rms && (rc_out = out.to(rms, d_rms, N * 4)) != PGP_OK) ||
-        (rc_out = out.to(T, d_T, N * 64)) != PGP_OK || (pose && (rc_out = out.to(pose, d_pose, N * 128)) != PGP_OK) ||
-        (rc_out = out.sync()) != PGP_OK)
-      return rc_out;
-  }
-  return PGP_OK;
+  return fits_home(ctx, fit, N, T, pose, status, rms, st);
 }
 
 int pgp_extract_pairs(pgp_ctx* ctx, float pair_distance, float eps, int* pairs, int cap, int* n_pairs) {
@@ -1368,38 +1354,19 @@ int pgp_congruent_batch_fit(pgp_ctx* ctx, const int* picks, const int* base_ids,
   int rc;
   if ((rc = ctx->d_ids.ensure(N * 32)) != PGP_OK) return rc;
   ctx->csb_fit_m = 0;   // d_rig is rewritten below: the fits a pgp_congruent_batch_fetch could name are gone
-  if ((rc = ctx->d_rig.ensure(N * (128 + 64 + 4 + 4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_rig.ensure(rig_fits(ctx, N).bytes)) != PGP_OK) return rc;
   int* d_b = ctx->d_ids.as<int>();
   int* d_q = d_b + 4 * N;
   // the base of every pick (scene ids), staged from the host; the quads never leave the device
   std::vector<int> hb(4 * N);
-  for (size_t k = 0; k < N; ++k) {
-    const int b = picks[2 * k];
-    if (b < 0 || b >= ctx->csb_nb) {
-      set_error("pgp_congruent_batch_fit: pick %zu names base %d of %d", k, b, ctx->csb_nb);
-      return PGP_EINVAL;
-    }
-    for (int j = 0; j < 4; ++j) hb[4 * k + j] = base_ids[4 * (size_t)b + j];
-  }
+  if (!pick_bases(picks, N, base_ids, hb.data(), ctx->csb_nb, "pgp_congruent_batch_fit")) return PGP_EINVAL;
   PGP_HIP(hipMemcpyAsync(d_b, hb.data(), N * 16, hipMemcpyHostToDevice, st));
   rc = launch_congruent_batch_gather(ctx, picks, m, reinterpret_cast<int4*>(d_q), st);
   if (rc != PGP_OK) return rc;
-  double* d_pose = ctx->d_rig.as<double>();
-  float* d_T = reinterpret_cast<float*>(d_pose + 16 * N);
-  float* d_rms = d_T + 16 * N;
-  int* d_status = reinterpret_cast<int*>(d_rms + N);
-  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, d_T, d_pose, d_status, d_rms, st);
+  const RigFits fit = rig_fits(ctx, N);
+  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, fit.T, fit.pose, fit.status, fit.rms, st);
   if (rc != PGP_OK) return rc;
-  {
-    // (through the pinned landing area where there is room, one wait for all: pgp::HostOut)
-    HostOut out(ctx, st);
-    int rc_out;
-    if ((rc_out = out.to(status, d_status, N * 4)) != PGP_OK || (rms && (rc_out = out.to(rms, d_rms, N * 4)) != PGP_OK) ||
-        (rc_out = out.to(T, d_T, N * 64)) != PGP_OK || (pose && (rc_out = out.to(pose, d_pose, N * 128)) != PGP_OK) ||
-        (rc_out = out.sync()) != PGP_OK)
-      return rc_out;
-  }   // also: hb is a stack-owned staging vector
-  return PGP_OK;
+  return fits_home(ctx, fit, N, T, pose, status, rms, st);   // (hb, the pageable staging vector, lives until the wait is over)
 }
 
 namespace {
@@ -1539,50 +1506,30 @@ int pgp_congruent_batch_fit_score(pgp_ctx* ctx, const int* picks, const int* bas
   if ((rc = pgp_reserve(ctx, m)) != PGP_OK) return rc;
   if ((rc = ctx->d_ids.ensure(N * 32)) != PGP_OK) return rc;
   ctx->csb_fit_m = 0;   // d_rig is rewritten below: the fits a pgp_congruent_batch_fetch could name are gone
-  if ((rc = ctx->d_rig.ensure(N * (128 + 64 + 4 + 4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_rig.ensure(rig_fits(ctx, N).bytes)) != PGP_OK) return rc;
   if ((rc = ctx->d_out.ensure(N * 8 + 8)) != PGP_OK) return rc;
   // pinned staging: [bases of the picks | picks] in, [scores | status | best] out
-  const size_t in_bytes = N * 16, out_bytes = N * 8 + 8, pin_need = in_bytes + out_bytes + 128;
-  if (pin_need > ctx->h_pin_cap) {
-    if (ctx->h_pin) {
-      hipError_t e = hipHostFree(ctx->h_pin);
-      (void)e;
-      ctx->h_pin = nullptr;
-      ctx->h_pin_cap = 0;
-    }
-    const size_t want = pin_need + pin_need / 4;
-    PGP_HIP(hipHostMalloc(&ctx->h_pin, want, hipHostMallocDefault));
-    ctx->h_pin_cap = want;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  const size_t in_bytes = N * 16, out_bytes = N * 8 + 8;
+  if ((rc = ctx->h_pin.ensure(in_bytes + out_bytes + 128)) != PGP_OK) return rc;
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   int* hb = reinterpret_cast<int*>(pin);
-  for (size_t k = 0; k < N; ++k) {
-    const int b = picks[2 * k];
-    if (b < 0 || b >= ctx->csb_nb) {
-      set_error("pgp_congruent_batch_fit_score: pick %zu names base %d of %d", k, b, ctx->csb_nb);
-      return PGP_EINVAL;
-    }
-    for (int j = 0; j < 4; ++j) hb[4 * k + j] = base_ids[4 * (size_t)b + j];
-  }
+  if (!pick_bases(picks, N, base_ids, hb, ctx->csb_nb, "pgp_congruent_batch_fit_score")) return PGP_EINVAL;
   int* d_b = ctx->d_ids.as<int>();
   int* d_q = d_b + 4 * N;
   PGP_HIP(hipMemcpyAsync(d_b, hb, in_bytes, hipMemcpyHostToDevice, st));
   rc = launch_congruent_batch_gather(ctx, picks, m, reinterpret_cast<int4*>(d_q), st);
   if (rc != PGP_OK) return rc;
-  double* d_pose = ctx->d_rig.as<double>();
-  float* d_T = reinterpret_cast<float*>(d_pose + 16 * N);
-  float* d_rms = d_T + 16 * N;
-  int* d_status = reinterpret_cast<int*>(d_rms + N);
-  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, d_T, d_pose, d_status, d_rms, st);
+  const RigFits fit = rig_fits(ctx, N);
+  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, fit.T, fit.pose, fit.status, fit.rms, st);
   if (rc != PGP_OK) return rc;
-  hipLaunchKernelGGL(mask_failed_fits, dim3((m + 255) / 256), dim3(256), 0, st, (const int*)d_status, m, d_T);
+  hipLaunchKernelGGL(mask_failed_fits, dim3((m + 255) / 256), dim3(256), 0, st, (const int*)fit.status, m, fit.T);
   float* d_scores = ctx->d_out.as<float>();
   int* d_best = reinterpret_cast<int*>(d_scores + 2 * N);
-  rc = launch_score(ctx, d_T, m, mode, gate_deg, d_scores, nullptr, d_best, st);
+  rc = launch_score(ctx, fit.T, m, mode, gate_deg, d_scores, nullptr, d_best, st);
   if (rc != PGP_OK) return rc;
   unsigned char* pin_out = pin + ((in_bytes + 63) & ~(size_t)63);
   PGP_HIP(hipMemcpyAsync(pin_out, d_scores, N * 4, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipMemcpyAsync(pin_out + N * 4, d_status, N * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(pin_out + N * 4, fit.status, N * 4, hipMemcpyDeviceToHost, st));
   PGP_HIP(hipMemcpyAsync(pin_out + N * 8, d_best, 8, hipMemcpyDeviceToHost, st));
   PGP_HIP(hipStreamSynchronize(st));
   std::memcpy(scores, pin_out, N * 4);
@@ -1603,12 +1550,11 @@ int pgp_congruent_batch_fetch(pgp_ctx* ctx, const int* index, int k, float* T, d
   if (k == 0) return PGP_OK;
   CtxGuard guard(ctx);
   const size_t N = (size_t)ctx->csb_fit_m;
-  if (N == 0 || ctx->d_rig.cap < N * (128 + 64 + 4 + 4)) {
+  const RigFits fit = rig_fits(ctx, N);
+  if (N == 0 || ctx->d_rig.cap < fit.bytes) {
     set_error("pgp_congruent_batch_fetch: no fits resident (pgp_congruent_batch_fit_score first)");
     return PGP_ESTATE;
   }
-  const double* d_pose = ctx->d_rig.as<double>();
-  const float* d_T = reinterpret_cast<const float*>(d_pose + 16 * N);
   for (int j = 0; j < k; ++j)
     if (index[j] < 0 || (size_t)index[j] >= N) {
       set_error("pgp_congruent_batch_fetch: index %d of %zu", index[j], N);
@@ -1616,26 +1562,17 @@ int pgp_congruent_batch_fetch(pgp_ctx* ctx, const int* index, int k, float* T, d
     }
   // gathered on the device, ONE copy back through the pinned buffer (a 64-byte copy into pageable memory per
   // entry cost 15 us each: 0.3 ms for the twenty entries of a running-best list)
-  const size_t K = (size_t)k, pin_need = K * (4 + 128 + 64) + 256;
+  const size_t K = (size_t)k, need = K * (4 + 128 + 64) + 256;
   int rc;
-  if ((rc = ctx->d_cs_out.ensure(K * (4 + 128 + 64) + 256)) != PGP_OK) return rc;
-  if (pin_need > ctx->h_pin_cap) {
-    if (ctx->h_pin) {
-      hipError_t e = hipHostFree(ctx->h_pin);
-      (void)e;
-      ctx->h_pin = nullptr;
-      ctx->h_pin_cap = 0;
-    }
-    PGP_HIP(hipHostMalloc(&ctx->h_pin, pin_need + pin_need / 4, hipHostMallocDefault));
-    ctx->h_pin_cap = pin_need + pin_need / 4;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  if ((rc = ctx->d_cs_out.ensure(need)) != PGP_OK || (rc = ctx->h_pin.ensure(need)) != PGP_OK) return rc;
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   unsigned char* dev = ctx->d_cs_out.as<unsigned char>();
   const size_t off_pose = (K * 4 + 127) & ~(size_t)127, off_T = off_pose + K * 128;
   std::memcpy(pin, index, K * 4);
   PGP_HIP(hipMemcpyAsync(dev, pin, K * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(gather_fits, dim3((k + 3) / 4), dim3(64), 0, ctx->stream, reinterpret_cast<const int*>(dev), k, d_T, d_pose,
-                     reinterpret_cast<float*>(dev + off_T), reinterpret_cast<double*>(dev + off_pose));
+  hipLaunchKernelGGL(gather_fits, dim3((k + 3) / 4), dim3(64), 0, ctx->stream, reinterpret_cast<const int*>(dev), k,
+                     (const float*)fit.T, (const double*)fit.pose, reinterpret_cast<float*>(dev + off_T),
+                     reinterpret_cast<double*>(dev + off_pose));
   PGP_HIP(hipMemcpyAsync(pin + off_pose, dev + off_pose, K * (128 + 64), hipMemcpyDeviceToHost, ctx->stream));
   PGP_HIP(hipStreamSynchronize(ctx->stream));
   if (pose) std::memcpy(pose, pin + off_pose, K * 128);
@@ -1833,7 +1770,7 @@ int fit_score_list_impl(pgp_ctx* ctx, const int* picks, const int* base_ids, int
   if ((rc = pgp_reserve(ctx, m)) != PGP_OK) return rc;
   if ((rc = ctx->d_ids.ensure(N * 40 + 64 + (size_t)std::max(ctx->csb_nb, 0) * 16 + 64)) != PGP_OK) return rc;   // bases of the picks | picks | quads | ids of the bases
   ctx->csb_fit_m = 0;
-  if ((rc = ctx->d_rig.ensure(N * (128 + 64 + 4 + 4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_rig.ensure(rig_fits(ctx, N).bytes)) != PGP_OK) return rc;
   // scores | (counts) | best -- then what goes home in ONE copy: best {index, score bits} | list {records, pushed, indices}
   // | record scores | poses (records, best) | transforms (records, best) | hits of the best pose
   const size_t off_best = N * 8, off_list = off_best + 16, off_rs = off_list + (C + 2) * 4, off_pose = (off_rs + C * 4 + 127) & ~(size_t)127,
@@ -1841,32 +1778,15 @@ int fit_score_list_impl(pgp_ctx* ctx, const int* picks, const int* base_ids, int
   if ((rc = ctx->d_out.ensure(total)) != PGP_OK) return rc;
   const size_t in_bytes = smp.on ? (((size_t)std::max(ctx->csb_nb, 0) * 16 + 63) & ~(size_t)63) : N * 24;   // bases of the picks | picks
   const size_t home = total - off_best, pin_need = in_bytes + home + (smp.on && smp.picks_out ? N * 8 + 64 : 0) + 256;
-  if (pin_need > ctx->h_pin_cap) {
-    if (ctx->h_pin) {
-      hipError_t e = hipHostFree(ctx->h_pin);
-      (void)e;
-      ctx->h_pin = nullptr;
-      ctx->h_pin_cap = 0;
-    }
-    const size_t want = pin_need + pin_need / 4;
-    PGP_HIP(hipHostMalloc(&ctx->h_pin, want, hipHostMallocDefault));
-    ctx->h_pin_cap = want;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  if ((rc = ctx->h_pin.ensure(pin_need)) != PGP_OK) return rc;
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   int* hb = reinterpret_cast<int*>(pin);
   // device: bases of the picks [4 N] | picks [2 N] (ONE copy) | quads [4 N] | (sampled form) the bases' ids [4 nb]
   int* d_b = ctx->d_ids.as<int>();
   int* d_pk = d_b + 4 * N;
   int* d_q = d_pk + ((2 * N + 3) & ~(size_t)3);   // (int4 records: 16-byte aligned)
   if (!smp.on) {
-    for (size_t k = 0; k < N; ++k) {
-      const int b = picks[2 * k];
-      if (b < 0 || b >= ctx->csb_nb) {
-        set_error("pgp_congruent_batch_fit_score_list: pick %zu names base %d of %d", k, b, ctx->csb_nb);
-        return PGP_EINVAL;
-      }
-      for (int j = 0; j < 4; ++j) hb[4 * k + j] = base_ids[4 * (size_t)b + j];
-    }
+    if (!pick_bases(picks, N, base_ids, hb, ctx->csb_nb, "pgp_congruent_batch_fit_score_list")) return PGP_EINVAL;
     std::memcpy(hb + 4 * N, picks, N * 8);
     if ((rc = stage_to_device(st, d_b, hb, in_bytes)) != PGP_OK) return rc;
     rc = launch_congruent_batch_gather(ctx, picks, m, reinterpret_cast<int4*>(d_q), st, reinterpret_cast<const int2*>(d_pk));
@@ -1884,13 +1804,10 @@ int fit_score_list_impl(pgp_ctx* ctx, const int* picks, const int* base_ids, int
     rc = launch_congruent_batch_gather(ctx, nullptr, m, reinterpret_cast<int4*>(d_q), st, reinterpret_cast<const int2*>(d_pk));
     if (rc != PGP_OK) return rc;
   }
-  double* d_pose = ctx->d_rig.as<double>();
-  float* d_T = reinterpret_cast<float*>(d_pose + 16 * N);
-  float* d_rms = d_T + 16 * N;
-  int* d_status = reinterpret_cast<int*>(d_rms + N);
-  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, d_T, d_pose, d_status, d_rms, st);
+  const RigFits fit = rig_fits(ctx, N);
+  rc = launch_rigid(ctx, d_b, d_q, m, centroid_P, centroid_Q, fit.T, fit.pose, fit.status, fit.rms, st);
   if (rc != PGP_OK) return rc;
-  hipLaunchKernelGGL(mask_failed_fits, dim3((m + 255) / 256), dim3(256), 0, st, (const int*)d_status, m, d_T);
+  hipLaunchKernelGGL(mask_failed_fits, dim3((m + 255) / 256), dim3(256), 0, st, (const int*)fit.status, m, fit.T);
   unsigned char* dev = ctx->d_out.as<unsigned char>();
   float* d_scores = reinterpret_cast<float*>(dev);
   int* d_best = reinterpret_cast<int*>(dev + off_best);
@@ -1899,12 +1816,12 @@ int fit_score_list_impl(pgp_ctx* ctx, const int* picks, const int* base_ids, int
   double* d_pose_out = reinterpret_cast<double*>(dev + off_pose);
   float* d_T_out = reinterpret_cast<float*>(dev + off_T);
   int* d_hits = reinterpret_cast<int*>(dev + off_hits);
-  rc = launch_score(ctx, d_T, m, mode, gate_deg, d_scores, nullptr, d_best, st);
+  rc = launch_score(ctx, fit.T, m, mode, gate_deg, d_scores, nullptr, d_best, st);
   if (rc != PGP_OK) return rc;
   // the walk, the poses it keeps, the best pose and the points it registers: all behind the scores on the stream
-  hipLaunchKernelGGL(records_walk, dim3(1), dim3(256), 0, st, m, (const float*)d_scores, (const int*)d_status, list_cap, d_list, d_rs);
+  hipLaunchKernelGGL(records_walk, dim3(1), dim3(256), 0, st, m, (const float*)d_scores, (const int*)fit.status, list_cap, d_list, d_rs);
   hipLaunchKernelGGL(gather_fits_list, dim3((list_cap + 1 + 3) / 4), dim3(64), 0, st, (const int*)d_list, list_cap, (const int*)d_best,
-                     (const float*)d_T, (const double*)d_pose, d_T_out, d_pose_out);
+                     (const float*)fit.T, (const double*)fit.pose, d_T_out, d_pose_out);
   PGP_HIP(hipGetLastError());
   if (nQ > 0 && (rc = launch_registered(ctx, d_T_out + 16 * C, mode, gate_deg, d_hits, st)) != PGP_OK) return rc;
   unsigned char* pin_out = pin + ((in_bytes + 63) & ~(size_t)63);
@@ -2119,18 +2036,8 @@ int icp_host_stage(pgp_ctx* ctx, const float* src_xyz, int n_src, const float* t
   g.total = g.off_i + (size_t)n * 4;
   if ((rc = ctx->d_icp_src.ensure(g.total)) != PGP_OK) return rc;
   if ((rc = ctx->d_icp_tgt.ensure((size_t)std::max(n_tgt, 1) * 16)) != PGP_OK) return rc;
-  if (g.total + 64 > ctx->h_pin_cap) {
-    if (ctx->h_pin) {
-      hipError_t e = hipHostFree(ctx->h_pin);
-      (void)e;
-      ctx->h_pin = nullptr;
-      ctx->h_pin_cap = 0;
-    }
-    const size_t want = g.total + g.total / 4 + 64;
-    PGP_HIP(hipHostMalloc(&ctx->h_pin, want, hipHostMallocDefault));
-    ctx->h_pin_cap = want;
-  }
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  if ((rc = ctx->h_pin.ensure(g.total + 64)) != PGP_OK) return rc;
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   {
     float4* ps = reinterpret_cast<float4*>(pin);
     for (int i = 0; i < n_src; ++i)
@@ -2162,14 +2069,14 @@ int icp_host_stage(pgp_ctx* ctx, const float* src_xyz, int n_src, const float* t
 
 // the results' way back: queued behind the job's kernels on `st` ...
 int icp_host_collect_enqueue(pgp_ctx* ctx, const IcpHostStage& g, hipStream_t st) {
-  unsigned char* pin = static_cast<unsigned char*>(ctx->h_pin);
+  unsigned char* pin = ctx->h_pin.as<unsigned char>();
   unsigned char* dev = ctx->d_icp_src.as<unsigned char>();
   PGP_HIP(hipMemcpyAsync(pin + g.off_T, dev + g.off_T, g.total - g.off_T, hipMemcpyDeviceToHost, st));
   return PGP_OK;
 }
 // ... and, once `st` is synchronised, out of the pinned image into the caller's arrays
 void icp_host_collect(pgp_ctx* ctx, const IcpHostStage& g, int n, float* T, float* energy, int* iters) {
-  const unsigned char* pin = static_cast<const unsigned char*>(ctx->h_pin);
+  const unsigned char* pin = ctx->h_pin.as<const unsigned char>();
   std::memcpy(T, pin + g.off_T, (size_t)n * 64);
   if (energy) std::memcpy(energy, pin + g.off_e, (size_t)n * 4);
   if (iters) std::memcpy(iters, pin + g.off_i, (size_t)n * 4);
@@ -2210,7 +2117,7 @@ int pgp_icp_refine_ex(pgp_ctx* ctx, const float* src_xyz, int n_src, const float
   // the results' way home: one publishing kernel + the completion word (pgp::publish_and_wait) where they are small and aligned,
   // else a copy and the stream
   auto home = [&]() -> int {
-    const PubItem item{ctx->d_icp_src.as<unsigned char>() + g.off_T, static_cast<unsigned char*>(ctx->h_pin) + g.off_T, g.total - g.off_T};
+    const PubItem item{ctx->d_icp_src.as<unsigned char>() + g.off_T, ctx->h_pin.as<unsigned char>() + g.off_T, g.total - g.off_T};
     if (publish_usable(&item, 1)) return publish_and_wait(ctx, st, &item, 1);
     const int r = icp_host_collect_enqueue(ctx, g, st);
     if (r != PGP_OK) return r;
@@ -2222,7 +2129,7 @@ int pgp_icp_refine_ex(pgp_ctx* ctx, const float* src_xyz, int n_src, const float
     // A pose the scene-sized one-launch form gave up on (iteration count -1: the device was held by somebody else for
     // seconds and the pose's units did not arrive, icp.hip icp_scene_persist) -- the caller's transforms are still
     // untouched: the whole job once more, host-driven.
-    const int* it = reinterpret_cast<const int*>(static_cast<const unsigned char*>(ctx->h_pin) + g.off_i);
+    const int* it = reinterpret_cast<const int*>(ctx->h_pin.as<const unsigned char>() + g.off_i);
     bool lost = false;
     for (int i = 0; i < n; ++i) lost = lost || it[i] < 0;
     if (lost) {
@@ -3446,6 +3353,78 @@ int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_ob
 
 }  // extern "C"
 
+// ---- the tail the matcher's one-call chains share ------------------------------------------------------------------------
+namespace pgp {
+namespace {
+// the picked quads of a chain's resident batch into d_quads (launch_v4pcs_gather, launch_congruent_batch_gather)
+using ChainGather = int (*)(pgp_ctx* ctx, const int* h_picks, int m, int4* d_quads, hipStream_t st);
+// the caller's outputs of a chain call (pgp_v4pcs_hypotheses, pgp_super4pcs_hypotheses); nullable: pose and all from picks on
+struct ChainOut {
+  int* n_hyp;
+  float* T;
+  double* pose;
+  int* status;
+  float* scores;
+  int *picks, *best_index;
+  float *best_score, *best_T;
+  double* best_pose;
+};
+
+// What follows a chain's join: at most max_per_base of every base's quads (counts[nb], the draw of pgp_sample_quads), their
+// fits and plain scores on the device, the best.  `io` is the chain's own staging buffer, base_ids[4 nb] its bases.
+int chain_tail(pgp_ctx* ctx, DevBuf& io, ChainGather gather, const int* base_ids, const int* counts, int nb, unsigned long long seed,
+               int max_per_base, const float centroid_P[3], const float centroid_Q[3], const ChainOut& o) {
+  hipStream_t st = ctx->stream;
+  std::vector<int> pk((size_t)nb * (size_t)max_per_base * 2);
+  int m = 0, rc;
+  if ((rc = pgp_sample_quads(seed, counts, nb, max_per_base, pk.data(), &m)) != PGP_OK) return rc;
+  if (m == 0) return PGP_OK;
+  if ((rc = reserve_impl(ctx, m)) != PGP_OK) return rc;
+  const size_t N = (size_t)m;
+  Carve c;
+  const auto p_pose = c.add<double>(16 * N, 16);
+  const auto p_base = c.add<int4>(N, 16);
+  const auto p_quad = c.add<int4>(N, 16);
+  const auto p_T = c.add<float>(16 * N, 16);
+  const auto p_rms = c.add<float>(N, 16);
+  const auto p_status = c.add<int>(N, 16);
+  const auto p_scores = c.add<float>(N, 16);
+  if ((rc = c.ensure(io)) != PGP_OK) return rc;
+  std::vector<int> hb(4 * N);
+  pick_bases(pk.data(), N, base_ids, hb.data());
+  PGP_HIP(hipMemcpyAsync(c.at(p_base), hb.data(), N * 16, hipMemcpyHostToDevice, st));
+  if ((rc = gather(ctx, pk.data(), m, c.at(p_quad), st)) != PGP_OK) return rc;
+  if ((rc = launch_rigid(ctx, reinterpret_cast<const int*>(c.at(p_base)), reinterpret_cast<const int*>(c.at(p_quad)), m, centroid_P,
+                         centroid_Q, c.at(p_T), c.at(p_pose), c.at(p_status), c.at(p_rms), st)) != PGP_OK)
+    return rc;
+  // (the caller's transforms are the fits as pgp_rigid_from_congruent returns them; the scored copy has the failed ones masked)
+  PGP_HIP(hipMemcpyAsync(o.T, c.at(p_T), N * 64, hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(mask_failed_fits, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const int*)c.at(p_status), m, c.at(p_T));
+  if ((rc = launch_score(ctx, c.at(p_T), m, PGP_MODE_PLAIN, 0.f, c.at(p_scores), nullptr, nullptr, st)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(o.scores, c.at(p_scores), N * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(o.status, c.at(p_status), N * 4, hipMemcpyDeviceToHost, st));
+  std::vector<double> h_pose;
+  double* pose_dst = o.pose;
+  if (!pose_dst && o.best_pose) {
+    h_pose.resize(16 * N);
+    pose_dst = h_pose.data();
+  }
+  if (pose_dst) PGP_HIP(hipMemcpyAsync(pose_dst, c.at(p_pose), N * 128, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  if ((rc = index_settled(ctx)) != PGP_OK) return rc;
+  if (o.picks) std::memcpy(o.picks, pk.data(), N * 8);
+  float bs = 0.f;
+  const int bi = best_above_zero(o.scores, m, &bs);
+  *o.n_hyp = m;
+  if (o.best_index) *o.best_index = bi;
+  if (o.best_score) *o.best_score = bs;
+  if (bi >= 0 && o.best_T) std::memcpy(o.best_T, o.T + 16 * (size_t)bi, 64);
+  if (bi >= 0 && o.best_pose) std::memcpy(o.best_pose, pose_dst + 16 * (size_t)bi, 128);
+  return PGP_OK;
+}
+}  // namespace
+}  // namespace pgp
+
 // ---- tetrahedron-base mode, "V4PCS" (v4pcs.hip) ----------------------------------------------------------------------
 namespace {
 constexpr int kV4MaxTrials = 1 << 20;   // triangle / fourth-point draws per attempt
@@ -3568,15 +3547,14 @@ int pgp_v4pcs_hypotheses(pgp_ctx* ctx, const pgp_v4pcs_options* opt, const float
   int rc = launch_tetrahedron_bases(ctx, opt->seed, opt->max_attempts, opt->triangle_trials, opt->fourth_trials, opt->max_base_diameter,
                                     a_ids.data(), a_dist.data(), a_status.data(), st);
   if (rc != PGP_OK) return rc;
+  const std::vector<int> kept = first_successes(a_status.data(), opt->max_attempts, opt->n_bases);
+  const int nb = (int)kept.size();
   std::vector<int> b_ids;
   std::vector<float> b_dist;
-  int nb = 0;
-  for (size_t a = 0; a < A && nb < opt->n_bases; ++a)
-    if (a_status[a] == 1) {
-      b_ids.insert(b_ids.end(), a_ids.begin() + 4 * a, a_ids.begin() + 4 * a + 4);
-      b_dist.insert(b_dist.end(), a_dist.begin() + 6 * a, a_dist.begin() + 6 * a + 6);
-      ++nb;
-    }
+  for (const int a : kept) {
+    b_ids.insert(b_ids.end(), a_ids.begin() + 4 * a, a_ids.begin() + 4 * a + 4);
+    b_dist.insert(b_dist.end(), a_dist.begin() + 6 * a, a_dist.begin() + 6 * a + 6);
+  }
   if (n_bases) *n_bases = nb;
   if (base_ids && nb > 0) std::memcpy(base_ids, b_ids.data(), (size_t)nb * 16);
   if (nb == 0) {   // no base: also no batch left behind that a pick could name
@@ -3586,60 +3564,9 @@ int pgp_v4pcs_hypotheses(pgp_ctx* ctx, const pgp_v4pcs_options* opt, const float
   // 2. the join: quads stay resident
   std::vector<int> stored((size_t)nb);
   if ((rc = launch_v4pcs_batch(ctx, b_dist.data(), nb, opt->eps, opt->per_base_cap, nullptr, stored.data(), st)) != PGP_OK) return rc;
-  // 3. at most max_per_base of every base's kept quads
-  std::vector<int> pk((size_t)nb * (size_t)opt->max_per_base * 2);
-  int m = 0;
-  if ((rc = pgp_sample_quads(opt->seed, stored.data(), nb, opt->max_per_base, pk.data(), &m)) != PGP_OK) return rc;
-  if (m == 0) return PGP_OK;
-  // 4. + 5. fit and plain score, on the device
-  if ((rc = reserve_impl(ctx, m)) != PGP_OK) return rc;
-  const size_t N = (size_t)m;
-  Carve c;
-  const auto p_pose = c.add<double>(16 * N, 16);
-  const auto p_base = c.add<int4>(N, 16);
-  const auto p_quad = c.add<int4>(N, 16);
-  const auto p_T = c.add<float>(16 * N, 16);
-  const auto p_rms = c.add<float>(N, 16);
-  const auto p_status = c.add<int>(N, 16);
-  const auto p_scores = c.add<float>(N, 16);
-  if ((rc = c.ensure(ctx->d_v4_io)) != PGP_OK) return rc;
-  std::vector<int> hb(4 * N);
-  for (size_t k = 0; k < N; ++k) std::memcpy(&hb[4 * k], &b_ids[4 * (size_t)pk[2 * k]], 16);
-  PGP_HIP(hipMemcpyAsync(c.at(p_base), hb.data(), N * 16, hipMemcpyHostToDevice, st));
-  if ((rc = launch_v4pcs_gather(ctx, pk.data(), m, c.at(p_quad), st)) != PGP_OK) return rc;
-  if ((rc = launch_rigid(ctx, reinterpret_cast<const int*>(c.at(p_base)), reinterpret_cast<const int*>(c.at(p_quad)), m, centroid_P,
-                         centroid_Q, c.at(p_T), c.at(p_pose), c.at(p_status), c.at(p_rms), st)) != PGP_OK)
-    return rc;
-  // (the caller's transforms are the fits as pgp_rigid_from_congruent returns them; the scored copy has the failed ones masked)
-  PGP_HIP(hipMemcpyAsync(T, c.at(p_T), N * 64, hipMemcpyDeviceToHost, st));
-  hipLaunchKernelGGL(mask_failed_fits, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const int*)c.at(p_status), m, c.at(p_T));
-  if ((rc = launch_score(ctx, c.at(p_T), m, PGP_MODE_PLAIN, 0.f, c.at(p_scores), nullptr, nullptr, st)) != PGP_OK) return rc;
-  PGP_HIP(hipMemcpyAsync(scores, c.at(p_scores), N * 4, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipMemcpyAsync(status, c.at(p_status), N * 4, hipMemcpyDeviceToHost, st));
-  std::vector<double> h_pose;
-  double* pose_dst = pose;
-  if (!pose_dst && best_pose) {
-    h_pose.resize(16 * N);
-    pose_dst = h_pose.data();
-  }
-  if (pose_dst) PGP_HIP(hipMemcpyAsync(pose_dst, c.at(p_pose), N * 128, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipStreamSynchronize(st));
-  if (int rc2 = index_settled(ctx)) return rc2;
-  if (picks) std::memcpy(picks, pk.data(), N * 8);
-  // the lowest index of the maximum; no hypothesis above 0: none
-  int bi = -1;
-  float bs = 0.f;
-  for (int k = 0; k < m; ++k)
-    if (scores[k] > bs) {
-      bs = scores[k];
-      bi = k;
-    }
-  *n_hyp = m;
-  if (best_index) *best_index = bi;
-  if (best_score) *best_score = bs;
-  if (bi >= 0 && best_T) std::memcpy(best_T, T + 16 * (size_t)bi, 64);
-  if (bi >= 0 && best_pose) std::memcpy(best_pose, pose_dst + 16 * (size_t)bi, 128);
-  return PGP_OK;
+  // 3. .. 5. at most max_per_base of every base's kept quads, their fits and plain scores, the best
+  return chain_tail(ctx, ctx->d_v4_io, launch_v4pcs_gather, b_ids.data(), stored.data(), nb, opt->seed, opt->max_per_base, centroid_P,
+                    centroid_Q, ChainOut{n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose});
 }
 
 }  // extern "C"
@@ -3735,19 +3662,19 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
   int rc = launch_wide_bases(ctx, opt->seed, opt->max_attempts, opt->triangle_trials, opt->max_base_diameter, a_ids.data(), a_inv.data(),
                              a_dist.data(), a_status.data(), a_xyz.data(), st);
   if (rc != PGP_OK) return rc;
+  const std::vector<int> kept = first_successes(a_status.data(), opt->max_attempts, opt->n_bases);
+  const int nb = (int)kept.size();
   std::vector<int> b_ids, b_lists;
   std::vector<float> b_inv, b_dist, b_xyz;
-  int nb = 0;
-  for (size_t a = 0; a < A && nb < opt->n_bases; ++a)
-    if (a_status[a] == 1) {
-      b_ids.insert(b_ids.end(), a_ids.begin() + 4 * a, a_ids.begin() + 4 * a + 4);
-      b_inv.insert(b_inv.end(), a_inv.begin() + 2 * a, a_inv.begin() + 2 * a + 2);
-      b_dist.insert(b_dist.end(), a_dist.begin() + 2 * a, a_dist.begin() + 2 * a + 2);
-      b_xyz.insert(b_xyz.end(), a_xyz.begin() + 12 * a, a_xyz.begin() + 12 * a + 12);
-      b_lists.push_back(2 * nb);       // pairs1: the list of |b0 b1|
-      b_lists.push_back(2 * nb + 1);   // pairs6: the list of |b2 b3|
-      ++nb;
-    }
+  for (int b = 0; b < nb; ++b) {
+    const int a = kept[b];
+    b_ids.insert(b_ids.end(), a_ids.begin() + 4 * a, a_ids.begin() + 4 * a + 4);
+    b_inv.insert(b_inv.end(), a_inv.begin() + 2 * a, a_inv.begin() + 2 * a + 2);
+    b_dist.insert(b_dist.end(), a_dist.begin() + 2 * a, a_dist.begin() + 2 * a + 2);
+    b_xyz.insert(b_xyz.end(), a_xyz.begin() + 12 * a, a_xyz.begin() + 12 * a + 12);
+    b_lists.push_back(2 * b);       // pairs1: the list of |b0 b1|
+    b_lists.push_back(2 * b + 1);   // pairs6: the list of |b2 b3|
+  }
   if (n_bases) *n_bases = nb;
   if (base_ids && nb > 0) std::memcpy(base_ids, b_ids.data(), (size_t)nb * 16);
   if (base_invariants && nb > 0) std::memcpy(base_invariants, b_inv.data(), (size_t)nb * 8);
@@ -3758,60 +3685,12 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
   std::vector<int> nq((size_t)nb);
   if ((rc = launch_find_congruent_batch_lists(ctx, b_xyz.data(), b_inv.data(), b_lists.data(), nb, opt->eps, nq.data(), st)) != PGP_OK)
     return rc;
-  // 4. at most max_per_base of every base's quads
-  std::vector<int> pk((size_t)nb * (size_t)opt->max_per_base * 2);
-  int m = 0;
-  if ((rc = pgp_sample_quads(opt->seed, nq.data(), nb, opt->max_per_base, pk.data(), &m)) != PGP_OK) return rc;
-  if (m == 0) return PGP_OK;
-  // 5. + 6. fit and plain score, on the device
-  if ((rc = reserve_impl(ctx, m)) != PGP_OK) return rc;
-  const size_t N = (size_t)m;
-  Carve c;
-  const auto p_pose = c.add<double>(16 * N, 16);
-  const auto p_base = c.add<int4>(N, 16);
-  const auto p_quad = c.add<int4>(N, 16);
-  const auto p_T = c.add<float>(16 * N, 16);
-  const auto p_rms = c.add<float>(N, 16);
-  const auto p_status = c.add<int>(N, 16);
-  const auto p_scores = c.add<float>(N, 16);
-  if ((rc = c.ensure(ctx->d_s4_io)) != PGP_OK) return rc;
-  std::vector<int> hb(4 * N);
-  for (size_t k = 0; k < N; ++k) std::memcpy(&hb[4 * k], &b_ids[4 * (size_t)pk[2 * k]], 16);
-  PGP_HIP(hipMemcpyAsync(c.at(p_base), hb.data(), N * 16, hipMemcpyHostToDevice, st));
-  if ((rc = launch_congruent_batch_gather(ctx, pk.data(), m, c.at(p_quad), st)) != PGP_OK) return rc;
-  if ((rc = launch_rigid(ctx, reinterpret_cast<const int*>(c.at(p_base)), reinterpret_cast<const int*>(c.at(p_quad)), m, centroid_P,
-                         centroid_Q, c.at(p_T), c.at(p_pose), c.at(p_status), c.at(p_rms), st)) != PGP_OK)
-    return rc;
-  // (the caller's transforms are the fits as pgp_rigid_from_congruent returns them; the scored copy has the failed ones masked)
-  PGP_HIP(hipMemcpyAsync(T, c.at(p_T), N * 64, hipMemcpyDeviceToHost, st));
-  hipLaunchKernelGGL(mask_failed_fits, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const int*)c.at(p_status), m, c.at(p_T));
-  if ((rc = launch_score(ctx, c.at(p_T), m, PGP_MODE_PLAIN, 0.f, c.at(p_scores), nullptr, nullptr, st)) != PGP_OK) return rc;
-  PGP_HIP(hipMemcpyAsync(scores, c.at(p_scores), N * 4, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipMemcpyAsync(status, c.at(p_status), N * 4, hipMemcpyDeviceToHost, st));
-  std::vector<double> h_pose;
-  double* pose_dst = pose;
-  if (!pose_dst && best_pose) {
-    h_pose.resize(16 * N);
-    pose_dst = h_pose.data();
-  }
-  if (pose_dst) PGP_HIP(hipMemcpyAsync(pose_dst, c.at(p_pose), N * 128, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipStreamSynchronize(st));
-  if (int rc2 = index_settled(ctx)) return rc2;
-  if (picks) std::memcpy(picks, pk.data(), N * 8);
-  // the lowest index of the maximum; no hypothesis above 0: none
-  int bi = -1;
-  float bs = 0.f;
-  for (int k = 0; k < m; ++k)
-    if (scores[k] > bs) {
-      bs = scores[k];
-      bi = k;
-    }
-  *n_hyp = m;
-  if (best_index) *best_index = bi;
-  if (best_score) *best_score = bs;
-  if (bi >= 0 && best_T) std::memcpy(best_T, T + 16 * (size_t)bi, 64);
-  if (bi >= 0 && best_pose) std::memcpy(best_pose, pose_dst + 16 * (size_t)bi, 128);
-  return PGP_OK;
+  // 4. .. 6. at most max_per_base of every base's quads, their fits and plain scores, the best
+  const ChainGather gather = [](pgp_ctx* c, const int* h_picks, int m, int4* d_quads, hipStream_t s) {
+    return launch_congruent_batch_gather(c, h_picks, m, d_quads, s);
+  };
+  return chain_tail(ctx, ctx->d_s4_io, gather, b_ids.data(), nq.data(), nb, opt->seed, opt->max_per_base, centroid_P, centroid_Q,
+                    ChainOut{n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose});
 }
 
 }  // extern "C"

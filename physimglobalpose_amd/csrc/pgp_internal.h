@@ -79,6 +79,19 @@ struct DevBuf {
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// Its twin in pinned host memory: the staging images of the host-pointer calls.  Same growth, same life.  ensure() frees the
+// old image, so whatever may still read it (a queued stage_to_device, a copy on a side stream) is waited for by the caller
+// first.  The context's images are hipHostMallocDefault; the device group's, read by every member, is hipHostMallocPortable.
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  unsigned int flags;
+  explicit PinBuf(unsigned int f = hipHostMallocDefault) : flags(f) {}
+  int ensure(size_t bytes);  // returns PGP_OK / PGP_EHIP
+  void release();
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
 // Carves one device buffer into typed pieces: name the pieces (type, count, alignment) in order, read bytes(), ensure() the
 // buffer (or bind() one that already holds this layout), then read typed pointers with at().  Alignments are powers of two
 // up to hipMalloc's 256.
@@ -240,8 +253,7 @@ struct pgp_ctx {
   bool prob_cdf_valid = false;
   pgp::DevBuf d_sel_ws;                 // base-selection workspace / staging
   int sel_begun_A = 0;                  // attempts of a selection that was queued and not collected yet (pgp_select_bases_rows_begin)
-  void* h_sel_pin = nullptr;            // its variates' pinned image
-  size_t h_sel_cap = 0;
+  pgp::PinBuf h_sel_pin;                // its variates' pinned image
 
   pgp::DevBuf d_pre_ws, d_vg_ws, d_pre_io;   // preprocess.hip: bbox partials, voxel-grid workspace, host-API staging
   pgp::DevBuf d_mls_ws;                      // mls.hip: sort keys, sorted cloud, per-point results
@@ -296,17 +308,14 @@ struct pgp_ctx {
                           // (finalize_scores' exact re-score of near-best hypotheses)
 
   // pinned host staging for the host-pointer scoring call (transforms in, scores | counts | best out)
-  void* h_pin = nullptr;
-  size_t h_pin_cap = 0;
+  pgp::PinBuf h_pin;
   // pinned staging of pgp_set_scene_weights alone (weights + their double prefix sums go up without a synchronisation;
   // ev_w: the copies out of it have finished -- waited for before the next call overwrites it)
-  void* h_w_pin = nullptr;
-  size_t h_w_cap = 0;
+  pgp::PinBuf h_w_pin;
   hipEvent_t ev_w = nullptr;
   // the same for pgp_set_scene's points and normals (scenes up to 4 MB of them); the side-stream index build waits for
   // ev_s on its own stream, the host for nothing
-  void* h_s_pin = nullptr;
-  size_t h_s_cap = 0;
+  pgp::PinBuf h_s_pin;
   hipEvent_t ev_s = nullptr;
   bool scene_upload_pending = false;   // ev_s has been recorded behind this scene's uploads
   // pinned landing area of small results on their way to the caller's (pageable) memory: pgp::HostOut

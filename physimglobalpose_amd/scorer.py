@@ -415,23 +415,32 @@ class LcpScorer:
         return out[: len(pk)]
 
     @staticmethod
-    def v4pcs_options(max_base_diameter, **kw):
-        o = _lib.V4pcsOptions()
-        _lib.check(_lib.load().pgp_v4pcs_default_options(C.byref(o)))
-        o.max_base_diameter = float(max_base_diameter)
+    def _options(struct, name, **kw):
+        """A pgp_<name>_options struct: pgp_<name>_default_options, then the keyword overrides."""
+        o = struct()
+        _lib.check(getattr(_lib.load(), f"pgp_{name}_default_options")(C.byref(o)))
         for k, v in kw.items():
             if not hasattr(o, k):
-                raise TypeError(f"pgp_v4pcs_options has no field {k!r}")
+                raise TypeError(f"pgp_{name}_options has no field {k!r}")
             setattr(o, k, v)
         return o
+
+    @staticmethod
+    def v4pcs_options(max_base_diameter, **kw):
+        return LcpScorer._options(_lib.V4pcsOptions, "v4pcs", max_base_diameter=float(max_base_diameter), **kw)
 
     def v4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), **opt):
         """pgp_v4pcs_hypotheses: bases, join, sampling, fits and plain scores in one call.  Returns a dict: base_ids, T, pose,
         status, scores, picks (of the n_hyp hypotheses), best_index, best_score, best_T, best_pose."""
-        o = self.v4pcs_options(max_base_diameter, **opt)
+        return self._chain(self._lib.pgp_v4pcs_hypotheses, self.v4pcs_options(max_base_diameter, **opt), centroid_P, centroid_Q)
+
+    def _chain(self, call, o, centroid_P, centroid_Q, base_invariants=False):
+        """One call of a matcher chain (pgp_v4pcs_hypotheses, pgp_super4pcs_hypotheses) with options o -> its dict;
+        base_invariants: the call has that output behind base_ids."""
         cP, cQ = _f32(centroid_P).reshape(3), _f32(centroid_Q).reshape(3)
         cap = max(int(o.n_bases) * int(o.max_per_base), 1)
         bids = np.zeros((max(int(o.n_bases), 1), 4), np.int32)
+        binv = np.zeros((max(int(o.n_bases), 1), 2), np.float32)
         T = np.zeros((cap, 16), np.float32)
         pose = np.zeros((cap, 16), np.float64)
         status = np.zeros(cap, np.int32)
@@ -441,13 +450,17 @@ class LcpScorer:
         nb, nh, best = C.c_int(0), C.c_int(0), C.c_int(-1)
         bs = C.c_float(0)
         dp = C.POINTER(C.c_double)
-        _lib.check(self._lib.pgp_v4pcs_hypotheses(
-            self._h, C.byref(o), _fp(cP), _fp(cQ), C.byref(nb), bids.ctypes.data_as(_i), C.byref(nh), _fp(T), pose.ctypes.data_as(dp),
-            status.ctypes.data_as(_i), _fp(scores), picks.ctypes.data_as(_i), C.byref(best), C.byref(bs), _fp(bT), bp.ctypes.data_as(dp)))
+        _lib.check(call(
+            self._h, C.byref(o), _fp(cP), _fp(cQ), C.byref(nb), bids.ctypes.data_as(_i), *([_fp(binv)] if base_invariants else []),
+            C.byref(nh), _fp(T), pose.ctypes.data_as(dp), status.ctypes.data_as(_i), _fp(scores), picks.ctypes.data_as(_i),
+            C.byref(best), C.byref(bs), _fp(bT), bp.ctypes.data_as(dp)))
         k = nh.value
-        return dict(base_ids=bids[: nb.value].copy(), T=T[:k].copy(), pose=pose[:k].copy(), status=status[:k].copy(),
-                    scores=scores[:k].copy(), picks=picks[:k].copy(), best_index=best.value, best_score=float(np.float32(bs.value)),
-                    best_T=bT, best_pose=bp)
+        out = dict(base_ids=bids[: nb.value].copy())
+        if base_invariants:
+            out["base_invariants"] = binv[: nb.value].copy()
+        out.update(T=T[:k].copy(), pose=pose[:k].copy(), status=status[:k].copy(), scores=scores[:k].copy(), picks=picks[:k].copy(),
+                   best_index=best.value, best_score=float(np.float32(bs.value)), best_T=bT, best_pose=bp)
+        return out
 
     # ---- classic mode, "Super4PCS" (base.cc:505-580, 1963-1969): positions alone, two pair lists per base ----
     def select_wide_bases(self, seed, n_attempts, max_base_diameter, triangle_trials=1000):
@@ -494,41 +507,14 @@ class LcpScorer:
 
     @staticmethod
     def super4pcs_options(max_base_diameter, **kw):
-        o = _lib.Super4pcsOptions()
-        _lib.check(_lib.load().pgp_super4pcs_default_options(C.byref(o)))
-        o.max_base_diameter = float(max_base_diameter)
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise TypeError(f"pgp_super4pcs_options has no field {k!r}")
-            setattr(o, k, v)
-        return o
+        return LcpScorer._options(_lib.Super4pcsOptions, "super4pcs", max_base_diameter=float(max_base_diameter), **kw)
 
     def super4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), **opt):
         """pgp_super4pcs_hypotheses: wide bases, pair lists, join, sampling, fits and plain scores in one call.  Returns the
         dict of v4pcs_hypotheses (base_ids, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose) plus
         base_invariants."""
-        o = self.super4pcs_options(max_base_diameter, **opt)
-        cP, cQ = _f32(centroid_P).reshape(3), _f32(centroid_Q).reshape(3)
-        cap = max(int(o.n_bases) * int(o.max_per_base), 1)
-        bids = np.zeros((max(int(o.n_bases), 1), 4), np.int32)
-        binv = np.zeros((max(int(o.n_bases), 1), 2), np.float32)
-        T = np.zeros((cap, 16), np.float32)
-        pose = np.zeros((cap, 16), np.float64)
-        status = np.zeros(cap, np.int32)
-        scores = np.zeros(cap, np.float32)
-        picks = np.zeros((cap, 2), np.int32)
-        bT, bp = np.zeros(16, np.float32), np.zeros(16, np.float64)
-        nb, nh, best = C.c_int(0), C.c_int(0), C.c_int(-1)
-        bs = C.c_float(0)
-        dp = C.POINTER(C.c_double)
-        _lib.check(self._lib.pgp_super4pcs_hypotheses(
-            self._h, C.byref(o), _fp(cP), _fp(cQ), C.byref(nb), bids.ctypes.data_as(_i), _fp(binv), C.byref(nh), _fp(T),
-            pose.ctypes.data_as(dp), status.ctypes.data_as(_i), _fp(scores), picks.ctypes.data_as(_i), C.byref(best), C.byref(bs),
-            _fp(bT), bp.ctypes.data_as(dp)))
-        k = nh.value
-        return dict(base_ids=bids[: nb.value].copy(), base_invariants=binv[: nb.value].copy(), T=T[:k].copy(), pose=pose[:k].copy(),
-                    status=status[:k].copy(), scores=scores[:k].copy(), picks=picks[:k].copy(), best_index=best.value,
-                    best_score=float(np.float32(bs.value)), best_T=bT, best_pose=bp)
+        return self._chain(self._lib.pgp_super4pcs_hypotheses, self.super4pcs_options(max_base_diameter, **opt), centroid_P, centroid_Q,
+                           base_invariants=True)
 
     # ---- segment pre-processing (ObjectPoseCandidateSet.cpp:28-51) -----------------------------------
     def radius_outlier_filter(self, xyz, nrm=None, radius=0.03, min_neighbors=10):

@@ -292,3 +292,82 @@ def test_quads_drawn_on_the_device_equal_the_host_statement_and_the_picked_call(
     with pytest.raises(Exception, match="max_per_base"):
         sc.congruent_batch_sample_fit_score_list(1, ids, cP, cQ, max_per_base=129)
     sc.close()
+
+
+def test_one_pinned_buffer_through_growth_and_reuse(case):
+    """The host-pointer calls stage through ONE pinned buffer of the context, grown on demand.  A context that makes them in a
+    row -- a small scoring call, the list call, a fetch, a small ICP call, a scoring call that makes the buffer grow to more than
+    1.25 x its size, then the three small ones again in the grown buffer -- returns what a context returns that makes that
+    call alone, bit for bit.  (A 64-point model and a handful of picks keep the list call's image below the 64 hypotheses'.)"""
+    import ctypes as C
+    from physimglobalpose_amd import PGP_MODE_PLAIN
+    w, table, keys, sc0, ids, inv = case
+    counts = np.array([len(table[tuple(k)]) for k in keys.tolist()], np.int32)
+    pairs = np.concatenate([np.array(table[tuple(k)], np.int32).reshape(-1, 2) for k in keys.tolist()])
+    ids4, inv4 = np.ascontiguousarray(ids[:4], np.int32), inv[:4]
+    cP, cQ = np.ascontiguousarray(w.centroid_P, np.float32), np.ascontiguousarray(w.centroid_Q, np.float32)
+
+    def hypotheses(n):
+        T = np.tile(np.asarray(w.T_gt, np.float32).reshape(1, 16), (n, 1))     # the true pose, slid along x
+        T[:, 12] += np.arange(n, dtype=np.float32) * np.float32(0.0005)
+        return T
+
+    src = (w.Q_xyz[:64] + np.float32(0.002)).astype(np.float32)
+    eye = np.eye(4, dtype=np.float32).reshape(1, 16)
+
+    def context():
+        s = LcpScorer()
+        s.init(w.P_xyz, w.P_nrm, w.P_w, w.Q_xyz[:64], w.Q_nrm[:64], w.delta)
+        s.set_search_model(w.Qs_xyz)
+        s.set_ppf_map(keys, counts, pairs)
+        n_quads = s.find_congruent_batch(ids4, w.P_xyz[ids4], inv4, w.delta)
+        return s, LcpScorer.sample_quads(9, n_quads, 2)
+
+    def score(s, n):
+        return s.score(hypotheses(n), PGP_MODE_PLAIN)
+
+    def listed(s, picks):
+        return s.congruent_batch_fit_score_list(picks, ids4, cP, cQ, PGP_MODE_PLAIN, 0.0, list_cap=2)
+
+    def fetch(s, k):
+        index = np.arange(k, dtype=np.int32)
+        T, pose = np.zeros((k, 16), np.float32), np.zeros((k, 16), np.float64)
+        assert s._lib.pgp_congruent_batch_fetch(s._h, index.ctypes.data_as(C.POINTER(C.c_int)), k, T.ctypes.data_as(C.POINTER(C.c_float)),
+                                                pose.ctypes.data_as(C.POINTER(C.c_double))) == 0
+        return T, pose
+
+    def icp(s):
+        return s.icp_refine(src, w.Q_xyz, eye, trim=0.9, max_iterations=5)
+
+    def same(a, b):
+        a, b = (list(x.values()) if isinstance(x, dict) else list(x) for x in (a, b))
+        return len(a) == len(b) and all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b))
+
+    # every call alone on a context of its own (the fetch behind the list call it reads)
+    s, picks = context()
+    want_8 = score(s, 8)
+    s.close()
+    s, picks = context()
+    want_64 = score(s, 64)
+    s.close()
+    s, picks = context()
+    k = min(len(picks), 3)
+    assert 2 <= len(picks) <= 8
+    want_list = listed(s, picks)
+    want_fetch = fetch(s, k)
+    s.close()
+    s, picks = context()
+    want_icp = icp(s)
+    s.close()
+    assert want_8[0][0] > 0 and want_64[0][0] > 0
+    # ... and in a row on one
+    s, picks = context()
+    assert same(score(s, 8), want_8)
+    assert same(listed(s, picks), want_list)
+    assert same(fetch(s, k), want_fetch)
+    assert same(icp(s), want_icp)
+    assert same(score(s, 64), want_64)
+    assert same(listed(s, picks), want_list)
+    assert same(fetch(s, k), want_fetch)
+    assert same(icp(s), want_icp)
+    s.close()

@@ -12,6 +12,7 @@ import _v4pcs_restate as R
 from physimglobalpose_amd import LcpScorer
 from physimglobalpose_amd._lib import PgpError
 from test_super4pcs_cpu import RECOVERY, RECOVERY_SEEDS
+from test_v4pcs_gpu import CHAIN_OPT, check_optional_outputs, resident_fits
 
 pytestmark = pytest.mark.gpu
 
@@ -376,6 +377,23 @@ def test_chain_equals_the_steps_one_by_one(rec1):
     assert h["best_score"] == scores[best] and np.array_equal(h["best_T"], T[best]) and np.array_equal(h["best_pose"], pose[best])
     # the chain leaves its quad batch resident
     assert np.array_equal(s.congruent_batch_quads(picks), quads)
+
+
+def test_chain_best_pose_without_pose(rec1):
+    s, Q, seg, vis, truth, diam = rec1[:6]
+    check_optional_outputs(s, "super4pcs", diam, CHAIN_OPT)
+
+
+def test_chain_keeps_its_own_buffers(rec1):
+    """The fits of a pgp_congruent_batch_fit_score on a quad batch made from pair lists do NOT survive a chain call: the
+    chain's first step after the bases is pgp_extract_pairs_batch's, which rewrites the lists that batch names and discards
+    it with its fits -- the fetch is a state error, not poses of a batch that is gone."""
+    s, Q, seg, vis, truth, diam = rec1[:6]
+    fetch = resident_fits(s, seg, diam)
+    assert fetch()[0] == 0
+    zero = np.zeros(3, np.float32)
+    assert len(s.super4pcs_hypotheses(diam, zero, zero, **CHAIN_OPT)["T"]) > 12
+    assert fetch()[0] == ESTATE
 
 
 def test_chain_reports_fewer_bases_when_attempts_run_out(rec1):

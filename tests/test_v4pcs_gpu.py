@@ -341,6 +341,98 @@ def test_chain_equals_the_steps_one_by_one(rec1):
     assert h["best_score"] == scores[best] and np.array_equal(h["best_T"], T[best]) and np.array_equal(h["best_pose"], pose[best])
 
 
+def chain_raw(s, which, diam, opt, pose=True, rest=True):
+    """pgp_<which>_hypotheses through ctypes, centroids zero.  pose=False: pose is NULL; rest=False: picks, best_T and best_pose
+    are NULL as well."""
+    import ctypes as C
+    o = getattr(s, which + "_options")(diam, **opt)
+    cap = o.n_bases * o.max_per_base
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))
+    zero = np.zeros(3, np.float32)
+    bids, binv = np.zeros((o.n_bases, 4), np.int32), np.zeros((o.n_bases, 2), np.float32)
+    T, status, scores = np.zeros((cap, 16), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+    P = np.zeros((cap, 16), np.float64) if pose else None
+    picks = np.zeros((cap, 2), np.int32) if rest else None
+    bT = np.zeros(16, np.float32) if rest else None
+    bP = np.zeros(16, np.float64) if rest else None
+    nb, nh, best, bs = C.c_int(0), C.c_int(0), C.c_int(-1), C.c_float(0)
+    args = [s._h, C.byref(o), ptr(zero, C.c_float), ptr(zero, C.c_float), C.byref(nb), ptr(bids, C.c_int)]
+    args += [ptr(binv, C.c_float)] if which == "super4pcs" else []
+    args += [C.byref(nh), ptr(T, C.c_float), ptr(P, C.c_double), ptr(status, C.c_int), ptr(scores, C.c_float), ptr(picks, C.c_int),
+             C.byref(best), C.byref(bs), ptr(bT, C.c_float), ptr(bP, C.c_double)]
+    assert getattr(s._lib, f"pgp_{which}_hypotheses")(*args) == 0
+    n = nh.value
+    return dict(n=n, T=T[:n], status=status[:n], scores=scores[:n], pose=None if P is None else P[:n], best_index=best.value,
+                best_score=np.float32(bs.value), best_T=bT, best_pose=bP)
+
+
+def check_optional_outputs(s, which, diam, opt):
+    """best_pose out of the chain's own temporary (pose NULL) is best_pose out of the caller's pose array, bit for bit; with
+    picks, best_T and best_pose NULL as well nothing else changes."""
+    full = chain_raw(s, which, diam, opt)
+    bi = full["best_index"]
+    assert full["n"] > 12 and bi >= 0
+    assert full["best_pose"].tobytes() == full["pose"][bi].tobytes() and full["best_T"].tobytes() == full["T"][bi].tobytes()
+    no_pose = chain_raw(s, which, diam, opt, pose=False)
+    assert no_pose["best_pose"].tobytes() == full["best_pose"].tobytes()
+    bare = chain_raw(s, which, diam, opt, pose=False, rest=False)
+    for got in (no_pose, bare):
+        assert got["n"] == full["n"] and got["best_index"] == bi and got["best_score"] == full["best_score"]
+        assert got["scores"].tobytes() == full["scores"].tobytes() and np.array_equal(got["status"], full["status"])
+        assert got["T"].tobytes() == full["T"].tobytes()
+    assert no_pose["best_T"].tobytes() == full["best_T"].tobytes()
+
+
+def resident_fits(s, seg, diam):
+    """A small quad batch (classic-mode pair lists) made resident on the context and fitted by
+    pgp_congruent_batch_fit_score; returns fetch() -> (rc, T, pose) of pgp_congruent_batch_fetch over all its fits."""
+    import ctypes as C
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    ids, inv, dist, status = s.select_wide_bases(11, 60, diam)
+    ok = np.flatnonzero(status == 1)[:4]
+    assert len(ok) == 4
+    s.extract_pairs_batch(dist[ok].reshape(-1), 0.005)
+    nq = s.find_congruent_batch_lists(seg[ids[ok]], inv[ok], np.arange(8, dtype=np.int32).reshape(4, 2), 0.005)
+    picks = np.ascontiguousarray(LcpScorer.sample_quads(5, nq, 8), np.int32)
+    m = len(picks)
+    assert m >= 4
+    zero, base_ids = np.zeros(3, np.float32), np.ascontiguousarray(ids[ok], np.int32)
+    scores, st = np.zeros(m, np.float32), np.zeros(m, np.int32)
+    assert s._lib.pgp_congruent_batch_fit_score(s._h, ip(picks), ip(base_ids), m, fp(zero), fp(zero), 0, C.c_float(0), fp(scores), ip(st),
+                                                None, None) == 0
+    assert (st == 1).any()
+
+    def fetch():
+        index = np.arange(m, dtype=np.int32)
+        T, pose = np.zeros((m, 16), np.float32), np.zeros((m, 16), np.float64)
+        rc = s._lib.pgp_congruent_batch_fetch(s._h, ip(index), m, fp(T), pose.ctypes.data_as(C.POINTER(C.c_double)))
+        return rc, T, pose
+
+    return fetch
+
+
+CHAIN_OPT = dict(seed=77, n_bases=12, max_attempts=20, max_per_base=10, eps=0.005)
+
+
+def test_chain_best_pose_without_pose(rec1):
+    s, Q, seg, vis, truth, diam = rec1
+    check_optional_outputs(s, "v4pcs", diam, dict(CHAIN_OPT, per_base_cap=64))
+
+
+def test_chain_keeps_its_own_buffers(rec1):
+    """The fits of a pgp_congruent_batch_fit_score stay resident (and unchanged) across a chain call: the chain stages in
+    d_v4_io and touches neither the fits nor the quad batch they came from."""
+    s, Q, seg, vis, truth, diam = rec1
+    fetch = resident_fits(s, seg, diam)
+    rc, T, pose = fetch()
+    assert rc == 0
+    zero = np.zeros(3, np.float32)
+    assert len(s.v4pcs_hypotheses(diam, zero, zero, per_base_cap=64, **CHAIN_OPT)["T"]) > 12
+    rc2, T2, pose2 = fetch()
+    assert rc2 == 0 and T2.tobytes() == T.tobytes() and pose2.tobytes() == pose.tobytes()
+
+
 def test_chain_best_is_the_lowest_index_of_the_maximum():
     """A scene and model that are the same regular lattice: many hypotheses register every point and tie at the top."""
     Q = lattice(3, 0.05)
