@@ -153,32 +153,15 @@ struct IcpArgs {
   unsigned* x_ctr;               // [n] arrivals of the pose's workgroups (monotone; zeroed before the launch)
   unsigned* x_ticks;             // [2][n][4] search time of every share, published with it
   unsigned solo_ticks;           // every share searched faster than this: the pose goes on in ONE workgroup
-  int slot_budget;               // A/B knob (PGP_ICP_SLOTS): lane slots up to which queries get more lanes; 0 = one pass
-  int rows_mode;                 // A/B knob (PGP_ICP_ROWS): phase B's lanes dealt by rows -- 0: where it pays (default), 1: always, 2: never
   // vicinity graph of the target (nnidx_vic_*): per image position the kVicK nearest other target points and a
   // radius inside which no unlisted point lies -- resolves a query next to a known candidate without a search
   const uint4* nn_vic;           // [n_tgt] or nullptr
   int first_walk;                // moves downhill on the graph in the FIRST iteration (no previous correspondence yet)
-  // lost passes (the helping launch, PGP_ICP_HELP): a workgroup sets *x_lost; the follow-up launch (run_if = x_lost, one
-  // workgroup per pose, starting again from the transforms saved in T_save) repairs the call.  (The clustered launch
-  // repairs a lost meeting inside itself: workgroup 0 of the pose goes on alone.)
-  unsigned* x_lost;              // [1] in the library's own workspace
+  // lost meetings: the clustered launch repairs them inside itself -- workgroup 0 of the pose goes on alone
   unsigned* x_done;              // [n] workgroups of the pose that have left: the last one zeroes the pose's counters for the next call
   unsigned* x_abandon;           // [n] set by the first workgroup whose wait for a meeting ran out: the partners leave at once
   unsigned wait_ticks;           // floor of every wait's clock bound (100 MHz ticks; launch_icp: 3 ms, PGP_ICP_WAIT_MS)
   int force_lost;                // test knob (PGP_ICP_FORCE_LOST): every pose's first meeting is declared lost
-  float* T_save;                 // [n][16]: clustered launch: part 0 stores the pose's initial transform here
-  const float* T_in;             // where a pose's initial transform is read (T itself, or T_save in the repair launch)
-  const unsigned* run_if;        // non-null: the whole launch returns at once unless *run_if != 0
-  // helping (icp_persist_help: one workgroup per pose, all resident): a workgroup whose pose has finished takes
-  // search passes of poses that are still running -- see HelpPub
-  unsigned char* help;           // the poses' publication blocks, help_stride bytes each
-  size_t help_stride;
-  unsigned long long* help_ctl;  // [n] (iteration tag << 32) | next unclaimed slot; tag 0 = nothing to take
-  unsigned* help_nslots;         // [n] slots of the published iteration
-  unsigned* help_done;           // [n] passes completed
-  unsigned* help_finished;       // [1] poses that are through all their iterations
-  int dbg_pose;                  // diagnostic builds (PGP_ICP_STAMPS): the pose whose phases are timed (PGP_ICP_DBG_POSE)
 };
 
 __device__ __forceinline__ float row_xf(float a, float b, float c, float t, float x, float y, float z) {
@@ -251,7 +234,7 @@ __device__ void largest_eigvec4(double (&A)[4][4], double q[4]) {
 // the Gershgorin bound descends monotonically onto that root (Horn 1987 section 4; Theobald 2005), and
 // every non-zero column of adj(N - l I) is the eigenvector.  ~400 f64 operations against ~50 Jacobi
 // rotations of four divisions / square roots each: 27 us -> 2 us of ONE lane per ICP iteration
-// (tools/icp_phases.py).  Returns false -- the caller falls back to the Jacobi sweeps -- when the largest
+// (DESIGN.md).  Returns false -- the caller falls back to the Jacobi sweeps -- when the largest
 // eigenvalue is (nearly) double: the adjugate then vanishes and the rotation is not unique.
 __device__ __forceinline__ double det3(double a, double b, double c, double d, double e, double f, double g, double h,
                                        double i) {
@@ -1240,13 +1223,7 @@ struct SceneArgs {
   int n_upd;                  // workgroups 0 .. n_upd-1 are updaters (pose p: updater p % n_upd), the rest workers
   int force_lost;             // test knob (PGP_ICP_FORCE_LOST): every pose's first wait for its units counts as run out
   unsigned wait_ticks;        // floor of every wait's clock bound (100 MHz ticks; 3 ms, PGP_ICP_WAIT_MS)
-  unsigned long long* dbg;    // PGP_SCENE_STAMPS builds: [64 iterations][16] clock stamps (100 MHz) of updater 0 and of three workers
 };
-#ifdef PGP_SCENE_STAMPS
-#define SCENE_STAMP(slot) do { if (it < 64) z.dbg[it * 16 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SCENE_STAMP(slot) do { } while (0)
-#endif
 constexpr int kSceneThreads = 256;
 constexpr int kSceneLanes = 8;                         // lanes per query (grid_nn27_flat)
 constexpr int kSceneQ = kSceneThreads / kSceneLanes;   // queries per chunk: 32
@@ -1322,7 +1299,6 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
           __syncthreads();   // (every wave reads the state word at the top of the next pass)
           continue;
         }
-        if (tid == 0 && pose == 0) SCENE_STAMP(0);   // every unit has arrived
         if (tid < 16) s_G[tid] = agent_load(&a.T[16 * (size_t)pose + tid]);
         // ---- the pose's sums: icp_sums_partial adds its 16 waves in order from 0.0, icp_refine<true, true> the blocks in
         // order from 0.0.  Eight blocks per pass: lane k + 32 (b & 1) of wave b / 2 adds the sixteen wave sums of block b
@@ -1347,14 +1323,12 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
         __syncthreads();
         // ---- closed-form update and the progress tests (icp_refine's, thread 0's)
         int go_i = 0;
-        if (tid == 0 && pose == 0) SCENE_STAMP(1);   // sums added
         if (tid == 0) {
           const double* red = s_sum;
           const double E = red[0] >= 1.0 ? red[kRedPlane] / red[0] : 0.0;
           for (int q = 0; q < 16; ++q) s_G_old[q] = s_G[q];
           if constexpr (METRIC == 1) solve_plane(red, s_G);
           else solve_rigid(red, s_G);
-          if (pose == 0) SCENE_STAMP(2);   // solved
           const double E_old = it == 0 ? (double)FLT_MAX : z.E_old[pose];   // PCL: energy starts at numeric_limits<float>::max()
           bool go = it + 1 < a.max_iter;
           if (a.ratio > 0.f && !(E / E_old < (double)a.ratio)) go = false;
@@ -1375,7 +1349,6 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
         // every copy of the state word by ONE store instruction, a line each
         if (tid < kSceneRep)
           agent_store(&z.state[((size_t)pose * kSceneRep + tid) * kSceneRepStride], (unsigned)(it + 1) | (go_i ? 0u : 0x80000000u));
-        if (tid == 0 && pose == 0) SCENE_STAMP(3);   // published
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();   // (every wave reads the state word at the top of the next pass)
       }
@@ -1421,11 +1394,6 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
       }
       __syncthreads();
       const bool pose_done = s_flag[0] != 0;
-#ifdef PGP_SCENE_STAMPS
-      const int dslot = me == 0 ? (item == me ? 4 : 8) : -1;
-      if (tid == 0 && dslot >= 0) SCENE_STAMP(dslot);       // the state word said go
-      if (tid == 0 && it == 10 && me < 2048) z.dbg[1024 + me] = __builtin_amdgcn_s_memrealtime();   // every worker's go
-#endif
       if (!pose_done && tid < 16) s_G[tid] = agent_load(&a.T[16 * (size_t)pose + tid]);
       __syncthreads();   // (also: everybody has read s_flag[0] before thread 0 writes it again)
       if (pose_done) continue;
@@ -1444,10 +1412,6 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's keys have left ...
       __syncthreads();                                    // ... and so have every wave's, before the chunk's ticket
-#ifdef PGP_SCENE_STAMPS
-      if (tid == 0 && dslot >= 0) SCENE_STAMP(dslot + 1);   // searched, keys out
-      if (tid == 0 && it == 10 && me < 2048) z.dbg[1024 + 2048 + me] = __builtin_amdgcn_s_memrealtime();   // every worker's chunk searched
-#endif
       const int u = chunk / kSceneCpu;
       if (tid == 0) {
         const unsigned per = (unsigned)min(kSceneCpu, z.n_chunks - kSceneCpu * u);
@@ -1455,11 +1419,6 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
         s_flag[1] = old + 1u == per * (unsigned)(it + 1) ? 1 : 0;
       }
       __syncthreads();
-#ifdef PGP_SCENE_STAMPS
-      if (tid == 0 && dslot >= 0) SCENE_STAMP(dslot + 2);   // ticket drawn
-#endif
-#ifdef PGP_SCENE_STAMPS
-#endif
       if (!s_flag[1] || wave != 0) continue;   // (the other waves wait at the next item's barrier while wave 0 closes the unit)
       // ---- 2. the unit's sums: lane l holds the points 256 u + 4 l .. + 3, as thread 64 w + l of icp_sums_partial does
       const int b0 = 256 * u;
@@ -1525,13 +1484,8 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
         for (int k = 0; k < kNs; ++k) mine = lane == k ? acc[k] : mine;
         if (lane <= kRedPlane) agent_store(&Wu[lane], mine);
       }
-#ifdef PGP_SCENE_STAMPS
-#endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the unit's sums have left before its arrival is counted
       if (lane == 0) __hip_atomic_fetch_add(&z.pose_ctr[pose], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef PGP_SCENE_STAMPS
-      if (lane == 0 && it < 64) atomicMax(&z.dbg[it * 16 + 12], __builtin_amdgcn_s_memrealtime());   // the LAST unit closed (any worker)
-#endif
     }
     if (!any) break;
   }
@@ -1702,9 +1656,6 @@ struct NnLds {
   uint16_t* pos;      // its position in the image (0xFFFF: none)
   uint16_t* order;    // the queries sorted by estimated search cost (dearest first), then by where they fall
   uint32_t* bins;     // kNnBins 16-bit counters / offsets of that sort, two per word
-#ifdef PGP_ICP_STAMPS
-  unsigned* dbg;      // diagnostic build: rows / live rows / points / lane slots / queries
-#endif
 };
 constexpr int kNnClasses = 16;
 constexpr int kNnStrips = 512 / kPS;                 // runs of neighbouring cells a class is subdivided into (8 counters per thread, 16 classes)
@@ -1748,12 +1699,11 @@ __device__ __forceinline__ NnBox nn_box(const NnGeom& g, float x, float y, float
 
 // Phase A helpers.  nn_class: the cost class (0 cheapest .. 14) of the row search that starts from the bound d2.
 __device__ __forceinline__ int nn_cost(const NnBox& b) { return (b.y1 - b.y0 + 1) * (b.z1 - b.z0 + 1) * (((b.x1 - b.x0) >> 2) + 3); }
-// (round 5, tools/icp_lane_balance.py: the dearest lane of a wave-pass carries about twice the mean lane's work; ordering
+// (round 5, a stamped build: the dearest lane of a wave-pass carries about twice the mean lane's work; ordering
 // the queries of a class by the next two bits of their cost did not change that -- neighbouring queries' costs differ by
 // their ROW lengths, which the box cost does not see -- and timed equal or slower: profiles/r05_ab/icp_lane_balance.log)
-__device__ __forceinline__ int nn_class(const NnGeom& g, float x, float y, float z, float bound_d2, unsigned* rows = nullptr) {
+__device__ __forceinline__ int nn_class(const NnGeom& g, float x, float y, float z, float bound_d2) {
   const NnBox b = nn_box(g, x, y, z, bound_d2);
-  if (rows) *rows = (unsigned)((b.y1 - b.y0 + 1) * (b.z1 - b.z0 + 1));
   const int cost = nn_cost(b);   // rows x (row overhead + cells)
   const int c = 31 - __clz(cost);   // cost >= 3
   return c < kNnClasses - 2 ? c : kNnClasses - 2;
@@ -1800,18 +1750,13 @@ __device__ __forceinline__ bool nn_vic_check(const NnLds& t, const uint4 rec, fl
 // lane `sub` takes the rows sub, sub + L, ... of the search box (or, without a bound, every L-th target
 // point); the group's results are merged by the caller.  The row loop is the cost of a far query
 // (~(2U/h + 1)^2 pi/4 rows): everything in it works in CELL UNITS on values prepared once per query.
-// (returns the lane's work in instruction units -- ~45 per row, ~12 per point -- in PGP_ICP_STAMPS builds, 0 otherwise)
-// box_d2 >= 0: the box is cut for THAT squared distance (every lane of a query's group must enumerate the same rows, while
-// `best` may already hold a nearer point another lane found); scan_all: the query has no bound at all.
-__device__ __forceinline__ unsigned nn_search(const NnGeom& g, const NnLds& t, int n_tgt, float x, float y, float z,
-                                              int sub, int L, unsigned long long& best, int& bpos, float box_d2 = -1.f,
-                                              bool scan_all = false) {
-  if (box_d2 < 0.f ? bpos < 0 : scan_all) {
+__device__ __forceinline__ void nn_search(const NnGeom& g, const NnLds& t, int n_tgt, float x, float y, float z,
+                                          int sub, int L, unsigned long long& best, int& bpos) {
+  if (bpos < 0) {
     for (int k = sub; k < n_tgt; k += L) nn_consider(x, y, z, t.pts[k], k, best, bpos);
-    return 0u;
+    return;
   }
-  const float bound = box_d2 < 0.f ? __uint_as_float((unsigned)(best >> 32)) : box_d2;
-  const NnBox b = nn_box(g, x, y, z, bound);
+  const NnBox b = nn_box(g, x, y, z, __uint_as_float((unsigned)(best >> 32)));
   const float mag = fabsf(x) + fabsf(y) + fabsf(z) + fabsf(g.ox) + fabsf(g.oy) + fabsf(g.oz);
   // query in cell units relative to the grid origin; a cell c spans [c, c + 1].  Slack of the row tests:
   // 1e-4 cell for the float cell boundaries (values <= 2^7 cells carry <= 2^-16 cell of rounding)
@@ -1826,15 +1771,9 @@ __device__ __forceinline__ unsigned nn_search(const NnGeom& g, const NnLds& t, i
   int iz = sub / nyb;
   int cz = b.z0 + iz, cy = b.y0 + (sub - iz * nyb);
   const int step_z = L / nyb, step_y = L - step_z * nyb;
-#ifdef PGP_ICP_STAMPS
-  unsigned dbg_rows = 0, dbg_live = 0, dbg_pts = 0;
-#endif
   // (round 5: the same loop one row ahead -- the next row's chord cut with the bound before this row's points, its two `start`
   // reads in flight beside this row's point reads -- timed equal on every row of tools/icp_quick.py: profiles/r05_ab/icp_lane_balance.log)
   while (cz <= b.z1) {
-#ifdef PGP_ICP_STAMPS
-    ++dbg_rows;
-#endif
     // distance (cells) from the query to the row's (y, z) square: max(|f - (c + 1/2)| - 1/2 - slack, 0)
     const float gy = fmaxf(fabsf(fy - ((float)cy + 0.5f)) - (0.5f + slack), 0.f);
     const float gz = fmaxf(fabsf(fz - ((float)cz + 0.5f)) - (0.5f + slack), 0.f);
@@ -1850,10 +1789,6 @@ __device__ __forceinline__ unsigned nn_search(const NnGeom& g, const NnLds& t, i
       if (x0 <= x1) {
         const int row = (cz * g.ny + cy) * g.nx;
         const int kb = t.start[row + x0], ke = t.start[row + x1 + 1];
-#ifdef PGP_ICP_STAMPS
-        ++dbg_live;
-        dbg_pts += ke - kb;
-#endif
         for (int k = kb; k < ke; k += 4) {   // four LDS reads in flight; the last point of a short run counts again
           const int k1 = min(k + 1, ke - 1), k2 = min(k + 2, ke - 1), k3 = min(k + 3, ke - 1);
           const float4 m0 = t.pts[k], m1 = t.pts[k1], m2 = t.pts[k2], m3 = t.pts[k3];
@@ -1871,20 +1806,6 @@ __device__ __forceinline__ unsigned nn_search(const NnGeom& g, const NnLds& t, i
       ++cz;
     }
   }
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 2
-  if (t.dbg) {
-    atomicAdd(&t.dbg[0], dbg_rows);
-    atomicAdd(&t.dbg[1], dbg_live);
-    atomicAdd(&t.dbg[2], dbg_pts);
-    atomicAdd(&t.dbg[3], 1u);
-    if (sub == 0) atomicAdd(&t.dbg[4], 1u);
-  }
-#endif
-#ifdef PGP_ICP_STAMPS
-  return 45u * dbg_rows + 12u * dbg_pts;
-#else
-  return 0u;
-#endif
 }
 
 // LDS layout of a workgroup that answers up to n_q_cap queries: [image |] d2[n_q_cap] | pos[n_q_cap] | order[n_q_cap] | bins.
@@ -1912,9 +1833,6 @@ __device__ __forceinline__ NnLds nn_load_image(const IcpArgs& a, unsigned char* 
   t.pos = reinterpret_cast<uint16_t*>(t.d2 + n_q_cap);
   t.order = t.pos + n_q_cap;
   t.bins = reinterpret_cast<uint32_t*>(smem + ((base + 8 * (size_t)n_q_cap + 15) & ~(size_t)15));
-#ifdef PGP_ICP_STAMPS
-  t.dbg = nullptr;
-#endif
   return t;
 }
 __host__ __device__ inline size_t nn_lds_bytes(uint32_t image_bytes, int n_q, bool image_in_lds = true) {
@@ -1939,9 +1857,6 @@ __device__ __forceinline__ int nn_class_lanes_log2(int c, int base = kNnBaseClas
   return l < 0 ? 0 : (l > 6 ? 6 : l);
 }
 constexpr int kNnFew = 64;        // up to this many unanswered queries skip the sort: 16 lanes each, one pass
-#ifndef PGP_NN_ROWS
-#define PGP_NN_ROWS 0             // phase B's lanes dealt by exact row counts instead of cost classes: 0 nowhere (default), 1 in the kernels with
-#endif                            // several workgroups per pose, 2 everywhere.  Built, same bits, measured: profiles/r05_ab/icp_rows_dealt.log
 struct NnSched {
   unsigned cnt[kNnClasses + 1];    // offset of every class in `order` (dearest class first); [kNnClasses] = n_q
   unsigned slot_end[kNnClasses];   // end of the class's lane slots
@@ -1949,110 +1864,9 @@ struct NnSched {
   unsigned wave_sum[16];
   unsigned search_ticks;           // time of the search loop below as thread 0 saw it (100 MHz ticks)
   unsigned n_unres;                // queries the vicinity graph did not answer: phase B's population
-  unsigned all_rows, max_rows;     // rows of their search boxes, summed / the largest box beyond 2048 rows (PGP_NN_ROWS)
   uint16_t few[kNnFew];            // the first of them, in arrival order: the short path of phase B
-  unsigned help_s0[2];             // helping: the pass this workgroup has claimed (ping-pong across turns)
-  unsigned help_avail;             // helping: some workgroup of the launch is through with its pose
   int base;                        // classes above it get 2^(class - base) lanes (kNnBaseClass, lower when lanes would idle)
 };
-// ---- helping: search passes of a slow pose taken by workgroups whose own pose has finished -----------------------
-// With one workgroup per pose a launch lasts as long as its slowest pose (256 poses from up to 6 cm off: 240 .. 1050 us,
-// mean 680: a third of the chip's time idle).  What makes a pose slow is its search -- 2000 queries still far from
-// the surface, three passes of 1024 lane slots at ~20 us each -- and the passes of one iteration are independent.
-// So the owner of such an iteration PUBLISHES it in HBM (the sorted slot table, the queries' bounds, the pose) and
-// takes passes off a counter; a workgroup that is through with its own pose polls the counters of the others and
-// takes passes too: it holds the same target image in LDS and needs nothing else.  Results come back through HBM,
-// the owner waits for the passes it did not run itself.  The answer of a query does not depend on who searched
-// for it (exact nearest neighbour), so results are the bits of the unhelped kernel.
-//   ctl[p] = (tag << 32) | next unclaimed slot, tag = iteration + 1 while open, 0 when closed: a helper claims a pass
-//   by compare-and-swap on the whole word, so a pass of iteration k + 1 is never taken with the tables of iteration k;
-//   done[p] counts completed passes.  Nobody waits for anybody except the owner for passes that were CLAIMED, and a
-//   claimed pass is always finished: no cycle of waits; every spin is bounded by a clock all the same (a lost pass
-//   sets the lost flag and the repair launch behind the helping launch redoes the call).
-struct HelpPub {                     // one per pose, in HBM (write-through stores, agent-scope loads)
-  unsigned n_unres, base, pad0, pad1;
-  unsigned cnt[kNnClasses + 1];
-  unsigned slot_end[kNnClasses];
-  float G[16];
-  // followed by: order[n_src] (u32) | bound[n_src] (u64, by query) | result[n_src] (u64, by query)
-};
-__host__ __device__ inline size_t help_off_order() { return (sizeof(HelpPub) + 255) & ~(size_t)255; }
-__host__ __device__ inline size_t help_off_bound(int n_src) { return help_off_order() + (((size_t)n_src * 4 + 255) & ~(size_t)255); }
-__host__ __device__ inline size_t help_off_result(int n_src) { return help_off_bound(n_src) + (((size_t)n_src * 8 + 255) & ~(size_t)255); }
-__host__ __device__ inline size_t help_bytes(int n_src) { return help_off_result(n_src) + (((size_t)n_src * 8 + 255) & ~(size_t)255); }
-
-template <class V>
-__device__ __forceinline__ void st_agent(V* p, V v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class V>
-__device__ __forceinline__ V ld_agent(const V* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ONE pass of 1024 lane slots.  tab: the slot table in LDS (the owner's own, or a helper's copy); from_pub: the
-// queries' order and bounds are read from the publication (a helper) instead of this workgroup's LDS arrays (the
-// owner); to_pub: the results go to the publication (a published iteration) instead of the LDS arrays (an owner's
-// unpublished single pass).  ONE instance per kernel: the search it inlines is the bulk of the kernel's code.
-template <int NT>
-__device__ __forceinline__ void help_pass(const IcpArgs& a, const NnLds& t, const NnSched* tab, const float* G, unsigned char* pub,
-                                          unsigned s0, unsigned n_slots, int tid, bool from_pub, bool to_pub) {
-  const float g00 = G[0], g10 = G[1], g20 = G[2], g01 = G[4], g11 = G[5], g21 = G[6], g02 = G[8], g12 = G[9],
-              g22 = G[10], g03 = G[12], g13 = G[13], g23 = G[14];
-  const unsigned* p_order = reinterpret_cast<const unsigned*>(pub + help_off_order());
-  const unsigned long long* p_bound = reinterpret_cast<const unsigned long long*>(pub + help_off_bound(a.n_src));
-  unsigned long long* p_result = reinterpret_cast<unsigned long long*>(pub + help_off_result(a.n_src));
-  const unsigned sl = s0 + (unsigned)tid;
-  const bool valid = sl < n_slots;
-  unsigned long long best = kNnNone;
-  int bpos = -1, q = 0, lg = 0, sub = 0;
-  if (valid) {
-    int c = kNnClasses - 1;
-    while (sl >= tab->slot_end[c]) --c;
-    lg = nn_class_lanes_log2(c, tab->base);
-    const unsigned first = c == kNnClasses - 1 ? 0u : tab->slot_end[c + 1];
-    const unsigned rel = sl - first;
-    sub = (int)(rel & ((1u << lg) - 1u));
-    const unsigned at = tab->cnt[c] + (rel >> lg);
-    q = !from_pub ? (int)t.order[at] : (int)ld_agent(&p_order[at]);
-    const float4 s = a.src[q];
-    const float x = row_xf(g00, g01, g02, g03, s.x, s.y, s.z), y = row_xf(g10, g11, g12, g13, s.x, s.y, s.z),
-                z = row_xf(g20, g21, g22, g23, s.x, s.y, s.z);
-    unsigned pp, d2b;
-    if (!from_pub) {
-      pp = t.pos[q];
-      d2b = __float_as_uint(t.d2[q]);
-    } else {
-      const unsigned long long b = ld_agent(&p_bound[q]);
-      pp = (unsigned)(b & 0xFFFFull);
-      d2b = (unsigned)(b >> 32);
-    }
-    bpos = pp == 0xFFFFu ? -1 : (int)pp;
-    if (bpos >= 0) best = ((unsigned long long)d2b << 32) | (unsigned)__float_as_int(t.pts[bpos].w);
-    nn_search(a.nn, t, a.n_tgt, x, y, z, sub, 1 << lg, best, bpos);
-  }
-  const bool b0 = __ballot(lg >= 1) != 0ull, b1 = __ballot(lg >= 2) != 0ull, b2 = __ballot(lg >= 3) != 0ull,
-             b3 = __ballot(lg >= 4) != 0ull, b4 = __ballot(lg >= 5) != 0ull, b5 = __ballot(lg >= 6) != 0ull;
-  const bool need[6] = {b0, b1, b2, b3, b4, b5};
-#pragma unroll
-  for (int st = 0; st < 6; ++st) {
-    if (!need[st]) break;   // wave-uniform
-    const int off = 1 << st;
-    const unsigned lo = __shfl_xor((unsigned)best, off, 64), hi = __shfl_xor((unsigned)(best >> 32), off, 64);
-    const int pp = __shfl_xor(bpos, off, 64);
-    const unsigned long long pk = ((unsigned long long)hi << 32) | lo;
-    if (off < (1 << lg) && pk < best) {
-      best = pk;
-      bpos = pp;
-    }
-  }
-  if (valid && sub == 0) {
-    if (to_pub) {   // {d2 bits, position}: what the owner copies into its LDS arrays after the last pass
-      st_agent(&p_result[q], ((unsigned long long)(bpos < 0 ? 0x7F7FFFFFu : (unsigned)(best >> 32)) << 32) |
-                                 (unsigned long long)(bpos < 0 ? 0xFFFFu : (unsigned)bpos));
-    } else {
-      t.d2[q] = bpos < 0 ? FLT_MAX : __uint_as_float((unsigned)(best >> 32));
-      t.pos[q] = (uint16_t)(bpos < 0 ? 0xFFFF : bpos);
-    }
-  }
-}
-
 // The caller may hand over a SHARE of the queries (several workgroups per pose): the cloud is dealt in blocks of
 // eight consecutive queries, block k to workgroup k % P -- eight 8-byte meeting records are one 64-byte line, so a
 // line of the meeting buffer is written by ONE workgroup (interleaving single queries made every 8-byte store a
@@ -2070,29 +1884,18 @@ __host__ __device__ __forceinline__ int nn_share_count(int n, int part, int P) {
 }
 __host__ __device__ __forceinline__ bool nn_share_owns(int q, int part, int P) { return P == 1 || ((q >> 3) % P) == part; }
 
-template <int NT, int R, bool HELP = false, bool ROWS = false>
+template <int NT, int R>
 __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t, const float* G, int q_base, int n_q,
-                                               NnSched* sch /* LDS */, int tid, int part = 0, int P = 1, int help_pose = 0,
-                                               unsigned help_tag = 0, int* lost = nullptr, int first_walk = 0) {
+                                               NnSched* sch /* LDS */, int tid, int part = 0, int P = 1, int first_walk = 0) {
   const float g00 = G[0], g10 = G[1], g20 = G[2], g01 = G[4], g11 = G[5], g21 = G[6], g02 = G[8], g12 = G[9],
               g22 = G[10], g03 = G[12], g13 = G[13], g23 = G[14];
   static_assert(kNnBins / 2 == 4 * NT, "four counter words per thread");
   {   // zero the sort's counters
     uint4* b4 = reinterpret_cast<uint4*>(t.bins);
     b4[tid] = make_uint4(0u, 0u, 0u, 0u);
-    if (tid == 0) {
-      sch->n_unres = 0;
-      sch->all_rows = 0;
-      sch->max_rows = 0;
-    }
+    if (tid == 0) sch->n_unres = 0;
   }
   __syncthreads();
-#ifdef PGP_ICP_STAMPS
-  unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
-#define PGP_NN_STAMP(k) do { if (tid == 0 && t.dbg) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); t.dbg[k] += (unsigned)(now - st0); st0 = now; } } while (0)
-#else
-#define PGP_NN_STAMP(k) do { } while (0)
-#endif
   // Phase A: every query is bounded -- and, next to a known candidate, ANSWERED -- on the vicinity graph
   // (nn_vic_check).  The unanswered ones are filed for phase B under
   // sort key = (15 - class) * 512 + strip: dearest class first (the lane groups of phase B need whole classes in
@@ -2173,7 +1976,6 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
   for (int r = 0; r < R; ++r) {
     tag[r] = kNoTag;
     bool unres = false;
-    unsigned q_rows = 0;
     const int q = nn_share_query(r * NT + tid, part, P);
     if (live[r]) {
       const bool proven = vic && bpos[r] >= 0 && nn_vic_check(t, rec[r], qx[r], qy[r], qz[r], best[r], bpos[r]);
@@ -2182,8 +1984,7 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
       if (!proven) {
         unres = true;
         // no candidate at all (a non-finite or astronomically far query): the plain scan, class 15
-        q_rows = ((unsigned)a.n_tgt + 63u) >> 6;
-        const int c = bpos[r] < 0 ? kNnClasses - 1 : nn_class(a.nn, qx[r], qy[r], qz[r], __uint_as_float((unsigned)(best[r] >> 32)), &q_rows);
+        const int c = bpos[r] < 0 ? kNnClasses - 1 : nn_class(a.nn, qx[r], qy[r], qz[r], __uint_as_float((unsigned)(best[r] >> 32)));
         const int cell = nn_cell_of(a.nn, qx[r], qy[r], qz[r]);
         const unsigned key = (unsigned)(kNnClasses - 1 - c) * kNnStrips + (unsigned)min(cell >> strip_shift, kNnStrips - 1);
         const unsigned old = atomicAdd(&t.bins[key >> 1], (key & 1u) ? 0x10000u : 1u);
@@ -2198,41 +1999,16 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
       base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
       const unsigned slot = base + (unsigned)__popcll(um & ((1ull << (tid & 63)) - 1ull));
       if (unres && slot < (unsigned)kNnFew) sch->few[slot] = (uint16_t)q;
-      if (ROWS) {   // the rows of the boxes (a lane's share of phase B): one add per wave and sweep
-        const unsigned incl = wave_scan_incl_u32(unres ? q_rows : 0u);
-        if ((tid & 63) == 63) atomicAdd(&sch->all_rows, incl);
-      }
     }
   }
   __syncthreads();
-  PGP_NN_STAMP(5);
   const unsigned n_unres = sch->n_unres;
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 1
-  if (tid == 0 && t.dbg) t.dbg[3] += n_unres;   // queries the graph left to the search, summed over the iterations
-#endif
   if (n_unres == 0) {   // every query answered on the graph (the usual iteration of a converged pose)
     if (tid == 0) sch->search_ticks = 0;
     __syncthreads();    // n_unres is zeroed by the next call: everybody has read it
     return;
   }
-  if (HELP && NT == 16 * kNnFew && n_unres <= (unsigned)kNnFew) {
-    // (the helping kernel keeps ONE inlined copy of the search: the handful goes through help_pass as one class of
-    //  16-lane groups -- class 15 with base 11)
-    if (tid < kNnClasses) {
-      sch->cnt[tid] = 0;
-      sch->slot_end[tid] = tid == kNnClasses - 1 ? 16u * n_unres : 16u * n_unres;
-    }
-    if (tid == 0) {
-      sch->base = kNnClasses - 1 - 4;
-      sch->search_ticks = 1;
-    }
-    if ((unsigned)tid < n_unres) t.order[tid] = sch->few[tid];
-    __syncthreads();
-    help_pass<NT>(a, t, sch, G, nullptr, 0u, 16u * n_unres, tid, false, false);
-    __syncthreads();
-    return;
-  }
-  if (!HELP && NT == 16 * kNnFew && n_unres <= (unsigned)kNnFew) {
+  if (NT == 16 * kNnFew && n_unres <= (unsigned)kNnFew) {
     // A handful of stragglers (the graph answers all but ~30 of 1800 queries of a pose that is millimetres off):
     // no sort, no slot table -- query i takes lanes 16 i .. 16 i + 15, which share its rows; one pass, one barrier.
     const int grp = tid >> 4, sub = tid & 15;
@@ -2311,13 +2087,12 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
     unsigned total = count_slots(base);
     while (base > 0) {
       const unsigned wider = count_slots(base - 1);
-      if (wider > (unsigned)(a.slot_budget > 0 ? a.slot_budget : NT)) break;
+      if (wider > (unsigned)NT) break;
       --base;
       total = wider;
     }
     sch->n_slots = total;
     sch->base = base;
-    if (HELP) sch->help_avail = ld_agent(a.help_finished);   // nobody idle yet: nothing is published (no overhead)
     unsigned slots = 0;
 #pragma unroll
     for (int c = kNnClasses - 1; c >= 0; --c) {
@@ -2335,197 +2110,7 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
     }
   }
   __syncthreads();
-  PGP_NN_STAMP(6);
   const unsigned n_slots = sch->n_slots;
-  if (HELP && n_slots > (unsigned)NT && sch->help_avail != 0u) {
-    // ---- more than one pass: published, so that idle workgroups can take passes (see HelpPub)
-    unsigned char* pub = a.help + (size_t)help_pose * a.help_stride;
-    HelpPub* hp = reinterpret_cast<HelpPub*>(pub);
-    unsigned* p_order = reinterpret_cast<unsigned*>(pub + help_off_order());
-    unsigned long long* p_bound = reinterpret_cast<unsigned long long*>(pub + help_off_bound(a.n_src));
-    const unsigned long long* p_result = reinterpret_cast<const unsigned long long*>(pub + help_off_result(a.n_src));
-    for (unsigned i = (unsigned)tid; i < n_unres; i += NT) {
-      const unsigned q = t.order[i];
-      st_agent(&p_order[i], q);
-      st_agent(&p_bound[q], ((unsigned long long)__float_as_uint(t.d2[q]) << 32) | (unsigned long long)t.pos[q]);
-    }
-    if (tid < kNnClasses) {
-      st_agent(&hp->cnt[tid], sch->cnt[tid]);
-      st_agent(&hp->slot_end[tid], sch->slot_end[tid]);
-    }
-    if (tid < 16) st_agent(&hp->G[tid], G[tid]);
-    if (tid == 0) {
-      st_agent(&hp->base, (unsigned)sch->base);
-      st_agent(&hp->n_unres, n_unres);
-      st_agent(&a.help_nslots[help_pose], n_slots);
-      st_agent(&a.help_done[help_pose], 0u);
-    }
-    __builtin_amdgcn_s_waitcnt(0);   // everything above has left before the counter opens
-    __syncthreads();
-    if (tid == 0) {
-      st_agent(&a.help_ctl[help_pose], (unsigned long long)help_tag << 32);
-      __builtin_amdgcn_s_waitcnt(0);
-    }
-    const unsigned long long search_t0 = __builtin_amdgcn_s_memrealtime();
-    for (int turn = 0;; ++turn) {
-      if (tid == 0)
-        sch->help_s0[turn & 1] = (unsigned)(__hip_atomic_fetch_add(&a.help_ctl[help_pose], (unsigned long long)NT, __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_AGENT) & 0xFFFFFFFFull);
-      __syncthreads();
-      const unsigned s0 = sch->help_s0[turn & 1];
-      if (s0 >= n_slots) break;
-      help_pass<NT>(a, t, sch, G, pub, s0, n_slots, tid, false, true);
-      __builtin_amdgcn_s_waitcnt(0);   // this pass's results have left
-      __syncthreads();
-      if (tid == 0) __hip_atomic_fetch_add(&a.help_done[help_pose], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (tid == 0) {   // the passes others took: wait for them (claimed passes are always finished)
-      const unsigned n_passes = (n_slots + NT - 1) / NT;
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      while (ld_agent(&a.help_done[help_pose]) < n_passes) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__builtin_amdgcn_s_memrealtime() - t0 > max(200000ull, 4ull * (unsigned long long)a.wait_ticks)) {   // (claimed passes are being worked on by RUNNING workgroups)
-          if (lost) *lost = 1;
-          break;
-        }
-      }
-      st_agent(&a.help_ctl[help_pose], 0ull);   // closed
-      sch->search_ticks = (unsigned)(__builtin_amdgcn_s_memrealtime() - search_t0);
-    }
-    __syncthreads();
-    for (unsigned i = (unsigned)tid; i < n_unres; i += NT) {
-      const unsigned q = t.order[i];
-      const unsigned long long v = ld_agent(&p_result[q]);
-      t.d2[q] = __uint_as_float((unsigned)(v >> 32));
-      t.pos[q] = (uint16_t)(v & 0xFFFFull);
-    }
-    __syncthreads();
-    return;
-  }
-  if (HELP) {   // a single pass, or nobody there to help: this workgroup's own passes, results straight into LDS
-    for (unsigned s0 = 0; s0 < n_slots; s0 += NT) help_pass<NT>(a, t, sch, G, nullptr, s0, n_slots, tid, false, false);
-    if (tid == 0) sch->search_ticks = 1;
-    __syncthreads();
-    return;
-  }
-  if (ROWS && !HELP && a.rows_mode != 2) {
-    // ---- phase B, lanes dealt by ROWS (round 5).  The class scheme above gives a query 2^k lanes from the log2 of its box
-    // cost: per-lane work then spreads over a factor of two inside a class alone, and tools/icp_lane_balance.py measured
-    // the dearest lane of a wave-pass at 1.85 - 2.3 x the mean.  Here the rows of the queries' boxes are counted exactly,
-    // `per` = ceil(all rows / NT) rows is a lane's share, query j gets L_j = ceil(rows_j / per) consecutive lane slots
-    // (any number, in the sort's dearest-first order) and lane `sub` of the group takes its rows sub, sub + L_j, ... --
-    // at most `per` of them.  The lanes of a group need not sit in one wave: their results meet in a 64-bit minimum in
-    // LDS, key = d2 | original index (16 bits: an indexed target has at most 65 535 points) | position, the same order as
-    // nn_consider's.  The sort's bins are free by now: keys (8 B) and slot prefixes (4 B) of up to NT queries per batch.
-    // Exact nearest neighbours either way: same bits as every other schedule.
-    static_assert((size_t)kNnBins * 2 >= (size_t)NT * 12, "keys + slot prefixes of a batch fit the sort's bins");
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(t.bins);
-    unsigned* slotpre = reinterpret_cast<unsigned*>(t.bins) + 2 * NT;
-    constexpr unsigned long long kNoKey = ((unsigned long long)0x7F7FFFFFu << 32) | 0xFFFFFFFFull;
-    const unsigned long long search_t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned per = max((sch->all_rows + (unsigned)NT - 1u) / (unsigned)NT, 1u);
-    for (unsigned b0 = 0; b0 < n_unres; b0 += NT) {
-      const unsigned nb = min((unsigned)NT, n_unres - b0);
-      unsigned rows = 0;
-      int q_mine = 0;
-      if ((unsigned)tid < nb) {
-        q_mine = t.order[b0 + tid];
-        const unsigned pp = t.pos[q_mine];
-        if (pp == 0xFFFFu) {   // no candidate at all: the plain scan, dealt in runs of 64 points
-          rows = ((unsigned)a.n_tgt + 63u) >> 6;
-          keys[tid] = kNoKey;
-        } else {
-          const float4 s = nn_src(a, t, q_base, q_mine);
-          const float x = row_xf(g00, g01, g02, g03, s.x, s.y, s.z), y = row_xf(g10, g11, g12, g13, s.x, s.y, s.z),
-                      z = row_xf(g20, g21, g22, g23, s.x, s.y, s.z);
-          const float d2 = t.d2[q_mine];
-          const NnBox bx = nn_box(a.nn, x, y, z, d2);
-          rows = (unsigned)((bx.y1 - bx.y0 + 1) * (bx.z1 - bx.z0 + 1));
-          keys[tid] = ((unsigned long long)__float_as_uint(d2) << 32) | ((unsigned long long)((unsigned)__float_as_int(t.pts[pp].w) & 0xFFFFu) << 16) |
-                      (unsigned long long)pp;
-        }
-      }
-      const unsigned lanes = rows ? (rows + per - 1u) / per : 0u;   // (all batches share one `per`: phase A summed every box)
-      {   // exclusive scan of the lane counts in the sort's order
-        const unsigned incl = wave_scan_incl_u32(lanes);
-        if ((tid & 63) == 63) sch->wave_sum[tid >> 6] = incl;
-        __syncthreads();
-        unsigned base = 0;
-        for (int wv = 0; wv < (tid >> 6); ++wv) base += sch->wave_sum[wv];
-        slotpre[tid] = base + incl - lanes;
-      }
-      unsigned n_slots = 0;
-      for (int wv = 0; wv < NT / 64; ++wv) n_slots += sch->wave_sum[wv];
-      __syncthreads();
-      for (unsigned s0 = 0; s0 < n_slots; s0 += NT) {
-        const unsigned sl = s0 + (unsigned)tid;
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-        unsigned lane_cost = 0;
-#endif
-        if (sl < n_slots) {
-          // the query of slot sl: the last j with slotpre[j] <= sl
-          unsigned j = 0;
-#pragma unroll
-          for (unsigned step = (unsigned)NT / 2; step; step >>= 1) {
-            const unsigned cand = j + step;
-            if (cand < nb && slotpre[cand] <= sl) j = cand;
-          }
-          const unsigned first = slotpre[j], L = (j + 1 < nb ? slotpre[j + 1] : n_slots) - first;
-          const int q = t.order[b0 + j];
-          const float4 s = nn_src(a, t, q_base, q);
-          const unsigned long long key = keys[j];
-          const float x = row_xf(g00, g01, g02, g03, s.x, s.y, s.z), y = row_xf(g10, g11, g12, g13, s.x, s.y, s.z),
-                      z = row_xf(g20, g21, g22, g23, s.x, s.y, s.z);
-          const bool scan_all = t.pos[q] == 0xFFFFu;
-          unsigned long long best = kNnNone;
-          int bpos = -1;
-          if ((key & 0xFFFFull) != 0xFFFFull) {
-            best = (key & 0xFFFFFFFF00000000ull) | ((key >> 16) & 0xFFFFull);
-            bpos = (int)(key & 0xFFFFull);
-          }
-          if (scan_all) {   // run `sub + k L` of 64 points
-            for (unsigned run = sl - first; run * 64u < (unsigned)a.n_tgt; run += L) {
-              const int k_end = min((int)(run * 64u) + 64, a.n_tgt);
-              for (int k = (int)(run * 64u); k < k_end; ++k) nn_consider(x, y, z, t.pts[k], k, best, bpos);
-            }
-          } else {
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-            lane_cost =
-#endif
-            nn_search(a.nn, t, a.n_tgt, x, y, z, (int)(sl - first), (int)L, best, bpos, t.d2[q], false);
-          }
-          if (bpos >= 0) {
-            const unsigned long long nk = (best & 0xFFFFFFFF00000000ull) | ((best & 0xFFFFull) << 16) | (unsigned long long)(unsigned)bpos;
-            if (nk < key) atomicMin(&keys[j], nk);
-          }
-        }
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-        {   // how well a wave's lanes are balanced (tools/icp_lane_balance.py)
-          unsigned mx = lane_cost, sm = lane_cost;
-          for (int off = 32; off >= 1; off >>= 1) {
-            mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
-            sm += (unsigned)__shfl_xor((int)sm, off, 64);
-          }
-          if ((tid & 63) == 0 && t.dbg && sm > 0) {
-            atomicAdd(&t.dbg[0], mx);
-            atomicAdd(&t.dbg[1], sm / 64u);
-            atomicAdd(&t.dbg[2], 1u);
-          }
-        }
-#endif
-      }
-      __syncthreads();
-      if ((unsigned)tid < nb) {
-        const unsigned long long k = keys[tid];
-        const unsigned pp = (unsigned)(k & 0xFFFFull);
-        t.d2[q_mine] = pp == 0xFFFFu ? FLT_MAX : __uint_as_float((unsigned)(k >> 32));
-        t.pos[q_mine] = (uint16_t)pp;
-      }
-      __syncthreads();   // keys and slot prefixes belong to the next batch (and, after the last, to the next sort)
-    }
-    if (tid == 0) sch->search_ticks = max((unsigned)(__builtin_amdgcn_s_memrealtime() - search_t0), 1u);
-    return;
-  }
   const int lane_base = sch->base;
   int c = kNnClasses - 1;   // class of the current slot: slots only grow
   // a slot's query and its source point (an L2 read behind an LDS read) are fetched one trip ahead
@@ -2544,17 +2129,11 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
   };
   fetch((unsigned)tid);
   const unsigned long long search_t0 = __builtin_amdgcn_s_memrealtime();
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 3
-  const unsigned long long wv0 = __builtin_amdgcn_s_memrealtime();
-#endif
   for (unsigned s0 = 0; s0 < n_slots; s0 += NT) {   // uniform trip count: the exchanges below need whole waves
     const unsigned sl = s0 + (unsigned)tid;
     const bool valid = sl < n_slots;
     unsigned long long best = kNnNone;
     int bpos = -1;
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-    unsigned lane_cost = 0;
-#endif
     const int q = nq, lg = valid ? nlg : 0, sub = nsub;
     const float4 s = ns;
     fetch(sl + NT);
@@ -2564,27 +2143,8 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
       const unsigned pp = t.pos[q];
       bpos = pp == 0xFFFFu ? -1 : (int)pp;
       if (bpos >= 0) best = ((unsigned long long)__float_as_uint(t.d2[q]) << 32) | (unsigned)__float_as_int(t.pts[bpos].w);
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-      lane_cost = nn_search(a.nn, t, a.n_tgt, x, y, z, sub, 1 << lg, best, bpos);
-#else
       nn_search(a.nn, t, a.n_tgt, x, y, z, sub, 1 << lg, best, bpos);
-#endif
     }
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 6
-    {   // how well a wave's lanes are balanced: the wave pays its dearest lane, 64 times
-      unsigned mx = lane_cost, sm = lane_cost;
-      for (int off = 32; off >= 1; off >>= 1) {
-        mx = max(mx, (unsigned)__shfl_xor((int)mx, off, 64));
-        sm += (unsigned)__shfl_xor((int)sm, off, 64);
-      }
-      if ((tid & 63) == 0 && t.dbg && sm > 0) {
-        atomicAdd(&t.dbg[0], mx);          // critical path of the wave-pass (instruction units)
-        atomicAdd(&t.dbg[1], sm / 64u);    // what a perfectly balanced wave would pay
-        atomicAdd(&t.dbg[2], 1u);
-      }
-      lane_cost = 0;
-    }
-#endif
     // merge the lanes of a group: class regions start at multiples of their group size, so the partners
     // lane ^ off (off < L) work on the same query
     // (most waves hold single-lane queries only: no exchange at all)
@@ -2608,19 +2168,8 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
       t.pos[q] = (uint16_t)(bpos < 0 ? 0xFFFF : bpos);
     }
   }
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 3
-  if ((tid & 63) == 0 && t.dbg) {   // per-wave time in the search loop: sum over waves, maximum, wave 0's
-    const unsigned dtw = (unsigned)(__builtin_amdgcn_s_memrealtime() - wv0);
-    atomicAdd(&t.dbg[0], dtw);
-    atomicMax(&t.dbg[1], dtw);
-    if (tid == 0) t.dbg[2] += dtw;
-    if (tid == NT - 64) t.dbg[3] += dtw;
-  }
-#endif
   __syncthreads();
   if (tid == 0) sch->search_ticks = (unsigned)(__builtin_amdgcn_s_memrealtime() - search_t0);
-  PGP_NN_STAMP(7);
-#undef PGP_NN_STAMP
 }
 
 // Split-path correspondences through the index: grid (source chunks of 1024, poses); the workgroup
@@ -2678,7 +2227,7 @@ __device__ __forceinline__ void cluster_leave(const IcpArgs& a, int pose, int ti
   }
 }
 
-template <int METRIC, bool IMG_LDS, bool CLUSTER, bool TRIM_ONLY, int PIR, bool HELP = false>
+template <int METRIC, bool IMG_LDS, bool CLUSTER, bool TRIM_ONLY, int PIR>
 __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALUE: a reference to the kernel argument costs 16 -> 83 spilled registers
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double s_red[(kIcpThreads / 64) * (kRedPlane + 1)];
@@ -2694,9 +2243,6 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
   __shared__ double s_sum[kRedPlane + 1];
   __shared__ float s_G_old[16];
   __shared__ NnSched s_sch;
-
-  // the repair launch behind a helping launch (launch_icp, PGP_ICP_HELP): nothing to do unless a pass was lost
-  if (!CLUSTER && a.run_if && *a.run_if == 0u) return;   // (the helping launch's repair launch: one workgroup per pose)
 
   // several workgroups per pose (few poses in flight: 64 poses would use 64 of the 256 CUs): workgroup `part`
   // searches its share of the source points (nn_share_query); the shares meet in HBM (x_buf) once per iteration,
@@ -2718,23 +2264,9 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
     s_lost = s_solo = 0;
     s_slowest = 0u;
   }
-#if defined(PGP_ICP_STAMPS)
-  const unsigned long long k_start = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef PGP_ICP_STAMPS
-  __shared__ unsigned s_dbg[8];
-  if (tid < 8) s_dbg[tid] = 0;
-  NnLds t = nn_load_image<IMG_LDS>(a, smem, a.n_src, tid, kIcpThreads);
-  t.dbg = s_dbg;
-#else
   const NnLds t = nn_load_image<IMG_LDS>(a, smem, a.n_src, tid, kIcpThreads);
-#endif
   for (int q = tid; q < a.n_src; q += kIcpThreads) t.pos[q] = 0xFFFF;   // no previous correspondence yet
-  if (tid < 16) {
-    const float v = (!CLUSTER && a.T_in ? a.T_in : a.T)[16 * (size_t)pose + tid];
-    s_G[tid] = v;
-    if ((CLUSTER || HELP) && a.T_save && part == 0) a.T_save[16 * (size_t)pose + tid] = v;   // what a repair launch starts from
-  }
+  if (tid < 16) s_G[tid] = Tg[tid];
   if (tid == 0) {
     s_energy_old = (double)FLT_MAX;   // PCL: energy starts at numeric_limits<float>::max()
     s_energy = 0.0;
@@ -2742,20 +2274,9 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
   __syncthreads();
 
   int it = 0;
-#ifdef PGP_ICP_STAMPS   // diagnostic build only (tools/icp_phases.py): thread 0 of pose 0 times the phases (cycles, summed
-  // over the iterations) and reports them in energy[1..5] (poses 1..7 leave their energies alone)
-  unsigned long long st_prev = 0, st_acc[6] = {0, 0, 0, 0, 0, 0};
-#define PGP_STAMP(k) do { if (pose == a.dbg_pose && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memrealtime(); \
-    if ((k) > 0) st_acc[k] += now - st_prev; st_prev = now; } } while (0)
-#else
-#define PGP_STAMP(k) do { } while (0)
-#endif
   for (;;) {
-    PGP_STAMP(0);
     // ---- 1. correspondences ---------------------------------------------------------------------
-    nn_all_queries<kIcpThreads, PIR, HELP, PGP_NN_ROWS == 2 || (PGP_NN_ROWS == 1 && CLUSTER)>(a, t, s_G, 0, n_share, &s_sch, tid, part, P, pose, (unsigned)(it + 1), &s_lost,
-                                            it == 0 ? a.first_walk : 0);
-    if (HELP && s_lost) break;
+    nn_all_queries<kIcpThreads, PIR>(a, t, s_G, 0, n_share, &s_sch, tid, part, P, it == 0 ? a.first_walk : 0);
     if (CLUSTER && P > 1) {
       // publish this share (write-through, agent scope: the partners may sit on other XCDs), meet, read theirs.
       // Consecutive lanes store consecutive records of a block of eight: whole 64-byte lines.
@@ -2836,7 +2357,6 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
         n_share = a.n_src;
       }
     }
-    PGP_STAMP(1);
 
     // the source points of the sums (step 3): requested now, so that their L2 round trip passes under the selection
     // (thread t sums the points 4 t .. 4 t + 3, as icp_refine does: see there)
@@ -2966,7 +2486,6 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
       }
     }
 
-    PGP_STAMP(2);
     // ---- 3. f64 sums over the selected pairs (ordered tie handling), fixed-tree reduction ----
     constexpr int kNs = METRIC == 1 ? kRedPlane : 16;   // sums in use
     double acc[kNs];
@@ -3068,14 +2587,12 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
       s_sum[tid] = v;
     }
     __syncthreads();
-    PGP_STAMP(3);
     if (tid == 0) {
       const double* red = s_sum;
       const double E = red[0] >= 1.0 ? red[kRedPlane] / red[0] : 0.0;
       for (int k = 0; k < 16; ++k) s_G_old[k] = s_G[k];
       if constexpr (METRIC == 1) solve_plane(red, s_G);
       else solve_rigid(red, s_G);
-      PGP_STAMP(4);
       const double E_old = s_energy_old;
       s_energy = E;
       s_energy_old = E;
@@ -3087,91 +2604,10 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
           converged_extra(stop_rules_of(a), pose, it + 1, s_G_old, s_G, E, E_old))
         go = false;
       s_continue = go ? 1 : 0;
-      PGP_STAMP(5);
     }
     __syncthreads();
     ++it;
     if (!s_continue) break;
-  }
-  if (HELP) {
-    if (!s_lost) {
-      if (tid < 16) Tg[tid] = s_G[tid];
-      if (tid == 0) {
-        if (a.energy) a.energy[pose] = (float)s_energy;
-        if (a.iters) a.iters[pose] = it;
-      }
-    } else if (tid == 0) {
-      __hip_atomic_store(a.x_lost, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // ---- this pose is through: take search passes of the poses that are still running (see HelpPub)
-    __shared__ int h_pose;
-    __shared__ unsigned h_s0, h_ns;
-    __shared__ unsigned long long h_pick[kIcpThreads / 64];
-    if (tid == 0) {
-      __builtin_amdgcn_s_waitcnt(0);
-      __hip_atomic_fetch_add(a.help_finished, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    unsigned long long h_t0 = __builtin_amdgcn_s_memrealtime();   // (thread 0 reads it) the last time this helper had something to do
-    for (;;) {
-      // every thread looks at one pose's counter; the lowest open one is tried
-      unsigned long long c = 0;
-      unsigned ns = 0;
-      bool open = false;
-      if (tid < a.n && tid != pose) {
-        c = ld_agent(&a.help_ctl[tid]);
-        if ((c >> 32) != 0ull) {
-          ns = ld_agent(&a.help_nslots[tid]);
-          open = (unsigned)(c & 0xFFFFFFFFull) < ns;
-        }
-      }
-      const unsigned long long bm = __ballot(open);
-      if (lane == 0) h_pick[wave] = bm;
-      __syncthreads();
-      int cand = -1;
-      for (int w = 0; w < kIcpThreads / 64 && cand < 0; ++w)
-        if (h_pick[w]) cand = 64 * w + __builtin_ctzll(h_pick[w]);
-      if (tid == 0) h_pose = -1;
-      __syncthreads();
-      if (cand >= 0) {
-        if (tid == cand) {   // the thread that read this pose's counter claims a pass with it
-          unsigned long long expected = c;
-          if (__hip_atomic_compare_exchange_strong(&a.help_ctl[cand], &expected, c + (unsigned long long)kIcpThreads, __ATOMIC_RELAXED,
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            h_pose = cand;
-            h_s0 = (unsigned)(c & 0xFFFFFFFFull);
-            h_ns = ns;
-          }
-        }
-        __syncthreads();
-        const int hp_pose = h_pose;
-        if (hp_pose >= 0) {
-          unsigned char* pub = a.help + (size_t)hp_pose * a.help_stride;
-          const HelpPub* hp = reinterpret_cast<const HelpPub*>(pub);
-          if (tid < kNnClasses) {
-            s_sch.cnt[tid] = ld_agent(&hp->cnt[tid]);
-            s_sch.slot_end[tid] = ld_agent(&hp->slot_end[tid]);
-          }
-          if (tid < 16) s_G[tid] = ld_agent(&hp->G[tid]);
-          if (tid == 0) s_sch.base = (int)ld_agent(&hp->base);
-          __syncthreads();
-          help_pass<kIcpThreads>(a, t, &s_sch, s_G, pub, h_s0, h_ns, tid, true, true);
-          __builtin_amdgcn_s_waitcnt(0);
-          __syncthreads();
-          if (tid == 0) __hip_atomic_fetch_add(&a.help_done[hp_pose], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          h_t0 = __builtin_amdgcn_s_memrealtime();
-        }
-        continue;   // (a lost race for the pass: look again at once)
-      }
-      // nothing open: done when every pose is through -- or when nobody has asked for help for a few milliseconds: an idle
-      // helper holds a compute unit that a workgroup of this launch which is not resident yet (or another process) waits for
-      if (tid == 0)
-        h_pose = (ld_agent(a.help_finished) >= (unsigned)a.n ||
-                  __builtin_amdgcn_s_memrealtime() - h_t0 > (unsigned long long)a.wait_ticks) ? -2 : -1;
-      __syncthreads();
-      if (h_pose == -2) break;
-      __builtin_amdgcn_s_sleep(127);   // ~3 us between looks: 255 idle workgroups must not crowd the counters
-    }
-    return;
   }
   // (every workgroup of a clustered launch runs and leaves sooner or later -- also the one that came too late for a meeting --,
   //  so the counters are back at zero when the launch is over)
@@ -3179,24 +2615,7 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
   if (CLUSTER && part != 0) return;
   if (tid < 16) Tg[tid] = s_G[tid];
   if (tid == 0) {
-#if defined(PGP_ICP_STAMPS) && PGP_ICP_STAMPS == 4
-    // level 4: every pose reports its whole time in the kernel (ticks) instead of its energy
-    if (a.energy) a.energy[pose] = (float)(__builtin_amdgcn_s_memrealtime() - k_start);
-    if (a.iters) a.iters[pose] = it;
-    return;
-#endif
-#ifdef PGP_ICP_STAMPS
-    if (pose == a.dbg_pose && a.energy && a.n >= 16) {
-      for (int k = 1; k < 6; ++k) a.energy[k] = (float)st_acc[k];
-      for (int k = 0; k < 8; ++k) a.energy[8 + k] = (float)s_dbg[k];
-    }
-    // poses 16.. report their whole time in the kernel (ticks) instead of their energy: tools/icp_phases.py picks
-    // the slowest of them for a second run
-    if (a.energy && pose >= 16) a.energy[pose] = (float)(__builtin_amdgcn_s_memrealtime() - k_start);
-    else if (a.energy && (pose == a.dbg_pose || a.n < 16)) a.energy[pose] = (float)s_energy;
-#else
     if (a.energy) a.energy[pose] = (float)s_energy;
-#endif
     if (a.iters) a.iters[pose] = it;
   }
 }
@@ -3204,12 +2623,6 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
 template <int METRIC, bool IMG_LDS, bool CLUSTER, bool TRIM_ONLY, int PIR>
 __global__ __launch_bounds__(kIcpThreads) void icp_persist_index(IcpArgs a) {
   icp_persist_body<METRIC, IMG_LDS, CLUSTER, TRIM_ONLY, PIR>(a);
-}
-
-// one workgroup per pose, all resident, finished workgroups helping the running ones (see HelpPub)
-template <bool TRIM_ONLY, int PIR>
-__global__ __launch_bounds__(kIcpThreads) void icp_persist_help(IcpArgs a) {
-  icp_persist_body<0, true, false, TRIM_ONLY, PIR, true>(a);
 }
 
 // SEVERAL (source, target) pairs in ONE launch: the children of an MCTS expansion belong to different objects
@@ -3279,13 +2692,6 @@ static const void* persist_kernel(int metric, bool img_lds, bool cluster, bool t
   return persist_kernel_at(14 + (metric == 1 ? 2 : 0) + (cluster ? 1 : 0));
 }
 
-static const void* help_kernel(bool trim_only, int pir) {
-  static const void* const tab[6] = {
-      reinterpret_cast<const void*>(icp_persist_help<false, 2 * kPS>), reinterpret_cast<const void*>(icp_persist_help<false, 3 * kPS>),
-      reinterpret_cast<const void*>(icp_persist_help<false, 4 * kPS>), reinterpret_cast<const void*>(icp_persist_help<true, 2 * kPS>),
-      reinterpret_cast<const void*>(icp_persist_help<true, 3 * kPS>),  reinterpret_cast<const void*>(icp_persist_help<true, 4 * kPS>)};
-  return tab[(trim_only ? 3 : 0) + (pir <= 2 ? 0 : (pir == 3 ? 1 : 2))];
-}
 static const void* multi_kernel(bool trim_only, int pir) {
   static const void* const tab[6] = {
       reinterpret_cast<const void*>(icp_persist_multi<false, 2 * kPS>), reinterpret_cast<const void*>(icp_persist_multi<false, 3 * kPS>),
@@ -3305,10 +2711,8 @@ static int ensure_icp_attrs(pgp_ctx* ctx) {
   for (const void* f : big) PGP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
   for (int v = 0; v < kPersistKernels; ++v)
     PGP_HIP(hipFuncSetAttribute(persist_kernel_at(v), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-  for (int v = 0; v < 6; ++v) {
+  for (int v = 0; v < 6; ++v)
     PGP_HIP(hipFuncSetAttribute(multi_kernel(v >= 3, 2 + v % 3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-    PGP_HIP(hipFuncSetAttribute(help_kernel(v >= 3, 2 + v % 3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8 * 1024));
-  }
   ctx->icp_attr_set = true;
   return PGP_OK;
 }
@@ -3327,7 +2731,6 @@ static IcpEnv icp_env() {
   e.part = on("PGP_ICP_PART", true);
   e.open_grid = on("PGP_ICP_OPEN_GRID", true);
   e.multi = on("PGP_ICP_MULTI", true);
-  e.help = on("PGP_ICP_HELP", false);
   if (const char* v = getenv("PGP_ICP_WGS")) e.wgs = atoi(v) == 4 ? 4 : (atoi(v) == 2 ? 2 : 1);
   if (const char* v = getenv("PGP_ICP_IMAGE")) e.image_global = !strcmp(v, "global");
   if (const char* v = getenv("PGP_ICP_CELL")) e.cell = atof(v);
@@ -3338,9 +2741,6 @@ static IcpEnv icp_env() {
   if (const char* v = getenv("PGP_ICP_OPEN_CELL")) e.open_cell = atof(v) > 0.0 ? atof(v) : e.open_cell;
   if (const char* v = getenv("PGP_ICP_SCENE_WGS")) e.scene_wgs = (unsigned)atoi(v);
   if (const char* v = getenv("PGP_ICP_SCENE_SLEEP")) e.scene_sleep = atoi(v);
-  if (const char* v = getenv("PGP_ICP_DBG_POSE")) e.dbg_pose = atoi(v);
-  if (const char* v = getenv("PGP_ICP_SLOTS")) e.slots = atoi(v);
-  if (const char* v = getenv("PGP_ICP_ROWS")) e.rows = atoi(v);
   e.cooperative = on("PGP_COOPERATIVE_LAUNCH", false);
   if (const char* v = getenv("PGP_ICP_WAIT_MS")) e.wait_ms = atof(v) > 0.0 ? atof(v) : e.wait_ms;
   e.force_lost = getenv("PGP_ICP_FORCE_LOST") != nullptr;
@@ -3486,7 +2886,7 @@ struct CoopChain {
 CoopChain g_coop;
 }  // namespace
 
-// A launch whose workgroups wait for each other (the clustered, the helping and the scene-sized kernels).  By default a
+// A launch whose workgroups wait for each other (the clustered and the scene-sized kernels).  By default a
 // PLAIN launch of a grid that fits on the device at the kernel's occupancy: on an idle or lightly shared device every
 // workgroup is resident at once; behind somebody else's long kernel the late ones arrive when it ends, and every wait in
 // these kernels is bounded by a clock (a lost meeting is finished by the pose's first workgroup; a lost unit of the scene-
@@ -3538,11 +2938,11 @@ struct IcpCall {
 
 // The chain of one resident launch.  Under the chain's lock: the previous resident launch of this device (any stream of this
 // process) has finished before prepare() (re)allocates and clears this one's buffers and names its kernel; the kernel goes
-// through launch_resident; behind() queues what belongs behind it; the device's event is recorded.  *e = the launch's
+// through launch_resident; the device's event is recorded.  *e = the launch's
 // result: anything but hipSuccess (the grid does not fit on this device at the kernel's occupancy) leaves the stream
 // without the kernel and the caller takes the plan's fall-back.
-template <class Prepare, class Behind>
-static int launch_chained(const IcpCall& c, Prepare&& prepare, Behind&& behind, hipError_t* e) {
+template <class Prepare>
+static int launch_chained(const IcpCall& c, Prepare&& prepare, hipError_t* e) {
   const int dev = c.ctx->device >= 0 && c.ctx->device < 64 ? c.ctx->device : 0;
   std::lock_guard<std::mutex> chain(g_coop.mu);
   if (g_coop.last[dev]) PGP_HIP(hipStreamWaitEvent(c.stream, g_coop.last[dev], 0));
@@ -3555,12 +2955,10 @@ static int launch_chained(const IcpCall& c, Prepare&& prepare, Behind&& behind, 
     (void)hipGetLastError();
     return PGP_OK;
   }
-  if ((rc = behind()) != PGP_OK) return rc;
   PGP_HIP(hipEventRecord(g_coop.last[dev], c.stream));
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }
-static int nothing_behind() { return PGP_OK; }
 
 // (an error of the query counts as capturing: the forms that cannot be captured are not taken)
 static bool stream_capturing(hipStream_t stream) {
@@ -3633,7 +3031,7 @@ static int launch_clustered(const IcpCall& c, IcpArgs& a, bool* launched) {
     a.solo_ticks = c.env.solo_ticks;
     // The counters are zero whenever a clustered launch on this context is over (every pose's last workgroup to leave
     // puts them back, lost meeting or not: cluster_leave): a fill only when these words were not the counters of the
-    // last such launch (first use, a grown buffer, another pose count, the helping launch's layout in between).
+    // last such launch (first use, a grown buffer, another pose count, the scene-sized form's layout in between).
     const bool same_words = c.ctx->icp_x_clean && c.ctx->d_icp_x.p == x_before && c.ctx->d_icp_x.cap == x_cap_before &&
                             c.ctx->icp_x_n == c.n && c.ctx->icp_x_need == need;
     if (!same_words) PGP_HIP(hipMemsetAsync(a.x_ctr, 0, p_ctr.bytes(), c.stream));
@@ -3642,58 +3040,12 @@ static int launch_clustered(const IcpCall& c, IcpArgs& a, bool* launched) {
     c.ctx->icp_x_need = need;
     *k = ResidentKernel{per_pose_kernel(c, a, true), (unsigned)(c.n * a.wgs_per_pose), kIcpThreads, params, per_pose_lds(c, a)};
     return PGP_OK;
-  }, nothing_behind, &e);
+  }, &e);
   // (nothing behind the kernel: after a lost meeting the pose's workgroup 0 goes on alone inside the launch, icp_persist_body)
   if (rc != PGP_OK) return rc;
   if (c.env.debug) fprintf(stderr, "icp: %d poses x %d workgroups, resident launch: %s\n", c.n, a.wgs_per_pose, hipGetErrorString(e));
   *launched = e == hipSuccess;
   if (!*launched) a.wgs_per_pose = 1;
-  return PGP_OK;
-}
-
-// One workgroup per pose and all of them resident at once (129 .. 256 poses on 256 compute units): a workgroup
-// that is through with its pose takes search passes of the poses still running (HelpPub) -- the launch then
-// lasts about as long as the MEAN pose, not the slowest.  Launched and chained like the clustered launches; a repair
-// launch behind it (the clustered launch needs none).  Off unless PGP_ICP_HELP=1: measured slower (icp_plan.h).
-static int launch_helping(const IcpCall& c, const IcpArgs& a, bool* launched) {
-  const size_t N = (size_t)c.n, hb = help_bytes(c.n_src);
-  IcpArgs h = a, fix = a;
-  void* hparams[] = {&h};
-  void* fparams[] = {&fix};
-  hipError_t e = hipSuccess;
-  const int rc = launch_chained(c, [&](ResidentKernel* k) -> int {
-    // header, one fill: claim words | slot counts | passes done | finished, lost;  saved transforms;  publications
-    Carve cv;
-    const auto p_ctl = cv.add<unsigned long long>(N);
-    const auto p_words = cv.add<unsigned>(2 * N + 2);
-    const auto p_save = cv.add<float>(16 * N, 256);
-    const auto p_help = cv.add<unsigned char>(N * hb, 256);
-    cv.pad(256);
-    int r;
-    if ((r = cv.ensure(c.ctx->d_icp_x)) != PGP_OK) return r;
-    c.ctx->icp_x_clean = false;   // (the clustered launch's counters live in the same buffer)
-    h.help_ctl = cv.at(p_ctl);
-    h.help_nslots = cv.at(p_words);
-    h.help_done = h.help_nslots + N;
-    h.help_finished = h.help_done + N;
-    h.x_lost = h.help_finished + 1;
-    h.T_save = cv.at(p_save);
-    h.help = cv.at(p_help);
-    h.help_stride = hb;
-    PGP_HIP(hipMemsetAsync(h.help_ctl, 0, p_ctl.bytes() + p_words.bytes(), c.stream));
-    *k = ResidentKernel{help_kernel(c.plan.trim_only, c.plan.pir), (unsigned)c.n, kIcpThreads, hparams, per_pose_lds(c, a)};
-    return PGP_OK;
-  }, [&]() -> int {   // the repair launch: poses the helping launch reported lost, from their saved transforms
-    fix.wgs_per_pose = 1;
-    fix.run_if = h.x_lost;
-    fix.T_in = h.T_save;
-    fix.T_save = nullptr;
-    PGP_HIP(hipLaunchKernel(per_pose_kernel(c, a, false), dim3(c.n), dim3(kIcpThreads), fparams, per_pose_lds(c, a), c.stream));
-    return PGP_OK;
-  }, &e);
-  if (rc != PGP_OK) return rc;
-  if (c.env.debug) fprintf(stderr, "icp: %d poses, helping launch: %s\n", c.n, hipGetErrorString(e));
-  *launched = e == hipSuccess;
   return PGP_OK;
 }
 
@@ -3876,50 +3228,6 @@ static int search_grid(const IcpCall& c, const pgp_icp_options* prm, const float
   return PGP_OK;
 }
 
-#ifdef PGP_SCENE_STAMPS
-// diagnostic build: the stamps of icp_scene_persist, reported on stderr after the launch
-static unsigned long long* g_scene_dbg = nullptr;
-static int scene_stamps_begin(SceneArgs* z, hipStream_t stream) {
-  if (!g_scene_dbg) PGP_HIP(hipMalloc(&g_scene_dbg, (1024 + 4096) * 8));
-  PGP_HIP(hipMemsetAsync(g_scene_dbg, 0, (1024 + 4096) * 8, stream));
-  z->dbg = g_scene_dbg;
-  return PGP_OK;
-}
-static int scene_stamps_report(hipStream_t stream) {
-  std::vector<unsigned long long> h(1024 + 4096);
-  PGP_HIP(hipStreamSynchronize(stream));
-  PGP_HIP(hipMemcpy(h.data(), g_scene_dbg, (1024 + 4096) * 8, hipMemcpyDeviceToHost));
-  {   // iteration 10: every worker's go and searched times relative to the publication of iteration 9
-    const unsigned long long pub = h[9 * 16 + 3];
-    std::vector<double> go, se;
-    for (int w = 0; w < 2048; ++w)
-      if (h[1024 + w]) {
-        go.push_back((double)((long long)(h[1024 + w] - pub)) * 0.01);
-        se.push_back((double)((long long)(h[1024 + 2048 + w] - pub)) * 0.01);
-      }
-    if (!go.empty()) {
-      auto pct = [](std::vector<double> v, double p) { std::sort(v.begin(), v.end()); return v[(size_t)(p * (v.size() - 1))]; };
-      fprintf(stderr, "iteration 10, %zu workers: go min %.2f median %.2f p90 %.2f max %.2f | searched min %.2f median %.2f p90 %.2f p99 %.2f max %.2f us\n",
-              go.size(), pct(go, 0), pct(go, 0.5), pct(go, 0.9), pct(go, 1), pct(se, 0), pct(se, 0.5), pct(se, 0.9), pct(se, 0.99), pct(se, 1));
-      int slow = 0;
-      for (size_t w = 0; w < se.size() && slow < 12; ++w)
-        if (se[w] > pct(se, 0.97)) { fprintf(stderr, "  worker %zu: go %.2f searched %.2f\n", w, go[w], se[w]); ++slow; }
-    }
-  }
-  // per iteration, in 10 ns ticks relative to the previous publication: worker 0's two chunks (go, searched, ticket),
-  // the last unit closed, the updater (units in, sums added, solved, published)
-  unsigned long long prev = h[4];
-  for (int it = 0; it < 64 && h[it * 16 + 3]; ++it) {
-    const unsigned long long* r = &h[it * 16];
-    auto d = [&](unsigned long long v) { return v ? (double)((long long)(v - prev)) * 0.01 : -1.0; };
-    fprintf(stderr, "it %2d  w0 chunk A: go %6.2f searched %6.2f ticket %6.2f | last unit closed %6.2f | updater: units in %6.2f summed %6.2f solved %6.2f "
-                    "published %6.2f us\n", it, d(r[4]), d(r[5]), d(r[6]), d(r[12]), d(r[0]), d(r[1]), d(r[2]), d(r[3]));
-    prev = r[3];
-  }
-  return PGP_OK;
-}
-#endif
-
 // The capped grid search with sums by block -- the shape of the reference's table alignment -- as ONE launch of resident
 // workgroups (icp_scene_persist): every iteration on the device, no host round trip.  PGP_ICP_SCENE_PERSIST=0: the host-
 // driven iterations (the checker of that kernel: same bits).
@@ -3955,9 +3263,6 @@ static int launch_scene(const IcpCall& c, IcpArgs& a, bool* launched) {
     z.E_old = cv.at(p_E);
     z.lost = cv.at(p_lost);
     z.keys = a.ws_key;
-#ifdef PGP_SCENE_STAMPS
-    if ((r = scene_stamps_begin(&z, c.stream)) != PGP_OK) return r;
-#endif
     PGP_HIP(hipMemsetAsync(z.W, 0, filled, c.stream));
     const void* fn = a.metric == 1 ? reinterpret_cast<const void*>(icp_scene_persist<1>) : reinterpret_cast<const void*>(icp_scene_persist<0>);
     PGP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kSceneThreads, 0));
@@ -3970,15 +3275,12 @@ static int launch_scene(const IcpCall& c, IcpArgs& a, bool* launched) {
     if (c.env.force_lost) z.force_lost = 1;
     if (room > z.n_upd) *k = ResidentKernel{fn, grid, kSceneThreads, params, 0};
     return PGP_OK;
-  }, nothing_behind, &e);
+  }, &e);
   if (rc != PGP_OK) return rc;
   if (c.env.debug)
     fprintf(stderr, "icp: scene-sized capped ICP in one launch: %d poses x %d chunks on %u workgroups (%d per CU): %s\n", c.n, z.n_chunks,
             grid, per_cu, hipGetErrorString(e));
   *launched = e == hipSuccess;
-#ifdef PGP_SCENE_STAMPS
-  if (*launched) return scene_stamps_report(c.stream);
-#endif
   return PGP_OK;
 }
 
@@ -4075,9 +3377,9 @@ int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt
   if ((rc = ensure_icp_attrs(ctx)) != PGP_OK) return rc;
   const IcpCall c{ctx, stream, env, plan, n, n_src, n_tgt};
   bool launched = false;
-  IcpForm form = plan.form;
+  const IcpForm form = plan.form;
 
-  if (form == IcpForm::PerPose || form == IcpForm::Clustered || form == IcpForm::Helping) {
+  if (form == IcpForm::PerPose || form == IcpForm::Clustered) {
     // everything of an iteration lives in LDS: the workspace holds the pointmatcher history only
     if (a.smooth > 0) {
       Carve cv;
@@ -4088,16 +3390,9 @@ int launch_icp(pgp_ctx* ctx, const float4* d_src, int n_src, const float4* d_tgt
       PGP_HIP(hipMemsetAsync(a.st_hist, 0, p_hist.bytes(), stream));
     }
     a.wgs_per_pose = 1;
-    a.dbg_pose = env.dbg_pose;
-    a.slot_budget = env.slots;
-    a.rows_mode = env.rows;
     if (env.debug) fprintf(stderr, "icp: n_cus %d, %d poses -> %d workgroups per pose\n", ctx->n_cus, n, plan.wgs_per_pose);
-    if (form == IcpForm::Clustered) {
-      if ((rc = launch_clustered(c, a, &launched)) != PGP_OK || launched) return rc;
-      form = plan.fallback;   // the grid does not fit on this device at the kernel's occupancy
-    }
-    if (form == IcpForm::Helping && ((rc = launch_helping(c, a, &launched)) != PGP_OK || launched)) return rc;
-    return launch_per_pose(c, a);   // (also when the helping grid does not fit)
+    if (form == IcpForm::Clustered && ((rc = launch_clustered(c, a, &launched)) != PGP_OK || launched)) return rc;
+    return launch_per_pose(c, a);   // (the plan's fall-back when the clustered grid does not fit on this device at the kernel's occupancy)
   }
 
   HostWs w;

@@ -33,11 +33,6 @@ struct IcpEnv {
   bool part = true;             // PGP_ICP_PART, checker path: 0 = one workgroup walks the scene for the sums
   bool open_grid = true;        // PGP_ICP_OPEN_GRID, checker path: 0 = the scan alone on targets beyond the index
   bool multi = true;            // PGP_ICP_MULTI, A/B knob: 0 = a multi-target call goes job by job
-  // PGP_ICP_HELP, A/B knob: 1 = the helping launch.  MEASURED SLOWER and therefore off (profiles/r04_ab/icp_helping.log: 256
-  // poses from far 0.84 -> 1.00 ms, from near 0.25 -> 0.28 ms, same bits): the helped kernel's own passes lose the one-trip-
-  // ahead prefetch of the plain slot loop, a published iteration costs ~10 us of write-through traffic and waiting, and idle
-  // workgroups only exist once the fast poses are through -- when the slow ones have few far iterations left.
-  bool help = false;
   int wgs = 0;                  // PGP_ICP_WGS, A/B knob: 0 unset, else 1 / 2 / 4 workgroups per pose
   bool image_global = false;    // PGP_ICP_IMAGE=global, A/B knob: the index image is read from L2 even where it fits LDS
   double cell = 1.0;            // PGP_ICP_CELL, A/B knob: multiplier of the index's cell edge
@@ -48,9 +43,6 @@ struct IcpEnv {
   double open_cell = 2.0;       // PGP_ICP_OPEN_CELL, A/B knob: the open grid's cell edge in point spacings
   unsigned scene_wgs = UINT_MAX;   // PGP_ICP_SCENE_WGS, A/B knob: upper bound of the scene-sized form's workgroups
   int scene_sleep = 1;          // PGP_ICP_SCENE_SLEEP, A/B knob: the scene-sized form's polling pause
-  int dbg_pose = 0;             // PGP_ICP_DBG_POSE, A/B knob (diagnostic builds of the per-pose kernels)
-  int slots = 0;                // PGP_ICP_SLOTS, A/B knob: slot budget of the per-pose kernels
-  int rows = 0;                 // PGP_ICP_ROWS, A/B knob: row dealing of the per-pose kernels
   bool cooperative = false;     // PGP_COOPERATIVE_LAUNCH, A/B knob: 1 = hipLaunchCooperativeKernel for resident launches
   double wait_ms = 3.0;         // PGP_ICP_WAIT_MS, test hook: the clock bound of the kernels whose workgroups wait for each other
   bool force_lost = false;      // PGP_ICP_FORCE_LOST, test hook: the first meeting of every pose counts as lost
@@ -164,7 +156,6 @@ struct IcpFit {
 enum class IcpForm {
   PerPose,     // one launch, one workgroup per pose
   Clustered,   // the same launch with 2 or 4 workgroups per pose (resident)
-  Helping,     // one workgroup per pose, the finished ones help; a repair launch behind it (resident)
   Scene,       // the scene-sized capped form in one launch (resident)
   Host,        // host-driven iterations
   Legacy       // the single-launch persistent kernel of the exhaustive search
@@ -173,7 +164,7 @@ enum class IcpSearch { Scan, CappedGrid, OpenGrid, IndexLds, IndexL2 };
 struct IcpPlan {
   IcpError err;
   IcpForm form = IcpForm::Host;
-  IcpForm fallback = IcpForm::Host;     // when a resident grid does not fit the device (Helping falls to PerPose in turn)
+  IcpForm fallback = IcpForm::Host;     // when a resident grid does not fit the device
   int wgs_per_pose = 1;                 // Clustered: 2 or 4
   bool trim_only = false;               // per-pose forms: the kernels of the TrimmedICP form
   int pir = 4;                          // per-pose forms: points-per-thread class 2 / 3 / 4
@@ -198,9 +189,6 @@ inline IcpPlan icp_stage2(const pgp_icp_options* prm, const IcpShape& s, const I
     p.search = fit.image_in_lds ? IcpSearch::IndexLds : IcpSearch::IndexL2;
     p.trim_only = icp_trim_only(prm);
     p.pir = icp_pir_class(s.n_src);
-    // One workgroup per pose and all of them resident at once: a workgroup that is through with its pose takes search passes
-    // of the poses still running.  Not while the stream is being captured.
-    const bool help = env.help && s.n >= 2 && s.n <= s.n_cus && prm->error_metric == 0 && fit.image_in_lds && smooth == 0 && !s.capturing;
     // Few poses: 2 or 4 workgroups per pose share the search (64 poses alone would use 64 of the 256 CUs).  Not while the
     // stream is being captured (the chain's event wait is not for a graph) and not with the pointmatcher history.
     int want_wgs = s.n * 4 <= s.n_cus ? 4 : (s.n * 2 <= s.n_cus ? 2 : 1);
@@ -208,9 +196,6 @@ inline IcpPlan icp_stage2(const pgp_icp_options* prm, const IcpShape& s, const I
     if (want_wgs > 1 && smooth == 0 && s.n * want_wgs <= s.n_cus && s.n_src >= 64 * want_wgs && !s.capturing) {
       p.form = IcpForm::Clustered;
       p.wgs_per_pose = want_wgs;
-      p.fallback = help ? IcpForm::Helping : IcpForm::PerPose;
-    } else if (help) {
-      p.form = IcpForm::Helping;
     }
     return p;
   }

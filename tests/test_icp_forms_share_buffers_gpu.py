@@ -1,5 +1,5 @@
 """The forms of an ICP call share three buffers of a context (csrc/icp.hip): d_icp_x holds the clustered launch's meeting
-buffers and counters, the helping launch's header and publications or the scene-sized form's unit sums; d_icp_ws the split
+buffers and counters or the scene-sized form's unit sums; d_icp_ws the split
 workspace; d_icp_grid the target's exact index or the search's grid.  One context goes through the forms in the order in
 which a stale layout, a counter fill that was skipped wrongly or an index taken for a grid would show; every result must be
 the bits of the same call on a fresh context."""
@@ -22,7 +22,7 @@ def _calls():
     return [
         clustered,
         ({}, lambda sc: sc.icp_refine_ex(scene[0], scene[1], scene[3], **SCENE)),                                  # scene-sized, one launch
-        ({"PGP_ICP_WGS": "1", "PGP_ICP_HELP": "1"}, lambda sc: sc.icp_refine(small[0], small[1], small[3], trim=0.9, max_iterations=8)),
+        ({"PGP_ICP_WGS": "1"}, lambda sc: sc.icp_refine(small[0], small[1], small[3], trim=0.9, max_iterations=8)),     # one workgroup per pose
         ({}, lambda sc: sc.icp_refine(big[0], big[1], big[3], trim=1.0, max_iterations=6)),                          # open grid
         clustered,
     ]

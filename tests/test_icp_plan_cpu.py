@@ -17,7 +17,6 @@ DEFAULT = dict(n=1, n_src=2500, n_tgt=5000, n_cus=256, trim=0.75, pose_fits=1, h
 SMOOTH = dict(drot=0.001, dtrans=0.005, smooth=4)
 BIG = dict(n_src=30000, n_tgt=100000, trim=1, pose_fits=0, host_fits=0, lds=0)   # the table alignment's shape
 CAPPED = dict(BIG, cap=0.01)
-HELP = {"n": 200, "env.help": 1}
 
 PER_POSE = dict(form="per_pose", wgs="1")
 HOST_SCAN = dict(form="host", search="scan")
@@ -42,11 +41,10 @@ ICP_ROWS = [
     ("class-2048", dict(n=129, n_src=2048), dict(PER_POSE, pir="2")),
     ("class-2500", dict(n=129, n_src=2500), dict(PER_POSE, pir="3")),
     ("class-4096", dict(n=129, n_src=4096), dict(PER_POSE, pir="4")),
-    # helping
-    ("help-on", HELP, dict(form="helping", fallback="per_pose")),
-    ("help-image-in-l2", dict(HELP, lds=0), PER_POSE),
-    ("help-capturing", dict(HELP, capturing=1), PER_POSE),
-    ("help-off", dict(n=200), PER_POSE),
+    # more poses than half the compute units: one workgroup per pose, wherever the image lies, captured or not
+    ("wgs-n200", dict(n=200), PER_POSE),
+    ("wgs-n200-image-in-l2", dict(n=200, lds=0), PER_POSE),
+    ("wgs-n200-capturing", dict(n=200, capturing=1), PER_POSE),
     # host-driven index
     ("persist-0", {"env.persist": 0}, dict(form="host", search="index_lds", sums="whole")),
     ("persist-0-l2", {"env.persist": 0, "lds": 0}, dict(form="host", search="index_l2")),

@@ -24,7 +24,6 @@ static const char* form_name(IcpForm f) {
   switch (f) {
     case IcpForm::PerPose: return "per_pose";
     case IcpForm::Clustered: return "clustered";
-    case IcpForm::Helping: return "helping";
     case IcpForm::Scene: return "scene";
     case IcpForm::Host: return "host";
     case IcpForm::Legacy: return "legacy";
@@ -74,11 +73,11 @@ static bool set_env(IcpEnv* e, const std::string& k, const char* v) {
     return true;              \
   }
   PGP_FIELD(nn, atoi(v)) PGP_FIELD(split, atoi(v)) PGP_FIELD(persist, atoi(v)) PGP_FIELD(scene_persist, atoi(v) != 0)
-  PGP_FIELD(part, atoi(v) != 0) PGP_FIELD(open_grid, atoi(v) != 0) PGP_FIELD(multi, atoi(v) != 0) PGP_FIELD(help, atoi(v) != 0)
+  PGP_FIELD(part, atoi(v) != 0) PGP_FIELD(open_grid, atoi(v) != 0) PGP_FIELD(multi, atoi(v) != 0)
   PGP_FIELD(wgs, atoi(v)) PGP_FIELD(image_global, atoi(v) != 0) PGP_FIELD(cell, atof(v)) PGP_FIELD(aspect, atof(v))
   PGP_FIELD(vic, atoi(v) != 0) PGP_FIELD(first_walk, atoi(v)) PGP_FIELD(solo_ticks, (unsigned)atoi(v)) PGP_FIELD(open_cell, atof(v))
-  PGP_FIELD(scene_wgs, (unsigned)atoi(v)) PGP_FIELD(scene_sleep, atoi(v)) PGP_FIELD(dbg_pose, atoi(v)) PGP_FIELD(slots, atoi(v))
-  PGP_FIELD(rows, atoi(v)) PGP_FIELD(cooperative, atoi(v) != 0) PGP_FIELD(wait_ms, atof(v)) PGP_FIELD(force_lost, atoi(v) != 0)
+  PGP_FIELD(scene_wgs, (unsigned)atoi(v)) PGP_FIELD(scene_sleep, atoi(v))
+  PGP_FIELD(cooperative, atoi(v) != 0) PGP_FIELD(wait_ms, atof(v)) PGP_FIELD(force_lost, atoi(v) != 0)
   PGP_FIELD(debug, atoi(v) != 0)
 #undef PGP_FIELD
   return false;
