@@ -337,6 +337,10 @@ __global__ __launch_bounds__(256) void bp_init(int* __restrict__ head, uint32_t 
   if (t < n_counters) counters[t] = 0u;
 }
 
+// the base number of an entry: the upper 16 bits of its third word, taken UNSIGNED (bases 32768 .. 65535 set the word's sign
+// bit: an arithmetic shift made them negative, they matched no base and reported no quads)
+__device__ __forceinline__ int entry_base(const int4& en) { return (int)((unsigned)en.z >> 16); }
+
 __global__ __launch_bounds__(256) void bp_entries(CsBatchArgs a) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= a.total_p) return;
@@ -351,7 +355,7 @@ __global__ __launch_bounds__(256) void bp_entries(CsBatchArgs a) {
   int bin = normal_bin(n, a.nepsilon);
   if (c < 0 || bin < 0) return;  // addElement returns false
   unsigned bk = bucket_of_b(c, b, a.bmask);
-  a.entries[t] = make_int4((int)(c & 0xFFFFFFFFll), (int)(c >> 32), bin | (b << 16), (int)i);
+  a.entries[t] = make_int4((int)(c & 0xFFFFFFFFll), (int)(c >> 32), (int)((unsigned)bin | ((unsigned)b << 16)), (int)i);
   a.next[t] = atomicExch(&a.head[bk], (int)t);   // (the entry is read by the NEXT launch only)
 }
 
@@ -371,7 +375,7 @@ __device__ __forceinline__ bool bq_has_cell(const CsBatchArgs& a, const uint32_t
   const int clo = (int)(c & 0xFFFFFFFFll), chi = (int)(c >> 32);
   for (int k = a.head[bk]; k >= 0; k = a.next[k]) {
     const int4 en = a.entries[k];
-    if (en.x == clo && en.y == chi && (en.z >> 16) == b) {
+    if (en.x == clo && en.y == chi && entry_base(en) == b) {
       *first = k;   // the walks of the match start at the first entry of the cell
       return true;
     }
@@ -440,7 +444,7 @@ __device__ __forceinline__ uint32_t bq_walk(const CsBatchArgs& a, const uint32_t
   for (int k = s, nk; k >= 0; k = nk) {
     nk = a.next[k];
     const int4 en = a.entries[k];
-    if (en.x != clo || en.y != chi || (en.z >> 16) != b) continue;
+    if (en.x != clo || en.y != chi || entry_base(en) != b) continue;
     const int bin = en.z & 0xFFFF;
     const uint32_t word = colored[bin >> 5];
     if (!((word >> (bin & 31)) & 1u)) continue;

@@ -186,6 +186,7 @@ def main():
     test_scene_frame_case()
     hausdorff_case()
     dead_code_case()
+    quad_edges_case()
 
 
 def morton_order(Q):
@@ -574,6 +575,49 @@ def congruent_cases():
               "quads", [len(x) for x in QD], f"{os.path.getsize(path)/1024:.0f} KiB")
 
 
+def quad_edges_case():
+    """(19) the congruent-set joins on hand-made lattices (tests/_congruent_models.py): exact +-axis pair directions, invariant
+    points on model points, a coarse grid with up to 72 quads per Q pair.  Pair lists are in (i, j) order (the set the
+    reference's functor finds); the quads are the reference's IndexedNormalSet join and its classic kd-tree join."""
+    import ctypes as C
+    import _congruent_models as M
+    from _checkers import CongruentChecker
+    L = ref_lib()
+    L.ref_4pcs_find_congruent.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, C.c_float,
+                                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
+                                          C.POINTER(C.c_int), C.c_int]
+    pts = M.models()
+    out = {f"pts_{k}": v for k, v in pts.items()}
+    ref = {k: CongruentChecker(v, "ref") for k, v in pts.items()}
+    orc = {k: CongruentChecker(v, "oracle") for k, v in pts.items()}
+    dist = {"L": (M.D_LONG, 0.0), "LJ": (M.D_LONG, M.LJ_EPS), "K": (M.K_SIDE, 0.0)}
+    for k, (d, eps) in dist.items():
+        p = orc[k].extract_pairs(d, eps)
+        base = M.base_of_case(k, "zx", pts[k])
+        assert set(map(tuple, p.tolist())) == set(map(tuple, ref[k].extract_pairs(d, eps, base).tolist()))
+        out[f"pairs_{k}"] = p
+    for key, mk, bn, inv, thr in M.s4_cases():
+        q = ref[mk].find_congruent(M.base_of_case(mk, bn, pts[mk]), inv[0], inv[1], thr, out[f"pairs_{mk}"], out[f"pairs_{mk}"])
+        M.store_quads(out, key, q)
+        print(key, len(q))
+    cap = 1 << 20
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    for key, mk, thr in M.t4_cases():
+        p = np.ascontiguousarray(out[f"pairs_{mk}"])
+        buf = np.zeros((cap, 4), np.int32)
+        n = L.ref_4pcs_find_congruent(_fp(pts[mk]), len(pts[mk]), C.c_float(0.5), C.c_float(0.5), C.c_float(float(thr)),
+                                      ip(p), len(p), ip(p), len(p), ip(buf), cap)
+        assert 0 < n <= cap
+        # inside one Q pair the order is the kd-tree's: stored sorted there, the Q pairs' own order kept
+        q = buf[:n]
+        assert np.array_equal(M.canon_per_q(q)[:, 2:], q[:, 2:])
+        M.store_quads(out, key, M.canon_per_q(q))
+        print(key, n)
+    path = os.path.join(HERE, "quad_edges.npz")
+    np.savez_compressed(path, **out)
+    print("quad_edges:", f"{os.path.getsize(path)/1024:.0f} KiB")
+
+
 def cluster_pose_set(rng, n, n_modes=12):
     """Scored pose list with structure: tight groups around a few modes + scattered poses."""
     from scipy.spatial.transform import Rotation as Rot
@@ -647,5 +691,8 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "weights":
         weights_case()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "quad_edges":
+        quad_edges_case()
         sys.exit(0)
     main()
