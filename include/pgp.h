@@ -347,7 +347,10 @@ int pgp_extract_pairs(pgp_ctx* ctx, float pair_distance, float eps, int* pairs, 
  * distance_factor * delta (base.cc:1989-1990), P_pairs / Q_pairs = the two pair lists (flat
  * (first,second) ids into the search model: pairs1 / pairs6 of base.cc:1970-1981).  quads:
  * cap x 4 ints in the reference's order (its std::set of (P-pair id, Q-pair id));
- * *n_quads = the full count. */
+ * *n_quads = the full count.  A list of 2^24 pairs or more: PGP_EINVAL (the join's keys hold a
+ * pair index in 24 bits).  The call runs on the batch's workspaces: it always discards the
+ * context's resident quad batch and its fits (below), whatever it finds; an empty list on either
+ * side gives 0 quads and touches nothing. */
 int pgp_find_congruent(pgp_ctx* ctx, const float* base, float invariant1, float invariant2, float threshold,
                        const int* P_pairs, int nP, const int* Q_pairs, int nQ, int* quads, int cap,
                        int* n_quads);
@@ -543,7 +546,8 @@ int pgp_extract_pairs_batch_fetch(pgp_ctx* ctx, int list, int* pairs, int cap, i
  * n_quads[n_bases].  Per base the quads and their order are those of pgp_find_congruent on the two fetched lists; a base with
  * an empty list has none (:1984).  The result is THE resident quad batch of the context (there is one): pgp_congruent_batch_quads,
  * _fit, _fit_score, _fit_score_list, _sample_fit_score_list and _fetch work on it unchanged; it replaces a batch of
- * pgp_find_congruent_batch and is replaced by one; a new pgp_extract_pairs_batch or pgp_set_search_model discards it
+ * pgp_find_congruent_batch and is replaced by one; a new pgp_extract_pairs_batch or pgp_set_search_model discards it, and so,
+ * always, does a pgp_find_congruent with two non-empty lists
  * (PGP_ESTATE from the calls above).  A list number out of range: PGP_EINVAL; no resident lists: PGP_ESTATE. */
 int pgp_find_congruent_batch_lists(pgp_ctx* ctx, const float* base_xyz, const float* invariants, const int* lists, int n_bases,
                                    float threshold, int* n_quads);

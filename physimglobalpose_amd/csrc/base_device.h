@@ -2,7 +2,7 @@
 //   ppfk::fit_plane / seg_seg / try_quadrilateral   the plane through three base points (base.cc:527-547, :731-745), distSegmentToSegment
 //                                                   (:81-148) and TryQuadrilateral (:415-464): base_select.hip (StoCS, pgp_base_invariants)
 //                                                   and super4pcs.hip (SelectQuadrilateral)
-//   v4dev::widest_triangle                          SelectRandomTriangle (:377-410) with the counter-based draw: v4pcs.hip and super4pcs.hip
+//   v4dev::widest_triangle, wave_max / wave_min      SelectRandomTriangle (:377-410) with the counter-based draw: v4pcs.hip and super4pcs.hip
 #pragma once
 
 #include "pgp_internal.h"
@@ -33,7 +33,7 @@ __device__ __forceinline__ Plane fit_plane(V3 q1, V3 q2, V3 q3) {  // base.cc:73
 __device__ inline float seg_seg(V3 p1, V3 p2, V3 q1, V3 q2, double* invariant1, double* invariant2) {
   const double tiny = 0.0001;
   const V3 u = vsub(p2, p1), v = vsub(q2, q1), w = vsub(p1, q1);
-  const double uu = dot(u, u), uv = dot(u, v), vv = dot(v, v), uw = dot(u, w), vw = dot(v, w);
+  const double uu = dot_eigen(u, u), uv = dot_eigen(u, v), vv = dot_eigen(v, v), uw = dot_eigen(u, w), vw = dot_eigen(v, w);
   const double det = uu * vv - uv * uv;
   double sN, sD = det, tN, tD = det;
   if (det < tiny) {            // (almost) parallel: pin s = 0 and project q-side only
@@ -78,7 +78,7 @@ __device__ inline float seg_seg(V3 p1, V3 p2, V3 q1, V3 q2, double* invariant1, 
   const float fs = (float)*invariant1, ft = (float)*invariant2;   // Eigen narrows the double scalars
   const V3 r = {sub(add(w.x, mul(fs, u.x)), mul(ft, v.x)), sub(add(w.y, mul(fs, u.y)), mul(ft, v.y)),
                 sub(add(w.z, mul(fs, u.z)), mul(ft, v.z))};
-  return norm(r);
+  return norm_eigen(r);
 }
 
 // TryQuadrilateral on lanes 0..11 of the calling wave (all 64 lanes call): pairing p enumerates
@@ -133,34 +133,25 @@ __device__ inline bool try_quadrilateral(const float4* __restrict__ P, int ids[4
 
 }  // namespace ppfk
 
-// The float helpers of the position-only modes: dot products and squared norms as (x x + y y) + z z.
+// The position-only modes (v4pcs.hip, super4pcs.hip SelectQuadrilateral): their dot products and squared norms are
+// (x x + y y) + z z, exact_f32.h's _lr forms.
 namespace v4dev {
 
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-// correctly rounded float sqrt (see rigid_fit.hip)
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 ld3(const float4* __restrict__ a, int i) {
-  float4 v = a[i];
-  return {v.x, v.y, v.z};
-}
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
-// base selection: (x x + y y) + z z
-__device__ __forceinline__ float dot(V3 a, V3 b) { return add(add(mul(a.x, b.x), mul(a.y, b.y)), mul(a.z, b.z)); }
+using namespace exact;
 
 __device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
     const unsigned long long other = __shfl_xor(k, o, 64);
     k = other > k ? other : k;
+  }
+  return k;
+}
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long k) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long other = __shfl_xor(k, o, 64);
+    k = other < k ? other : k;
   }
   return k;
 }
@@ -175,8 +166,8 @@ __device__ __forceinline__ unsigned long long widest_triangle(const float4* __re
     const int s = (int)(sample_variate(st, 1 + 2 * i) % un), t = (int)(sample_variate(st, 2 + 2 * i) % un);
     const V3 u = vsub(ld3(P, s), p0), w = vsub(ld3(P, t), p0);
     const V3 c = cross(u, w);
-    const float how_wide = sqrt_rn(dot(c, c));
-    if (how_wide > 0.f && dot(u, u) < DD && dot(w, w) < DD) {
+    const float how_wide = norm_lr(c);
+    if (how_wide > 0.f && sqnorm_lr(u) < DD && sqnorm_lr(w) < DD) {
       const unsigned long long key = ((unsigned long long)__float_as_uint(how_wide) << 32) | (0xFFFFFFFFu - (unsigned)i);
       best = key > best ? key : best;
     }

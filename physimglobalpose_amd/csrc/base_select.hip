@@ -72,7 +72,7 @@ __device__ __forceinline__ float stage2_weight(const SelectArgs& a, int i, float
 __device__ __forceinline__ float stage3_weight(const SelectArgs& a, int i, float cur_i, int b1, int b2, V3 p1,
                                                V3 v_1, V3 pb, V3 nb, float prob_b) {
   const V3 v_2 = vsub(ld3(a.P, i), p1);
-  const float d = dot(v_1, v_2);
+  const float d = dot_eigen(v_1, v_2);
   // int_angle = min(a, 180 - a) < 30 with a = acosf(d) * 180 / pi: thresholds on d (NaN: not excluded)
   const bool small_angle = (d >= a.gate_lo && d <= 1.0f) || (d <= a.gate_hi && d >= -1.0f);
   if (i == b1 || i == b2 || cur_i == 0.f || small_angle) return 0.f;
@@ -90,8 +90,8 @@ __device__ __forceinline__ float stage4_weight(const SelectArgs& a, int i, float
     // Scalar planar_distance = std::abs(A*x + B*y + C*z - 1.0): float products and sums, double minus
     const float lin = add(add(mul(pl.A, p.x), mul(pl.B, p.y)), mul(pl.C, p.z));
     const float planar = (float)fabs((double)lin - 1.0);
-    if ((double)planar > 0.01 || (double)norm(vsub(p, q1)) < 0.01 || (double)norm(vsub(p, q2)) < 0.01 ||
-        (double)norm(vsub(p, q3)) < 0.01)
+    if ((double)planar > 0.01 || (double)norm_eigen(vsub(p, q1)) < 0.01 || (double)norm_eigen(vsub(p, q2)) < 0.01 ||
+        (double)norm_eigen(vsub(p, q3)) < 0.01)
       return 0.f;
   }
   const float4 pn = a.Pnw[i];

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -31,11 +32,11 @@ namespace pgp {
 
 namespace {
 
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
+using exact::add;   // exact_f32.h
+using exact::fdiv;
+using exact::mul;
+using exact::sqrt_rn;
+using exact::sub;
 
 constexpr int kPoseStride = 12;  // per sorted pose: 9 floats of a 3x3 (row-major) + translation
 

@@ -18,10 +18,14 @@
 // cell of its own invariant point e2, "renders" a cone of half-angle alpha around the pair
 // direction into the 343 direction bins, and accepts the P-pairs of the coloured bins whose
 // world-space invariant points are within sqrt(delta) (sic: squared distance vs delta,
-// super4pcs.cc:170).  Here: P-pairs are bucketed by a hash of their cell (count / scan / fill),
-// one lane per Q-pair recomputes the cone mask (11 x 32 bits in VGPRs) and walks its bucket;
-// hits are (P-pair id, Q-pair id) keys, sorted with a device radix sort = the reference's
-// std::set order, so `congruent_quads[k]` means the same quad in both implementations.
+// super4pcs.cc:170).  Here there is ONE join, for any number of bases (below): the P-pairs of all
+// bases are linked into the buckets of one hash table keyed by (cell, base), a workgroup of Q-pairs
+// first gathers those whose cell holds anything, four lanes share the cone of each (11 x 32 bits in
+// LDS), and one lane walks its bucket; hits are (base, P-pair, Q-pair) keys, sorted with a device
+// radix sort = the reference's std::set order per base, so `congruent_quads[k]` means the same quad
+// in both implementations.  pgp_find_congruent is a batch of one base whose lists the host passes in
+// (launch_find_congruent).  (Up to 81c9ed9 it had kernels of its own -- p_entries, q_match,
+// emit_quads: count / scan / fill twice over -- with a second copy of the cone and of the walk.)
 //
 // Float parity: all index arithmetic (unit-cube coordinates, cell and bin indices, quaternion
 // rotation of the cone samples, normalisation) is evaluated in the reference's order with
@@ -32,6 +36,7 @@
 #include <cstring>  // rocprim's texture_cache_iterator.hpp uses memset without including it
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -44,38 +49,7 @@ namespace pgp {
 
 namespace {
 
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
-// correctly rounded float sqrt (see rigid_fit.hip: __fsqrt_rn is 1 ulp off on ~15 % of inputs)
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ float sqnorm(V3 v) { return add(mul(v.x, v.x), add(mul(v.y, v.y), mul(v.z, v.z))); }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ V3 normalized(V3 v) {  // Eigen normalized(): z > 0 ? v / sqrt(z) : v
-  float z = sqnorm(v);
-  if (z > 0.f) {
-    float n = sqrt_rn(z);
-    return {fdiv(v.x, n), fdiv(v.y, n), fdiv(v.z, n)};
-  }
-  return v;
-}
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
-__device__ __forceinline__ V3 ld3(const float4* __restrict__ a, int i) {
-  float4 v = a[i];
-  return {v.x, v.y, v.z};
-}
-// p1 + inv * (p2 - p1)
-__device__ __forceinline__ V3 lerp_pt(V3 p1, V3 p2, float inv) {
-  V3 d = vsub(p2, p1);
-  return {add(p1.x, mul(inv, d.x)), add(p1.y, mul(inv, d.y)), add(p1.z, mul(inv, d.z))};
-}
+using namespace exact;   // exact_f32.h
 
 // IndexedNormalSet::indexNormal (normalset.h:100-104, utils.h:141-148): 7 bins per axis
 __device__ __forceinline__ int normal_bin(V3 n, float nepsilon) {
@@ -95,11 +69,6 @@ __device__ __forceinline__ long long pos_cell(V3 p, float epsilon, int eg) {
   return ((long long)iz * eg + iy) * eg + ix;
 }
 
-__device__ __forceinline__ unsigned bucket_of(long long cell, unsigned mask) {
-  unsigned long long h = (unsigned long long)cell * 0x9E3779B97F4A7C15ull;
-  return (unsigned)(h >> 40) & mask;
-}
-
 // ---------------- ExtractPairs ----------------
 template <bool FILL>
 __global__ __launch_bounds__(256) void pair_rows(const float4* __restrict__ Qw, int n, double pair_distance,
@@ -117,7 +86,7 @@ __global__ __launch_bounds__(256) void pair_rows(const float4* __restrict__ Qw, 
     bool hit = false;
     if (j < i) {
       V3 d = vsub(qi, ld3(Qw, j));
-      float dist = sqrt_rn(sqnorm(d));  // (q.pos() - p.pos()).norm()
+      float dist = norm_eigen(d);  // (q.pos() - p.pos()).norm()
       hit = !(fabs((double)dist - pair_distance) > eps);
     }
     unsigned long long m = __ballot(hit);
@@ -131,146 +100,6 @@ __global__ __launch_bounds__(256) void pair_rows(const float4* __restrict__ Qw, 
   if (!FILL && lane == 0) row_cnt[i] = running;
 }
 
-// ---------------- FindCongruentQuadrilaterals ----------------
-struct ConeTable {
-  int nb;          // nbSample
-  float v[56][3];  // (sinAlpha cos(theta_a), sinAlpha sin(theta_a), cosAlpha)
-};
-
-int cone_for_base(const float base[12], float* cone /*[56][3]*/);   // defined with the batch launcher below
-
-struct CsArgs {
-  const float4* Qw;  // world (centred) search model
-  const float4* Qu;  // unit-cube image
-  int nQs;
-  const int2* Pp;
-  int nP;
-  const int2* Qp;
-  int nQ;
-  float inv1, inv2, threshold, epsilon, nepsilon;
-  int eg;
-  unsigned bmask;
-  uint32_t* bucket_cnt;          // [nb+1]
-  const uint32_t* bucket_start;  // [nb+1]
-  int4* entries;                 // {cell_lo, cell_hi, bin, id}
-  uint32_t* q_cnt;               // [nQ+1]
-  const uint32_t* q_start;
-  unsigned long long* keys;
-  uint32_t cap;
-};
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void p_entries(CsArgs a) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.nP) return;
-  int2 pr = a.Pp[i];
-  if ((unsigned)pr.x >= (unsigned)a.nQs || (unsigned)pr.y >= (unsigned)a.nQs) return;
-  V3 p1 = ld3(a.Qu, pr.x), p2 = ld3(a.Qu, pr.y);
-  V3 n = normalized(vsub(p2, p1));
-  long long c = pos_cell(lerp_pt(p1, p2, a.inv1), a.epsilon, a.eg);
-  int b = normal_bin(n, a.nepsilon);
-  if (c < 0 || b < 0) return;  // addElement returns false
-  unsigned bk = bucket_of(c, a.bmask);
-  uint32_t slot = atomicAdd(&a.bucket_cnt[bk], 1u);
-  if (FILL) a.entries[a.bucket_start[bk] + slot] = make_int4((int)(c & 0xFFFFFFFFll), (int)(c >> 32), b, i);
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(128) void q_match(CsArgs a, ConeTable cone) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.nQ) return;
-  int2 qr = a.Qp[i];
-  uint32_t found = 0;
-  const uint32_t out0 = FILL ? a.q_start[i] : 0u;
-  if ((unsigned)qr.x < (unsigned)a.nQs && (unsigned)qr.y < (unsigned)a.nQs) {
-    V3 p1 = ld3(a.Qu, qr.x), p2 = ld3(a.Qu, qr.y);
-    long long c = pos_cell(lerp_pt(p1, p2, a.inv2), a.epsilon, a.eg);
-    if (c >= 0) {
-      unsigned bk = bucket_of(c, a.bmask);
-      uint32_t s = a.bucket_start[bk], e = a.bucket_start[bk + 1];
-      // is there anything of this cell in the bucket?  (angularGrid(p) == NULL otherwise)
-      bool any = false;
-      for (uint32_t k = s; k < e && !any; ++k) {
-        int4 en = a.entries[k];
-        any = en.x == (int)(c & 0xFFFFFFFFll) && en.y == (int)(c >> 32);
-      }
-      if (any) {
-        // q.setFromTwoVectors((0,0,1), queryn)   (Eigen Quaternion.h:577-610)
-        V3 queryn = normalized(vsub(p2, p1));
-        V3 v1 = normalized(queryn);
-        float cq = add(mul(v1.x, 0.f), add(mul(v1.y, 0.f), mul(v1.z, 1.f)));
-        V3 qv;
-        float qw;
-        if (cq < add(-1.0f, 1e-5f)) {
-          // nearly opposite to +z: the reference takes the axis from a 2x3 SVD; any unit axis
-          // orthogonal to z is a valid half-turn, we take x (documented divergence)
-          float cc = cq > -1.0f ? cq : -1.0f;
-          float w2 = mul(add(1.0f, cc), 0.5f);
-          qw = sqrt_rn(w2);
-          qv = {sqrt_rn(sub(1.0f, w2)), 0.f, 0.f};
-        } else {
-          V3 axis = {sub(mul(0.f, v1.z), mul(1.f, v1.y)), sub(mul(1.f, v1.x), mul(0.f, v1.z)),
-                     sub(mul(0.f, v1.y), mul(0.f, v1.x))};
-          float sq = sqrt_rn(mul(add(1.0f, cq), 2.0f));
-          float invs = fdiv(1.0f, sq);
-          qv = {mul(axis.x, invs), mul(axis.y, invs), mul(axis.z, invs)};
-          qw = mul(sq, 0.5f);
-        }
-        // cone "rendering" into the 343 direction bins (normalset.hpp:186-196)
-        uint32_t colored[11];
-#pragma unroll
-        for (int w = 0; w < 11; ++w) colored[w] = 0u;
-        for (int s2 = 0; s2 < cone.nb; ++s2) {
-          V3 v = {cone.v[s2][0], cone.v[s2][1], cone.v[s2][2]};
-          V3 uv = cross(qv, v);  // q * v = v + w*uv + vec x uv, uv = 2 (vec x v)
-          uv = {add(uv.x, uv.x), add(uv.y, uv.y), add(uv.z, uv.z)};
-          V3 c2 = cross(qv, uv);
-          V3 r = {add(add(v.x, mul(qw, uv.x)), c2.x), add(add(v.y, mul(qw, uv.y)), c2.y),
-                  add(add(v.z, mul(qw, uv.z)), c2.z)};
-          int id = normal_bin(normalized(r), a.nepsilon);
-          if (id >= 0) {
-#pragma unroll
-            for (int w = 0; w < 11; ++w)
-              if (w == (id >> 5)) colored[w] |= 1u << (id & 31);
-          }
-        }
-        // world-space invariant point of the query pair
-        V3 queryQ = lerp_pt(ld3(a.Qw, qr.x), ld3(a.Qw, qr.y), a.inv2);
-        for (uint32_t k = s; k < e; ++k) {
-          int4 en = a.entries[k];
-          if (en.x != (int)(c & 0xFFFFFFFFll) || en.y != (int)(c >> 32)) continue;
-          uint32_t word = 0;
-#pragma unroll
-          for (int w = 0; w < 11; ++w)
-            if (w == (en.z >> 5)) word = colored[w];
-          if (!((word >> (en.z & 31)) & 1u)) continue;
-          int2 pp = a.Pp[en.w];
-          V3 w1 = ld3(a.Qw, pp.x), w2 = ld3(a.Qw, pp.y);
-          V3 dd = vsub(w2, w1);  // invPoint = pp1 + (pp2 - pp1) * invariant1
-          V3 ip = {add(w1.x, mul(dd.x, a.inv1)), add(w1.y, mul(dd.y, a.inv1)), add(w1.z, mul(dd.z, a.inv1))};
-          if (sqnorm(vsub(queryQ, ip)) <= a.threshold) {  // squared distance vs delta, sic
-            if (FILL && out0 + found < a.cap)
-              a.keys[out0 + found] = ((unsigned long long)(unsigned)en.w << 32) | (unsigned)i;
-            ++found;
-          }
-        }
-      }
-    }
-  }
-  if (!FILL) a.q_cnt[i] = found;
-}
-
-__global__ __launch_bounds__(256) void emit_quads(const unsigned long long* __restrict__ keys, uint32_t n,
-                                                  const int2* __restrict__ Pp, const int2* __restrict__ Qp,
-                                                  int4* __restrict__ quads) {
-  uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  unsigned long long key = keys[k];
-  int2 p = Pp[(uint32_t)(key >> 32)], q = Qp[(uint32_t)(key & 0xFFFFFFFFull)];
-  quads[k] = make_int4(p.x, p.y, q.x, q.y);
-}
-
-
 // ---------------- FindCongruentQuadrilaterals for MANY bases in one pass ----------------
 // The drop-in extracts congruent sets for ~100 bases per object (base.cc:1855-1874).  Driven base by
 // base that is ~12 small launches, two host syncs and two list uploads each (24 ms per object,
@@ -278,11 +107,11 @@ __global__ __launch_bounds__(256) void emit_quads(const unsigned long long* __re
 // (pgp_set_ppf_map: pairs1 = PPFMap[ppf(b0,b1)], pairs6 = PPFMap[ppf(b2,b3)], base.cc:1970-1981),
 // one thread handles one (base, pair), the P-pairs of all bases share ONE bucket table (the base id
 // is part of the hash and of the entry), and the match keys (base | P-pair | Q-pair) are sorted
-// once -- per base that is the reference's std::set order again.  Same arithmetic per pair as the
-// single-base kernels above; identical lists (tests/test_congruent_batch_gpu.py).
+// once -- per base that is the reference's std::set order again.  A base may also take its lists from
+// pgp_extract_pairs_batch or, for pgp_find_congruent, from the host: the pair array is an argument.
 struct BatchBase {
   float inv1, inv2;
-  uint32_t p_off, p_cnt, q_off, q_cnt;   // ranges of the table's pair array
+  uint32_t p_off, p_cnt, q_off, q_cnt;   // ranges of the pair array
   uint32_t p_flat, q_flat;               // first flat thread index of this base's P / Q pairs
   int cone_nb;
   int pad;
@@ -292,7 +121,7 @@ struct CsBatchArgs {
   const float4* Qw;
   const float4* Qu;
   int nQs;
-  const int2* pairs;          // the table's pair array
+  const int2* pairs;          // the pair array the bases' ranges index
   const BatchBase* bases;
   int nb;
   const float* cones;         // [nb][56][3]
@@ -452,7 +281,7 @@ __device__ __forceinline__ uint32_t bq_walk(const CsBatchArgs& a, const uint32_t
     const V3 w1 = ld3(a.Qw, pp.x), w2 = ld3(a.Qw, pp.y);
     const V3 dd = vsub(w2, w1);
     const V3 ip = {add(w1.x, mul(dd.x, B.inv1)), add(w1.y, mul(dd.y, B.inv1)), add(w1.z, mul(dd.z, B.inv1))};
-    if (sqnorm(vsub(queryQ, ip)) <= a.threshold) {
+    if (sqnorm_eigen(vsub(queryQ, ip)) <= a.threshold) {
       if (!WRITE) {
 #pragma unroll
         for (int q = 0; q < kBqKeep; ++q)
@@ -578,13 +407,13 @@ __global__ __launch_bounds__(256) void batch_base_starts(const uint32_t* __restr
   if (threadIdx.x == 255) base_start[nb] = run;   // the last thread's running sum is the total
 }
 
-// picks (base, j) -> the j-th quad of that base in the reference's order
+// picks (base, j) -> the j-th quad of that base in the reference's order; no picks: the first m quads of base 0
 __global__ void batch_gather(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ base_start,
                              const BatchBase* __restrict__ bases, const int2* __restrict__ pairs,
                              const int2* __restrict__ picks, int m, int4* __restrict__ quads) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= m) return;
-  const int2 pk = picks[t];
+  const int2 pk = picks ? picks[t] : make_int2(0, t);
   const BatchBase B = bases[pk.x];
   const unsigned long long key = keys[base_start[pk.x] + (uint32_t)pk.y];
   const int2 p = pairs[B.p_off + (uint32_t)((key >> 24) & 0xFFFFFFull)], q = pairs[B.q_off + (uint32_t)(key & 0xFFFFFFull)];
@@ -642,7 +471,7 @@ __global__ __launch_bounds__(256) void range_match(const float4* __restrict__ Qw
     for (int j = 0; j < tn; ++j) {
       const float4 e = s_e[j];
       const V3 d = {sub(e2.x, e.x), sub(e2.y, e.y), sub(e2.z, e.z)};
-      if (sqnorm(d) < sqdist) {   // strict; NaN never
+      if (sqnorm_eigen(d) < sqdist) {   // strict; NaN never
         if (FILL && out0 + found < cap) {
           const int2 pp = Pp[(t0 + j) / 2];   // sic: P_pairs[id / 2]
           quads[out0 + found] = make_int4(pp.x, pp.y, qr.x, qr.y);
@@ -715,103 +544,6 @@ int launch_extract_pairs(pgp_ctx* ctx, float pair_distance, float eps, int* d_pa
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }
-
-int launch_find_congruent(pgp_ctx* ctx, const float base[12], float inv1, float inv2, float threshold,
-                          const int* d_Pp, int nP, const int* d_Qp, int nQ, int* d_quads, int cap,
-                          int* n_quads_host, hipStream_t st) {
-  *n_quads_host = 0;
-  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
-    set_error("no search model: call pgp_set_search_model first");
-    return PGP_ESTATE;
-  }
-  if (nP <= 0 || nQ <= 0) return PGP_OK;
-  CsArgs a{};
-  const float eps = threshold / ctx->cs_ratio;          // getNormalizedEpsilon
-  const int gridDepth = (int)(-std::log2(eps));          // normalset.h:116
-  if (!(eps > 0.f) || gridDepth < 0 || gridDepth > 20) {
-    set_error("find_congruent: threshold %g gives an unusable grid depth %d", (double)threshold, gridDepth);
-    return PGP_EINVAL;
-  }
-  a.eg = (int)std::pow(2, gridDepth);
-  a.epsilon = 1.f / (float)a.eg;
-  a.nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);  // normalset.h:88
-  // per-base constants, host libm exactly as the reference evaluates them (cone_for_base)
-  ConeTable cone{};
-  cone.nb = cone_for_base(base, &cone.v[0][0]);
-  // ---- buffers -------------------------------------------------------------------------------
-  unsigned nbk = 1024;
-  while (nbk < 2u * (unsigned)nP && nbk < (1u << 24)) nbk <<= 1;
-  a.bmask = nbk - 1;
-  int rc;
-  const size_t n_cnt = (size_t)nbk + 1 + (size_t)nQ + 1;
-  if ((rc = ctx->d_cs_cnt.ensure(n_cnt * 8 + 64)) != PGP_OK) return rc;
-  if ((rc = ctx->d_cs_entries.ensure((size_t)nP * 16 + 16)) != PGP_OK) return rc;
-  if ((rc = ctx->d_scan_tmp.ensure((n_cnt / 2048 + 2) * 4)) != PGP_OK) return rc;
-  uint32_t* bcnt = ctx->d_cs_cnt.as<uint32_t>();
-  uint32_t* bstart = bcnt + (nbk + 1);
-  uint32_t* qcnt = bstart + (nbk + 1);
-  uint32_t* qstart = qcnt + (nQ + 1);
-  a.Qw = ctx->d_Qs.as<float4>();
-  a.Qu = ctx->d_Qs_unit.as<float4>();
-  a.nQs = ctx->nQs;
-  a.Pp = reinterpret_cast<const int2*>(d_Pp);
-  a.nP = nP;
-  a.Qp = reinterpret_cast<const int2*>(d_Qp);
-  a.nQ = nQ;
-  a.inv1 = inv1;
-  a.inv2 = inv2;
-  a.threshold = threshold;
-  a.bucket_cnt = bcnt;
-  a.bucket_start = bstart;
-  a.entries = ctx->d_cs_entries.as<int4>();
-  a.q_cnt = qcnt;
-  a.q_start = qstart;
-  a.cap = (uint32_t)(cap > 0 ? cap : 0);
-  uint32_t* scan_tmp = ctx->d_scan_tmp.as<uint32_t>();
-  const dim3 gp((nP + 255) / 256), gq((nQ + 127) / 128);
-  PGP_HIP(hipMemsetAsync(bcnt, 0, ((size_t)nbk + 1) * 4, st));
-  hipLaunchKernelGGL(p_entries<false>, gp, dim3(256), 0, st, a);
-  if ((rc = device_exclusive_scan(bcnt, bstart, (size_t)nbk + 1, scan_tmp, st)) != PGP_OK) return rc;
-  PGP_HIP(hipMemsetAsync(bcnt, 0, ((size_t)nbk + 1) * 4, st));
-  hipLaunchKernelGGL(p_entries<true>, gp, dim3(256), 0, st, a);
-  PGP_HIP(hipMemsetAsync(qcnt + nQ, 0, 4, st));
-  hipLaunchKernelGGL(q_match<false>, gq, dim3(128), 0, st, a, cone);
-  if ((rc = device_exclusive_scan(qcnt, qstart, (size_t)nQ + 1, scan_tmp, st)) != PGP_OK) return rc;
-  uint32_t total = 0;
-  PGP_HIP(hipMemcpyAsync(&total, qstart + nQ, 4, hipMemcpyDeviceToHost, st));
-  PGP_HIP(hipStreamSynchronize(st));
-  *n_quads_host = (int)total;
-  if (total == 0 || cap <= 0) return PGP_OK;
-  // all matches are materialised and sorted, then the first `cap` are emitted: truncation keeps
-  // the reference's (id, i) order
-  size_t sort_bytes = 0;
-  hipError_t he = rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (size_t)total, 0, 64, st);
-  if (he != hipSuccess) {
-    set_error("rocprim::radix_sort_keys (size query) failed: %s", hipGetErrorString(he));
-    return PGP_EHIP;
-  }
-  ctx->csb_fit_m = 0;
-  ctx->csb_nb = 0;   // the batch's sorted keys (if any) are overwritten here
-  if ((rc = ctx->d_cs_keys.ensure((size_t)total * 16 + sort_bytes + 256)) != PGP_OK) return rc;
-  unsigned long long* keys_in = ctx->d_cs_keys.as<unsigned long long>();
-  unsigned long long* keys_out = keys_in + total;
-  void* sort_tmp = keys_out + total;
-  a.keys = keys_in;
-  a.cap = total;
-  hipLaunchKernelGGL(q_match<true>, gq, dim3(128), 0, st, a, cone);
-  he = rocprim::radix_sort_keys(sort_tmp, sort_bytes, keys_in, keys_out, (size_t)total, 0, 64, st);
-  if (he != hipSuccess) {
-    set_error("rocprim::radix_sort_keys failed: %s", hipGetErrorString(he));
-    return PGP_EHIP;
-  }
-  const uint32_t n_emit = total < (uint32_t)cap ? total : (uint32_t)cap;
-  hipLaunchKernelGGL(emit_quads, dim3((n_emit + 255) / 256), dim3(256), 0, st,
-                     (const unsigned long long*)keys_out, n_emit, a.Pp, a.Qp, reinterpret_cast<int4*>(d_quads));
-  PGP_HIP(hipGetLastError());
-  return PGP_OK;
-}
-
 
 namespace {
 
@@ -894,11 +626,30 @@ struct StageClock {
   }
 };
 
+// d_csb: bases | cones | base_start, each piece on a 256-byte boundary (bases and cones are uploaded as one image)
+struct CsbLayout {
+  Carve c;
+  Carve::Piece<BatchBase> bases;
+  Carve::Piece<float> cones;           // [nb][56][3]
+  Carve::Piece<uint32_t> base_start;   // [nb + 1]
+  explicit CsbLayout(int nb) {
+    bases = c.add<BatchBase>((size_t)nb, 256);
+    cones = c.add<float>((size_t)nb * 168, 256);
+    base_start = c.add<uint32_t>((size_t)nb + 1, 256);
+    c.pad(64);
+  }
+};
+
+// whose pair array a batch's ranges index: the pair-feature table's d_ppf_pairs, d_s4_pairs (pgp_extract_pairs_batch), or the
+// staging buffer of pgp_find_congruent -- the next such call overwrites that one, so a batch on it is never left resident
+enum class PairSource { kTable, kLists, kStaged };
+
 // The join for nb bases whose pair lists are the ranges (p_off, p_cnt) / (q_off, q_cnt) of d_pairs, filled in by a front
-// below (both counts 0: no quads for that base): leaves the sorted match keys and the per-base starts in the context.
-// from_lists: d_pairs is the context's d_s4_pairs (pgp_extract_pairs_batch), else the pair-feature table's d_ppf_pairs.
-int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std::vector<BatchBase>& hb, const float* h_base_xyz,
-                         const float* h_inv, int nb, float threshold, int* h_n_quads, hipStream_t st, StageClock& stage) {
+// below (both counts 0: no quads for that base): leaves the sorted match keys in d_cs_keys (from csb_keys_off on) and the
+// per-base starts in d_csb, and makes the batch resident unless its pairs are staged.  `who` names the caller in error texts.
+int congruent_batch_body(pgp_ctx* ctx, const char* who, const int2* d_pairs, PairSource src, std::vector<BatchBase>& hb,
+                         const float* h_base_xyz, const float* h_inv, int nb, float threshold, int* h_n_quads, hipStream_t st,
+                         StageClock& stage) {
   const bool timing = stage.on;
   int rc = PGP_OK;
   const float eps = threshold / ctx->cs_ratio;          // getNormalizedEpsilon
@@ -914,7 +665,7 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
     B.inv1 = h_inv[2 * b];
     B.inv2 = h_inv[2 * b + 1];
     if (B.p_cnt >= (1u << 24) || B.q_cnt >= (1u << 24)) {
-      set_error("pgp_find_congruent_batch: a pair list exceeds 2^24 entries");
+      set_error("%s: a pair list exceeds 2^24 entries", who);
       return PGP_EINVAL;
     }
     B.p_flat = (uint32_t)tp;
@@ -925,7 +676,7 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
     B.pad = 0;
   }
   if (tp >= (1ull << 31) || tq >= (1ull << 31)) {
-    set_error("pgp_find_congruent_batch: more than 2^31 pairs in one batch");
+    set_error("%s: more than 2^31 pairs in one batch", who);
     return PGP_EINVAL;
   }
   if (tp == 0 || tq == 0) return PGP_OK;
@@ -941,29 +692,28 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
   const size_t n_cnt = (size_t)nbk + (size_t)tp + (size_t)nb + 4;
   if ((rc = ctx->d_cs_cnt.ensure(n_cnt * 4 + 64)) != PGP_OK) return rc;
   if ((rc = ctx->d_cs_entries.ensure((size_t)tp * 16 + 16)) != PGP_OK) return rc;
-  // bases | cones | base_start, in one staging buffer
-  const size_t bb = ((size_t)nb * sizeof(BatchBase) + 255) & ~(size_t)255, cb = ((size_t)nb * 168 * 4 + 255) & ~(size_t)255;
-  if ((rc = ctx->d_csb.ensure(bb + cb + ((size_t)nb + 1) * 4 + 64)) != PGP_OK) return rc;
-  unsigned char* sb = ctx->d_csb.as<unsigned char>();
-  BatchBase* d_bases = reinterpret_cast<BatchBase*>(sb);
-  float* d_cones = reinterpret_cast<float*>(sb + bb);
-  uint32_t* d_base_start = reinterpret_cast<uint32_t*>(sb + bb + cb);
+  CsbLayout lay(nb);
+  if ((rc = lay.c.ensure(ctx->d_csb)) != PGP_OK) return rc;
+  BatchBase* d_bases = lay.c.at(lay.bases);
+  float* d_cones = lay.c.at(lay.cones);
+  uint32_t* d_base_start = lay.c.at(lay.base_start);
+  const size_t bb = lay.cones.off, image = lay.base_start.off;   // the host image: bases | cones
   // bases and cones in ONE copy (a pageable copy costs the call ~10 us whatever its size); the staging vector lives until
   // the stream is synchronised below
   // (in the context's pinned area when there is room: the pageable form costs the host ~10 us)
   HostOut staging(ctx, st);
   std::vector<unsigned char> stage_h;
-  unsigned char* stage_p = staging.room(bb + cb);
+  unsigned char* stage_p = staging.room(image);
   if (!stage_p) {
-    stage_h.assign(bb + cb, 0);
+    stage_h.assign(image, 0);
     stage_p = stage_h.data();
   }
   std::memcpy(stage_p, hb.data(), (size_t)nb * sizeof(BatchBase));
   std::memcpy(stage_p + bb, cones.data(), (size_t)nb * 168 * 4);
   if (stage_h.empty()) {   // (the pinned area: by a kernel on the stream)
-    if ((rc = stage_to_device(st, d_bases, stage_p, bb + cb)) != PGP_OK) return rc;
+    if ((rc = stage_to_device(st, d_bases, stage_p, image)) != PGP_OK) return rc;
   } else {
-    PGP_HIP(hipMemcpyAsync(d_bases, stage_p, bb + cb, hipMemcpyHostToDevice, st));
+    PGP_HIP(hipMemcpyAsync(d_bases, stage_p, image, hipMemcpyHostToDevice, st));
   }
   int* head = ctx->d_cs_cnt.as<int>();
   int* next = head + nbk;
@@ -1028,11 +778,15 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
                       (unsigned long long)tp, (unsigned long long)tq, nbk, total);
   ctx->csb_cap_hint = std::max<uint32_t>(2u * total, 1u << 16);
   for (int b = 0; b < nb; ++b) h_n_quads[b] = (int)(starts[b + 1] - starts[b]);
-  if (total == 0) {   // a valid, empty batch: every pick is out of range
+  const auto publish = [&] {   // the batch becomes visible to pgp_congruent_batch_quads / _fit
+    if (src == PairSource::kStaged) return;
     ctx->csb_starts = starts;
     ctx->csb_nb = nb;
-    ctx->csb_lists = from_lists;
-    ctx->csb_total = 0;
+    ctx->csb_lists = src == PairSource::kLists;
+    ctx->csb_total = total;
+  };
+  if (total == 0) {   // a valid, empty batch: every pick is out of range
+    publish();
     return PGP_OK;
   }
   unsigned long long* keys_in = ctx->d_cs_keys.as<unsigned long long>();
@@ -1048,12 +802,48 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
   }
   PGP_HIP(hipGetLastError());
   stage("sort");
-  // only now do the sorted keys exist: the batch becomes visible to pgp_congruent_batch_quads / _fit
-  ctx->csb_starts = starts;
-  ctx->csb_nb = nb;
-  ctx->csb_lists = from_lists;
-  ctx->csb_total = total;
+  publish();   // only now do the sorted keys exist
   return PGP_OK;
+}
+
+// What every front does first: whatever batch and fits are resident are gone from here on (the body rewrites d_csb and
+// d_cs_keys), then the state a join needs.  have_pairs / no_pairs: the front's own source of pair lists.
+int batch_entry(pgp_ctx* ctx, bool have_pairs, const char* no_pairs) {
+  ctx->csb_fit_m = 0;
+  ctx->csb_nb = 0;
+  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
+    set_error("no search model: call pgp_set_search_model first");
+    return PGP_ESTATE;
+  }
+  if (!have_pairs) {
+    set_error("%s", no_pairs);
+    return PGP_ESTATE;
+  }
+  return PGP_OK;
+}
+
+// ... and what the two many-base fronts do next
+int batch_bases(const char* who, int nb, int* h_n_quads) {
+  if (nb > 65535) {   // bq_match keeps a base number in 16 bits
+    set_error("%s: at most 65535 bases per call", who);
+    return PGP_EINVAL;
+  }
+  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
+  return PGP_OK;
+}
+
+// lists l1 / l6 of the CSR offsets `off` as a base's P / Q ranges (l < 0: no such list).  pairs1.size() == 0 ||
+// pairs6.size() == 0 -> no quads for this base (base.cc:1984): both ranges stay empty
+void base_ranges(BatchBase& B, const std::vector<uint32_t>& off, int l1, int l6) {
+  B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
+  if (l1 < 0 || l6 < 0) return;
+  const uint32_t c1 = off[l1 + 1] - off[l1], c6 = off[l6 + 1] - off[l6];
+  if (c1 > 0 && c6 > 0) {
+    B.p_off = off[l1];
+    B.p_cnt = c1;
+    B.q_off = off[l6];
+    B.q_cnt = c6;
+  }
 }
 
 }  // namespace
@@ -1062,22 +852,9 @@ int congruent_batch_body(pgp_ctx* ctx, const int2* d_pairs, bool from_lists, std
 // ranges of d_ppf_pairs, then the body above.
 int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float* h_base_xyz, const float* h_inv,
                                 const int* h_rows, int nb, float threshold, int* h_n_quads, hipStream_t st) {
-  ctx->csb_fit_m = 0;
-  ctx->csb_nb = 0;
-  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
-    set_error("no search model: call pgp_set_search_model first");
-    return PGP_ESTATE;
-  }
-  if (!ctx->ppf_ready || ctx->ppf_n_pairs <= 0) {
-    set_error("no pair-feature table with pair lists: call pgp_set_ppf_map(keys, counts, pairs) first");
-    return PGP_ESTATE;
-  }
-  if (nb > 65535) {
-    set_error("pgp_find_congruent_batch: at most 65535 bases per call");
-    return PGP_EINVAL;
-  }
-  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
-  if (nb == 0) return PGP_OK;
+  int rc = batch_entry(ctx, ctx->ppf_ready && ctx->ppf_n_pairs > 0,
+                       "no pair-feature table with pair lists: call pgp_set_ppf_map(keys, counts, pairs) first");
+  if (rc != PGP_OK || (rc = batch_bases("pgp_find_congruent_batch", nb, h_n_quads)) != PGP_OK || nb == 0) return rc;
   StageClock stage(st);
   // ---- which rows of the table are pairs1 / pairs6 of every base: computePPF on the device
   std::vector<int> edge_pairs((size_t)nb * 4), rows((size_t)nb * 2);
@@ -1087,7 +864,6 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
     edge_pairs[4 * b + 2] = h_base_ids[4 * b + 2];   // computePPF(base_id3, base_id4)
     edge_pairs[4 * b + 3] = h_base_ids[4 * b + 3];
   }
-  int rc = PGP_OK;
   if (h_rows) {   // the caller holds them already (pgp_select_bases_rows): one launch and one round trip less
     const int n_rows = (int)ctx->ppf_off_host.size() - 1;
     for (int k = 0; k < 2 * nb; ++k) {
@@ -1103,61 +879,58 @@ int launch_find_congruent_batch(pgp_ctx* ctx, const int* h_base_ids, const float
   }
   stage("pair features of the bases");
   std::vector<BatchBase> hb((size_t)nb);
-  for (int b = 0; b < nb; ++b) {
-    BatchBase& B = hb[b];
-    const int r1 = rows[2 * b], r6 = rows[2 * b + 1];
-    B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
-    if (r1 >= 0 && r6 >= 0) {   // pairs1.size() == 0 || pairs6.size() == 0 -> no quads for this base
-      const uint32_t c1 = ctx->ppf_off_host[r1 + 1] - ctx->ppf_off_host[r1], c6 = ctx->ppf_off_host[r6 + 1] - ctx->ppf_off_host[r6];
-      if (c1 > 0 && c6 > 0) {
-        B.p_off = ctx->ppf_off_host[r1];
-        B.p_cnt = c1;
-        B.q_off = ctx->ppf_off_host[r6];
-        B.q_cnt = c6;
-      }
-    }
-  }
-  return congruent_batch_body(ctx, ctx->d_ppf_pairs.as<int2>(), false, hb, h_base_xyz, h_inv, nb, threshold, h_n_quads, st, stage);
+  for (int b = 0; b < nb; ++b) base_ranges(hb[b], ctx->ppf_off_host, rows[2 * b], rows[2 * b + 1]);   // (row -1: no such key)
+  return congruent_batch_body(ctx, "pgp_find_congruent_batch", ctx->d_ppf_pairs.as<int2>(), PairSource::kTable, hb, h_base_xyz,
+                              h_inv, nb, threshold, h_n_quads, st, stage);
 }
 
 // The same for bases whose pair lists are lists of the last pgp_extract_pairs_batch (mode 0): h_lists[nb][2] = (pairs1, pairs6).
 int launch_find_congruent_batch_lists(pgp_ctx* ctx, const float* h_base_xyz, const float* h_inv, const int* h_lists, int nb,
                                       float threshold, int* h_n_quads, hipStream_t st) {
-  ctx->csb_fit_m = 0;
-  ctx->csb_nb = 0;
-  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
-    set_error("no search model: call pgp_set_search_model first");
-    return PGP_ESTATE;
-  }
-  if (ctx->s4_nl <= 0 || (int)ctx->s4_off.size() != ctx->s4_nl + 1) {
-    set_error("no pair lists: call pgp_extract_pairs_batch first (pgp_set_search_model discards them)");
-    return PGP_ESTATE;
-  }
-  if (nb > 65535) {
-    set_error("pgp_find_congruent_batch_lists: at most 65535 bases per call");
-    return PGP_EINVAL;
-  }
-  for (int b = 0; b < nb; ++b) h_n_quads[b] = 0;
-  if (nb == 0) return PGP_OK;
+  int rc = batch_entry(ctx, ctx->s4_nl > 0 && (int)ctx->s4_off.size() == ctx->s4_nl + 1,
+                       "no pair lists: call pgp_extract_pairs_batch first (pgp_set_search_model discards them)");
+  if (rc != PGP_OK || (rc = batch_bases("pgp_find_congruent_batch_lists", nb, h_n_quads)) != PGP_OK || nb == 0) return rc;
   StageClock stage(st);
   std::vector<BatchBase> hb((size_t)nb);
   for (int b = 0; b < nb; ++b) {
-    BatchBase& B = hb[b];
     const int l1 = h_lists[2 * b], l6 = h_lists[2 * b + 1];
     if (l1 < 0 || l1 >= ctx->s4_nl || l6 < 0 || l6 >= ctx->s4_nl) {
       set_error("pgp_find_congruent_batch_lists: base %d names lists %d and %d of %d", b, l1, l6, ctx->s4_nl);
       return PGP_EINVAL;
     }
-    B.p_off = B.p_cnt = B.q_off = B.q_cnt = 0;
-    const uint32_t c1 = ctx->s4_off[l1 + 1] - ctx->s4_off[l1], c6 = ctx->s4_off[l6 + 1] - ctx->s4_off[l6];
-    if (c1 > 0 && c6 > 0) {   // pairs1.size() == 0 || pairs6.size() == 0 -> no quads for this base (base.cc:1984)
-      B.p_off = ctx->s4_off[l1];
-      B.p_cnt = c1;
-      B.q_off = ctx->s4_off[l6];
-      B.q_cnt = c6;
-    }
+    base_ranges(hb[b], ctx->s4_off, l1, l6);
   }
-  return congruent_batch_body(ctx, ctx->d_s4_pairs.as<int2>(), true, hb, h_base_xyz, h_inv, nb, threshold, h_n_quads, st, stage);
+  return congruent_batch_body(ctx, "pgp_find_congruent_batch_lists", ctx->d_s4_pairs.as<int2>(), PairSource::kLists, hb,
+                              h_base_xyz, h_inv, nb, threshold, h_n_quads, st, stage);
+}
+
+// FindCongruentQuadrilaterals for ONE base whose lists the host passed in (pgp_find_congruent): d_pairs = P_pairs | Q_pairs.
+// A batch of one base on that array; the first min(cap, total) quads, in key order, go to d_quads.  No batch is resident
+// afterwards, whatever the call finds.
+int launch_find_congruent(pgp_ctx* ctx, const float base[12], float inv1, float inv2, float threshold, const int2* d_pairs,
+                          int nP, int nQ, int4* d_quads, int cap, int* n_quads_host, hipStream_t st) {
+  *n_quads_host = 0;
+  int rc = batch_entry(ctx, true, nullptr);
+  if (rc != PGP_OK || nP <= 0 || nQ <= 0) return rc;
+  std::vector<BatchBase> hb(1);
+  hb[0].p_off = 0;
+  hb[0].p_cnt = (uint32_t)nP;
+  hb[0].q_off = (uint32_t)nP;
+  hb[0].q_cnt = (uint32_t)nQ;
+  const float inv[2] = {inv1, inv2};
+  StageClock stage(st);
+  rc = congruent_batch_body(ctx, "pgp_find_congruent", d_pairs, PairSource::kStaged, hb, base, inv, 1, threshold, n_quads_host,
+                            st, stage);
+  const int n_emit = std::min(*n_quads_host, cap);
+  if (rc != PGP_OK || n_emit <= 0) return rc;
+  CsbLayout lay(1);
+  lay.c.bind(ctx->d_csb);
+  const unsigned long long* keys_out = ctx->d_cs_keys.as<unsigned long long>() + ctx->csb_keys_off;
+  hipLaunchKernelGGL(batch_gather, dim3((n_emit + 255) / 256), dim3(256), 0, st, keys_out,
+                     (const uint32_t*)lay.c.at(lay.base_start), (const BatchBase*)lay.c.at(lay.bases), d_pairs,
+                     (const int2*)nullptr, n_emit, d_quads);
+  PGP_HIP(hipGetLastError());
+  return PGP_OK;
 }
 
 // picks[m][2] = (base, j) -> d_quads[m] (int4), on the sorted keys left by the call above
@@ -1192,11 +965,10 @@ int launch_congruent_batch_gather(pgp_ctx* ctx, const int* h_picks, int m, int4*
     PGP_HIP(hipMemcpyAsync(ctx->d_csb_picks.p, h_picks, (size_t)m * 8, hipMemcpyHostToDevice, st));
     d_picks = ctx->d_csb_picks.as<int2>();
   }
-  const int nb = ctx->csb_nb;
-  const size_t bb = ((size_t)nb * sizeof(BatchBase) + 255) & ~(size_t)255, cb = ((size_t)nb * 168 * 4 + 255) & ~(size_t)255;
-  unsigned char* sb = ctx->d_csb.as<unsigned char>();
-  const BatchBase* d_bases = reinterpret_cast<const BatchBase*>(sb);
-  const uint32_t* d_base_start = reinterpret_cast<const uint32_t*>(sb + bb + cb);
+  CsbLayout lay(ctx->csb_nb);
+  lay.c.bind(ctx->d_csb);
+  const BatchBase* d_bases = lay.c.at(lay.bases);
+  const uint32_t* d_base_start = lay.c.at(lay.base_start);
   const unsigned long long* keys_out = ctx->d_cs_keys.as<unsigned long long>() + ctx->csb_keys_off;
   hipLaunchKernelGGL(batch_gather, dim3((m + 255) / 256), dim3(256), 0, st, keys_out, d_base_start, d_bases,
                      (const int2*)(ctx->csb_lists ? ctx->d_s4_pairs : ctx->d_ppf_pairs).as<int2>(), d_picks, m, d_quads);
@@ -1207,9 +979,9 @@ int launch_congruent_batch_gather(pgp_ctx* ctx, const int* h_picks, int m, int4*
 
 // where the resident batch's per-base starts (nb + 1 words) live on the device
 const uint32_t* congruent_batch_starts_device(pgp_ctx* ctx) {
-  const int nb = ctx->csb_nb;
-  const size_t bb = ((size_t)nb * sizeof(BatchBase) + 255) & ~(size_t)255, cb = ((size_t)nb * 168 * 4 + 255) & ~(size_t)255;
-  return reinterpret_cast<const uint32_t*>(ctx->d_csb.as<unsigned char>() + bb + cb);
+  CsbLayout lay(ctx->csb_nb);
+  lay.c.bind(ctx->d_csb);
+  return lay.c.at(lay.base_start);
 }
 
 int launch_find_congruent_4pcs(pgp_ctx* ctx, float inv1, float inv2, float threshold, const int* d_Pp, int nP,

@@ -1284,18 +1284,21 @@ int pgp_find_congruent(pgp_ctx* ctx, const float* base, float invariant1, float 
   }
   *n_quads = 0;
   if (nP == 0 || nQ == 0) return PGP_OK;
+  if (nP >= (1 << 24) || nQ >= (1 << 24)) {   // the join's keys hold a pair index in 24 bits; refused before any upload
+    set_error("pgp_find_congruent: a pair list exceeds 2^24 entries");
+    return PGP_EINVAL;
+  }
   CtxGuard guard(ctx);
   hipStream_t st = ctx->stream;
   int rc;
   if ((rc = ctx->d_cs_pairs.ensure(((size_t)nP + nQ) * 8)) != PGP_OK) return rc;
   if ((rc = ctx->d_cs_out.ensure((size_t)std::max(cap, 1) * 16)) != PGP_OK) return rc;
-  int* d_Pp = ctx->d_cs_pairs.as<int>();
-  int* d_Qp = d_Pp + 2 * (size_t)nP;
-  PGP_HIP(hipMemcpyAsync(d_Pp, P_pairs, (size_t)nP * 8, hipMemcpyHostToDevice, st));
-  PGP_HIP(hipMemcpyAsync(d_Qp, Q_pairs, (size_t)nQ * 8, hipMemcpyHostToDevice, st));
+  int2* d_pairs = ctx->d_cs_pairs.as<int2>();   // P_pairs | Q_pairs
+  PGP_HIP(hipMemcpyAsync(d_pairs, P_pairs, (size_t)nP * 8, hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(d_pairs + nP, Q_pairs, (size_t)nQ * 8, hipMemcpyHostToDevice, st));
   int total = 0;
-  rc = launch_find_congruent(ctx, base, invariant1, invariant2, threshold, d_Pp, nP, d_Qp, nQ,
-                             ctx->d_cs_out.as<int>(), cap, &total, st);
+  rc = launch_find_congruent(ctx, base, invariant1, invariant2, threshold, d_pairs, nP, nQ, ctx->d_cs_out.as<int4>(), cap,
+                             &total, st);
   if (rc != PGP_OK) return rc;
   int n_copy = std::min(total, cap);
   if (n_copy > 0)

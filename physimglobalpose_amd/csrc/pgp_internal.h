@@ -506,9 +506,9 @@ int device_exclusive_scan(const uint32_t* in, uint32_t* out, size_t n, uint32_t*
 void unit_cube_image(const float* xyz, int n, float gcenter[3], float* ratio, std::vector<float4>* unit);
 int launch_extract_pairs(pgp_ctx* ctx, float pair_distance, float eps, int* d_pairs, int cap,
                          int* n_pairs_host, hipStream_t st);
-int launch_find_congruent(pgp_ctx* ctx, const float base[12], float inv1, float inv2, float threshold,
-                          const int* d_Pp, int nP, const int* d_Qp, int nQ, int* d_quads, int cap,
-                          int* n_quads_host, hipStream_t st);
+// d_pairs = P_pairs | Q_pairs (nP + nQ pairs); a batch of one base
+int launch_find_congruent(pgp_ctx* ctx, const float base[12], float inv1, float inv2, float threshold, const int2* d_pairs,
+                          int nP, int nQ, int4* d_quads, int cap, int* n_quads_host, hipStream_t st);
 
 int launch_find_congruent_4pcs(pgp_ctx* ctx, float inv1, float inv2, float threshold, const int* d_Pp, int nP,
                                const int* d_Qp, int nQ, int* d_quads, int cap, int* n_quads_host, hipStream_t st);

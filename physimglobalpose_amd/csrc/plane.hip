@@ -26,6 +26,7 @@
 // distance from the float coefficients, dist < threshold zeroes the pixel.
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 #include "eigen33.h"
 
 #include <cfloat>
@@ -45,7 +46,7 @@ constexpr int kAttempts = 64;                    // draws per slot before it is 
 constexpr int kSelThreads = 1024;
 constexpr int kMaxCandidates = 65535;
 
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
+using exact::sqrt_rn;   // exact_f32.h
 
 __device__ __forceinline__ float plane_dist(float4 q, float x, float y, float z) {
   return fabsf(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(q.x, x), __fmul_rn(q.y, y)), __fmul_rn(q.z, z)), q.w));

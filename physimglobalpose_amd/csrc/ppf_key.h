@@ -4,28 +4,12 @@
 #pragma once
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 
 namespace pgp {
 namespace ppfk {
 
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
-__device__ __forceinline__ float sum3(float a, float b, float c) { return add(a, add(b, c)); }  // Eigen: a + (b + c)
-__device__ __forceinline__ float dot(V3 a, V3 b) { return sum3(mul(a.x, b.x), mul(a.y, b.y), mul(a.z, b.z)); }
-__device__ __forceinline__ float norm(V3 v) { return sqrt_rn(dot(v, v)); }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
-__device__ __forceinline__ V3 ld3(const float4* __restrict__ a, int i) {
-  const float4 v = a[i];
-  return {v.x, v.y, v.z};
-}
+using namespace exact;   // exact_f32.h: V3, ld3, vsub, cross, ...; the key and the base geometry sum as Eigen does (_eigen)
 
 struct PpfTable {
   const unsigned long long* keys;  // open addressing, ~0ull = empty
@@ -62,10 +46,10 @@ __device__ __forceinline__ int angle_bin(const PpfTable& t, float y, float x) {
 // computePPF(i1, i2) packed as f1 << 24 | f2 << 16 | f3 << 8 | f4, or ~0ull when it is no key
 __device__ __forceinline__ unsigned long long ppf_key(const PpfTable& t, V3 p1, V3 n1, V3 p2, V3 n2, int* f) {
   const V3 u = vsub(p1, p2);
-  const int f1 = approximate_bin((int)mul(norm(u), 1000.0f), t.trans_disc);
-  const int f2 = angle_bin(t, norm(cross(n1, u)), dot(n1, u));
-  const int f3 = angle_bin(t, norm(cross(n2, u)), dot(n2, u));
-  const int f4 = angle_bin(t, norm(cross(n1, n2)), dot(n1, n2));
+  const int f1 = approximate_bin((int)mul(norm_eigen(u), 1000.0f), t.trans_disc);
+  const int f2 = angle_bin(t, norm_eigen(cross(n1, u)), dot_eigen(n1, u));
+  const int f3 = angle_bin(t, norm_eigen(cross(n2, u)), dot_eigen(n2, u));
+  const int f4 = angle_bin(t, norm_eigen(cross(n1, n2)), dot_eigen(n1, n2));
   if (f) {
     f[0] = f1;
     f[1] = f2;

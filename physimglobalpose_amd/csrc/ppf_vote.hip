@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void ppf_vote_kernel(VoteArgs a) {
       if (j < a.nP && j != r) {
         const V3 pj = ld3(a.P, j);
         const V3 u = vsub(pr, pj);
-        if (dot(u, u) <= a.skip2) {
+        if (sqnorm_eigen(u) <= a.skip2) {
           const int row = table_find(a.tab, ppf_key(a.tab, pr, nr, pj, v3(a.Pnw[j]), nullptr));
           if (row >= 0) {
             first = (int)a.off[row];

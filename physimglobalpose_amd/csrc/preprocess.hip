@@ -23,6 +23,7 @@
 #include <cstring>  // rocprim's texture_cache_iterator.hpp uses memset without including it
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -34,7 +35,7 @@ namespace pgp {
 
 namespace {
 
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
+using exact::sqrt_rn;   // exact_f32.h
 
 // ---- bounding box over finite points: per-block partials, the host folds them ------------------
 template <int STRIDE>   // floats per point: 3 (packed xyz) or 4 (float4)

@@ -8,7 +8,7 @@
 // base.cc:1468) and the de-centred double pose returned to the node (`allPose`, :1484).
 //
 // Float parity: every expression is evaluated in Eigen's order with separately rounded
-// operations, IEEE sqrt and divide (sqrt_rn below, __fdiv_rn) -- the centred transform and the rms
+// operations, IEEE sqrt and divide (exact_f32.h) -- the centred transform and the rms
 // are bit-identical to the reference expressions (pinned via oracle/, tests/golden/rigid_fit.npz).
 // The de-centred translation uses the linear part where the reference multiplies the SVD polar
 // factors rot*scale (computeRotationScaling, base.cc:1480): equal to ~1e-7.
@@ -18,63 +18,28 @@
 // never leaves HBM.
 
 #include "pgp_internal.h"
+#include "exact_f32.h"
 
 namespace pgp {
 
 namespace {
 
-struct V3 {
-  float x, y, z;
-};
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-
-// Correctly rounded float sqrt.  ROCm 7.2's __fsqrt_rn / sqrtf are 1 ulp off for ~15 % of inputs
-// on gfx950 (measured: 632 495 of 4 194 304 random values differ from IEEE sqrtf), the double
-// square root is exact, and rounding a 53-bit correctly rounded root to 24 bits is innocuous.
-__device__ __forceinline__ float sqrt_rn(float z) { return (float)__dsqrt_rn((double)z); }
-
-__device__ __forceinline__ float sum3(float a, float b, float c) { return add(a, add(b, c)); }  // a + (b + c)
-__device__ __forceinline__ float sqnorm(V3 v) { return sum3(mul(v.x, v.x), mul(v.y, v.y), mul(v.z, v.z)); }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return sum3(mul(a.x, b.x), mul(a.y, b.y), mul(a.z, b.z)); }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-
-__device__ __forceinline__ V3 normalized(V3 v) {  // Eigen normalize(): if z > 0: v /= sqrt(z)
-  float z = sqnorm(v);
-  if (z > 0.f) {
-    float n = sqrt_rn(z);
-    v.x = __fdiv_rn(v.x, n);
-    v.y = __fdiv_rn(v.y, n);
-    v.z = __fdiv_rn(v.z, n);
-  }
-  return v;
-}
-
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
+using namespace exact;   // exact_f32.h; every three-term sum here is Eigen's a + (b + c)
 
 // Gram-Schmidt frame of base.cc:1532-1546; false on the degenerate exits
 __device__ __forceinline__ bool frame(V3 a0, V3 a1, V3 a2, V3* v1, V3* v2, V3* v3) {
   V3 e1 = vsub(a1, a0);
-  if (sqnorm(e1) == 0.f) return false;
+  if (sqnorm_eigen(e1) == 0.f) return false;
   e1 = normalized(e1);
   V3 d = vsub(a2, a0);
-  float proj = dot(d, e1);
+  float proj = dot_eigen(d, e1);
   V3 e2 = {sub(d.x, mul(proj, e1.x)), sub(d.y, mul(proj, e1.y)), sub(d.z, mul(proj, e1.z))};
-  if (sqnorm(e2) == 0.f) return false;
+  if (sqnorm_eigen(e2) == 0.f) return false;
   e2 = normalized(e2);
   *v1 = e1;
   *v2 = e2;
   *v3 = cross(e1, e2);
   return true;
-}
-
-__device__ __forceinline__ V3 ld3(const float4* __restrict__ a, int i) {
-  float4 v = a[i];
-  return {v.x, v.y, v.z};
 }
 
 __device__ __forceinline__ float comp(V3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
@@ -125,11 +90,11 @@ __global__ __launch_bounds__(128) void rigid_from_congruent(const float4* __rest
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc)
-      R[r][cc] = sum3(mul(comp(fp1, r), comp(fq1, cc)), mul(comp(fp2, r), comp(fq2, cc)), mul(comp(fp3, r), comp(fq3, cc)));
+      R[r][cc] = sum3_eigen(mul(comp(fp1, r), comp(fq1, cc)), mul(comp(fp2, r), comp(fq2, cc)), mul(comp(fp3, r), comp(fq3, cc)));
   // discard non-orthogonal solutions: diag(R*R) - 1 > 1e-6 (base.cc:1563)
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    float d = sum3(mul(R[r][0], R[0][r]), mul(R[r][1], R[1][r]), mul(R[r][2], R[2][r]));
+    float d = sum3_eigen(mul(R[r][0], R[0][r]), mul(R[r][1], R[1][r]), mul(R[r][2], R[2][r]));
     if (sub(d, 1.0f) > 1e-6f) {
       fail(0, 1e9f);
       return;
@@ -141,11 +106,11 @@ __global__ __launch_bounds__(128) void rigid_from_congruent(const float4* __rest
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     V3 first = vsub({mul(1.0f, qq[k].x), mul(1.0f, qq[k].y), mul(1.0f, qq[k].z)}, c2);
-    V3 tr = {sum3(mul(R[0][0], first.x), mul(R[0][1], first.y), mul(R[0][2], first.z)),
-             sum3(mul(R[1][0], first.x), mul(R[1][1], first.y), mul(R[1][2], first.z)),
-             sum3(mul(R[2][0], first.x), mul(R[2][1], first.y), mul(R[2][2], first.z))};
+    V3 tr = {sum3_eigen(mul(R[0][0], first.x), mul(R[0][1], first.y), mul(R[0][2], first.z)),
+             sum3_eigen(mul(R[1][0], first.x), mul(R[1][1], first.y), mul(R[1][2], first.z)),
+             sum3_eigen(mul(R[2][0], first.x), mul(R[2][1], first.y), mul(R[2][2], first.z))};
     V3 e = {add(sub(tr.x, pp[k].x), c1.x), add(sub(tr.y, pp[k].y), c1.y), add(sub(tr.z, pp[k].z), c1.z)};
-    rms = add(rms, sqrt_rn(sqnorm(e)));
+    rms = add(rms, norm_eigen(e));
   }
   rms = __fdiv_rn(rms, 4.0f);
   if (!(rms >= 0.f)) {  // base.cc:1467 `ok && rms >= 0`
@@ -157,10 +122,10 @@ __global__ __launch_bounds__(128) void rigid_from_congruent(const float4* __rest
   V3 u = {add(c2.x, cQx), add(c2.y, cQy), add(c2.z, cQz)};
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    float s = sum3(mul(R[r][0], -c2.x), mul(R[r][1], -c2.y), mul(R[r][2], -c2.z));
+    float s = sum3_eigen(mul(R[r][0], -c2.x), mul(R[r][1], -c2.y), mul(R[r][2], -c2.z));
     t[r] = add(comp(c1, r), s);
     // de-centring (base.cc:1474-1482): (c1 + cP) - L (c2 + cQ)
-    float sw = sum3(mul(R[r][0], u.x), mul(R[r][1], u.y), mul(R[r][2], u.z));
+    float sw = sum3_eigen(mul(R[r][0], u.x), mul(R[r][1], u.y), mul(R[r][2], u.z));
     float cp = r == 0 ? cPx : (r == 1 ? cPy : cPz);
     tw[r] = sub(add(comp(c1, r), cp), sw);
   }

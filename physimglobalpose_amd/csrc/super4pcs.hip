@@ -33,17 +33,10 @@ namespace pgp {
 
 namespace {
 
+using namespace exact;   // exact_f32.h
+
 // ---------------- SelectQuadrilateral: a workgroup per attempt ----------------
 constexpr int kBaseThreads = 256;
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o, 64);
-    k = other < k ? other : k;
-  }
-  return k;
-}
 
 __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restrict__ P, int n, unsigned long long seed, int T,
                                                            float D, float too_small, int4* __restrict__ ids,
@@ -54,8 +47,8 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
   const unsigned long long st = sample_state(seed, a);
   const unsigned un = (unsigned)n;
   const int i0 = (int)(sample_variate(st, 0) % un);
-  const v4dev::V3 p0 = v4dev::ld3(P, i0);
-  const float DD = v4dev::mul(D, D);
+  const V3 p0 = ld3(P, i0);
+  const float DD = mul(D, D);
   // the widest triangle (base_device.h): trials strided over the workgroup
   unsigned long long best = v4dev::wave_max(v4dev::widest_triangle(P, un, st, T, DD, p0, tid, kBaseThreads));
   if (lane == 0) s_max[wave] = best;
@@ -70,15 +63,15 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
     const int i = v4dev::triangle_trial(best);
     i1 = (int)(sample_variate(st, 1 + 2 * i) % un);
     i2 = (int)(sample_variate(st, 2 + 2 * i) % un);
-    const v4dev::V3 p1 = v4dev::ld3(P, i1), p2 = v4dev::ld3(P, i2);
-    const ppfk::Plane pl = ppfk::fit_plane({p0.x, p0.y, p0.z}, {p1.x, p1.y, p1.z}, {p2.x, p2.y, p2.z});
+    const V3 p1 = ld3(P, i1), p2 = ld3(P, i2);
+    const ppfk::Plane pl = ppfk::fit_plane(p0, p1, p2);
     if (pl.denom != 0.f) {
       for (int k = tid; k < n; k += kBaseThreads) {
-        const v4dev::V3 p = v4dev::ld3(P, k);
-        const v4dev::V3 e0 = v4dev::vsub(p, p0), e1 = v4dev::vsub(p, p1), e2 = v4dev::vsub(p, p2);
-        if (v4dev::dot(e0, e0) >= too_small && v4dev::dot(e1, e1) >= too_small && v4dev::dot(e2, e2) >= too_small) {
+        const V3 p = ld3(P, k);
+        const V3 e0 = vsub(p, p0), e1 = vsub(p, p1), e2 = vsub(p, p2);
+        if (sqnorm_lr(e0) >= too_small && sqnorm_lr(e1) >= too_small && sqnorm_lr(e2) >= too_small) {
           // Scalar distance = std::abs(A x + B y + C z - 1.0): float products and sums, double minus
-          const float lin = v4dev::add(v4dev::add(v4dev::mul(pl.A, p.x), v4dev::mul(pl.B, p.y)), v4dev::mul(pl.C, p.z));
+          const float lin = add(add(mul(pl.A, p.x), mul(pl.B, p.y)), mul(pl.C, p.z));
           const float planar = (float)fabs((double)lin - 1.0);
           if (planar < FLT_MAX) {   // strict `<` from FLT_MAX: NaN and +inf never win (planar >= 0: its bits order as floats)
             const unsigned long long key = ((unsigned long long)__float_as_uint(planar) << 32) | (unsigned)k;
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
       }
     }
   }
-  mine = wave_min(mine);
+  mine = v4dev::wave_min(mine);
   if (lane == 0) s_min[wave] = mine;
   __syncthreads();
   if (wave != 0) return;
@@ -105,8 +98,8 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
       out = make_int4(q[0], q[1], q[2], q[3]);
       o_inv = make_float2(f1, f2);
       // distance1 / distance6 of base.cc:1952-1953: Eigen's norm, x x + (y y + z z)
-      o_dist = make_float2(ppfk::norm(ppfk::vsub(ppfk::ld3(P, q[0]), ppfk::ld3(P, q[1]))),
-                           ppfk::norm(ppfk::vsub(ppfk::ld3(P, q[2]), ppfk::ld3(P, q[3]))));
+      o_dist = make_float2(norm_eigen(vsub(ld3(P, q[0]), ld3(P, q[1]))),
+                           norm_eigen(vsub(ld3(P, q[2]), ld3(P, q[3]))));
       ok = 1;
     }
   }
@@ -147,12 +140,12 @@ __global__ __launch_bounds__(256) void pair_lists(const float4* __restrict__ Q, 
   const size_t my_row = (size_t)(k0 + lane) * (size_t)n + (size_t)i;
   // count pass: hits so far; fill pass: the next output position of the list, in pairs
   uint32_t mine = (FILL && has) ? list_off[k0 + lane] + 2u * row_start[my_row] : 0u;
-  const ppfk::V3 qi = ppfk::ld3(Q, i);
+  const V3 qi = ld3(Q, i);
   for (int j0 = 0; j0 < i; j0 += 64) {
     const int j = j0 + lane;
     const bool live = j < i;
     // (q.pos() - p.pos()).norm() as pair_rows has it: q_i - q_j, x x + (y y + z z), correctly rounded sqrt
-    const double dij = live ? (double)ppfk::norm(ppfk::vsub(qi, ppfk::ld3(Q, j))) : 0.0;
+    const double dij = live ? (double)norm_eigen(vsub(qi, ld3(Q, j))) : 0.0;
     for (int k = 0; k < kn; ++k) {
       const double dk = (double)dist[k0 + k];
       const bool hit = live && !(fabs(dij - dk) > eps);

@@ -34,10 +34,7 @@ namespace pgp {
 
 namespace {
 
-using namespace v4dev;   // base_device.h: the float helpers and the triangle rule shared with super4pcs.hip
-
-// the pair predicate's squared norm, as pair_rows has it: x x + (y y + z z)
-__device__ __forceinline__ float sqnorm_pair(V3 v) { return add(mul(v.x, v.x), add(mul(v.y, v.y), mul(v.z, v.z))); }
+using namespace v4dev;   // base_device.h: exact_f32.h's helpers and the triangle rule shared with super4pcs.hip
 
 // ---------------- SelectTetrahedronBase: a wave per attempt ----------------
 __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, int n, unsigned long long seed, int T, int F,
@@ -63,7 +60,7 @@ __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, 
     unsigned long long bestv = 0ull;
     for (int k = lane; k < F; k += 64) {
       const int f = (int)(sample_variate(st, 1 + 2 * T + k) % un);
-      const float volume = __fdiv_rn(fabsf(dot(n12, vsub(ld3(P, f), p0))), 6.0f);
+      const float volume = __fdiv_rn(fabsf(dot_lr(n12, vsub(ld3(P, f), p0))), 6.0f);
       if (volume > 0.f) {
         const unsigned long long key = ((unsigned long long)__float_as_uint(volume) << 32) | (0xFFFFFFFFu - (unsigned)k);
         bestv = key > bestv ? key : bestv;
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, 
       ok = 1;
       const V3 e[6] = {vsub(p1, p0), vsub(p2, p0), vsub(p3, p0), vsub(p2, p1), vsub(p3, p1), vsub(p3, p2)};
 #pragma unroll
-      for (int q = 0; q < 6; ++q) d[q] = sqrt_rn(dot(e[q], e[q]));
+      for (int q = 0; q < 6; ++q) d[q] = norm_lr(e[q]);
     }
   }
   if (lane == 0) {
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256) void pair_bits(const float4* __restrict__ Q, i
   if (live) {
     // (q_hi - q_lo, as pair_rows subtracts; the squares are the same either way round)
     const V3 d = j < i ? vsub(ld3(Q, i), ld3(Q, j)) : vsub(ld3(Q, j), ld3(Q, i));
-    dij = (double)sqrt_rn(sqnorm_pair(d));
+    dij = (double)norm_eigen(d);   // the pair predicate's norm, as pair_rows has it: x x + (y y + z z)
   }
   const size_t plane = (size_t)N * W, at = (size_t)i * W + c;
   for (int b = 0; b < nb; ++b) {

@@ -1,7 +1,8 @@
 """The congruent-set joins (csrc/congruent.hip) at their edges, on the hand-made models of tests/_congruent_models.py:
-the single-base join (p_entries / q_match), the many-base join (bp_entries / bq_match / batch_gather) and the classic 4PCS
-range join (invariant_points / range_match) against the C oracle, the numpy statement of the classic join and the fixture made
-with the reference (tests/golden/quad_edges.npz).  Every result is an integer list, compared exactly and in order.
+the join (bp_entries / bq_match / batch_gather) through its single-base entry pgp_find_congruent -- a batch of one base; up
+to 81c9ed9 a join of its own, p_entries / q_match -- and through its many-base entries, and the classic 4PCS range join
+(invariant_points / range_match) against the C oracle, the numpy statement of the classic join and the fixture made with the
+reference (tests/golden/quad_edges.npz).  Every result is an integer list, compared exactly and in order.
 tests/test_congruent_models_cpu.py pins what the oracle gives on every case used here, so nothing below passes on empty lists.
 
   exact directions     lattice pairs along +-x, +-y, +-z: the identity and the half-turn branch of the cone quaternion, bins at +-1
@@ -10,6 +11,8 @@ tests/test_congruent_models_cpu.py pins what the oracle gives on every case used
   sizes                lists cut next to the workgroup sizes, capacities next to the total, pair ids that name no point
   many bases           lists of 864 / 8 / 0 pairs, workgroups over 32 bases, empty bases, 256 and 257 Q pairs, 4 / 5 / 72 matches
                        per thread, a key array that has to grow, base numbers beyond 32 767, more than 65 535 bases refused
+  one join             a single base whose keys outgrow the first guess, the single-base call that finds nothing and still
+                       discards the batch, the 2^24-pair refusal, one base through the lists, the table rows and the single call
   classic join         the 1024-entry tile at 1023 / 1024 / 1025 / 2049, the strict `<` ON an occurring distance, P_pairs[id / 2]
 """
 import os
@@ -25,6 +28,7 @@ from physimglobalpose_amd._lib import PgpError
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "quad_edges.npz")
 EINVAL = r"libpgp error -1:"
+ESTATE = r"libpgp error -4:"
 
 
 @pytest.fixture(scope="module")
@@ -277,6 +281,99 @@ def test_more_than_65535_bases_are_refused(world):
     with pytest.raises(PgpError, match=EINVAL):
         sc.find_congruent_batch(np.zeros((nb, 4), np.int32), xyz, inv, M.K_THR)
     assert sc.find_congruent_batch(np.zeros((2, 4), np.int32), xyz[:2], inv[:2], M.K_THR, rows=zeros[:2]).tolist() == [48, 48]
+
+
+# ---------------- one join: the single-base call is a batch of one base ----------------
+
+def _raw_find_congruent(sc, base, inv, thr, Pp, Qp, cap):
+    """pgp_find_congruent as the C caller sees it -> (return code, *n_quads, the cap + 1 rows of the caller's buffer)"""
+    import ctypes as C
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    b = np.ascontiguousarray(base, np.float32).reshape(12)
+    Pp, Qp = np.ascontiguousarray(Pp, np.int32), np.ascontiguousarray(Qp, np.int32)
+    out = np.full((cap + 1, 4), -7, np.int32)
+    n = C.c_int(0)
+    rc = sc._lib.pgp_find_congruent(sc._h, b.ctypes.data_as(C.POINTER(C.c_float)), C.c_float(inv[0]), C.c_float(inv[1]), C.c_float(thr),
+                                    ip(Pp), len(Pp), ip(Qp), len(Qp), ip(out), cap, C.byref(n))
+    return rc, n.value, out
+
+
+def test_single_base_past_the_first_key_guess(world):
+    """the doubled P list: 124 416 keys of ONE base, more than a fresh context's first guess of 65 536 -- the key array grows
+    inside the call, and the next call starts from the hint"""
+    pts, orc, pairs, ctx = world
+    base, Q = M.bases_L()["zx"], pairs["L"]
+    P = np.concatenate([Q, Q])
+    want = orc["L"].find_congruent(base, 0.5, 0.5, M.THR_COARSE, P, Q)
+    assert len(want) == 124416 > 65536
+    fresh = LcpScorer()
+    fresh.set_search_model(M.lattice_L())
+    for _ in range(2):
+        assert np.array_equal(fresh.find_congruent(base, 0.5, 0.5, M.THR_COARSE, P, Q), want)
+    cap = 65537
+    rc, n, out = _raw_find_congruent(fresh, base, (0.5, 0.5), M.THR_COARSE, P, Q, cap)
+    assert rc == 0 and n == len(want) and np.array_equal(out[:cap], want[:cap]) and (out[cap:] == -7).all()
+    fresh.close()
+
+
+def test_a_single_base_call_that_finds_nothing_still_discards_the_batch(batch, world):
+    sc, lists, one_base = batch
+    pts, orc, pairs, ctx = world
+    n_quads = sc.find_congruent_batch_lists(*_arrays(M.batch_compositions()["q256"]), M.THR_FINE)
+    picks = _all_picks(n_quads)
+    assert n_quads.tolist() == [8] * 32 and len(sc.congruent_batch_quads(picks)) == 256          # resident
+    base, inv = M.bases_L()["zx"], (0.5, 40.0)                  # every Q pair's invariant point is far outside the grid
+    assert len(orc["L"].find_congruent(base, inv[0], inv[1], M.THR_FINE, lists[0], lists[0])) == 0
+    assert len(sc.find_congruent(base, inv[0], inv[1], M.THR_FINE, lists[0], lists[0])) == 0
+    with pytest.raises(PgpError, match=ESTATE):
+        sc.congruent_batch_quads(picks)
+    for k in range(3):                                           # the lists of extract_pairs_batch are not the batch
+        assert np.array_equal(sc.extract_pairs_batch_fetch(k)[0], lists[k])
+    assert sc.find_congruent_batch_lists(*_arrays(M.batch_compositions()["q256"]), M.THR_FINE).tolist() == [8] * 32
+
+
+def test_a_list_of_2_to_the_24_pairs_is_refused(world):
+    """the join's keys hold a pair index in 24 bits"""
+    pts, orc, pairs, ctx = world
+    big = np.zeros((1 << 24, 2), np.int32)
+    for P, Q in ((big, pairs["L"][:1]), (pairs["L"][:1], big)):
+        with pytest.raises(PgpError, match=EINVAL + r" pgp_find_congruent: "):
+            ctx["L"].find_congruent(M.bases_L()["zx"], 0.5, 0.5, M.THR_COARSE, P, Q)
+
+
+def test_one_base_through_all_three_entries(batch, world):
+    """a batch of ONE base (every workgroup of bq_match has s_b0 == s_b1, the base array has one entry) through the table
+    rows, the single-base call and the resident lists, each against the oracle.  Rows of a hand-made table and the lists of
+    the single-base call have any length: 1 and 257 pairs on either side.  The lists of extract_pairs_batch hold (j, i) and
+    (i, j) of every hit, an even count, so that entry runs on the lists it has: 864 and 8 pairs."""
+    sc, lists, one_base = batch
+    pts, orc, pairs, ctx = world
+    P, base, thr = pairs["L"], M.bases_L()["zx"], M.THR_COARSE
+    table = [P[:1], P[:257]]
+    sc.set_ppf_map(np.array([(k, 0, 0, 0) for k in range(2)], np.int32), np.array([1, 257], np.int32), np.concatenate(table))
+    totals = []
+    for r1 in (0, 1):
+        for r6 in (0, 1):
+            want = orc["L"].find_congruent(base, 0.5, 0.5, thr, table[r1], table[r6])
+            totals.append(len(want))
+            n_quads = sc.find_congruent_batch(np.zeros((1, 4), np.int32), base[None], [(0.5, 0.5)], thr, rows=[(r1, r6)])
+            assert n_quads.tolist() == [len(want)], (r1, r6)
+            if len(want):
+                assert np.array_equal(sc.congruent_batch_quads(_all_picks(n_quads)), want), (r1, r6)
+            assert np.array_equal(sc.find_congruent(base, 0.5, 0.5, thr, table[r1], table[r6]), want), (r1, r6)
+    assert totals == [0, 48, 48, 10640]
+    totals = []
+    for bn, inv, (l1, l6) in (("zx", (0.5, 0.5), (0, 0)), ("short", M.SHORT_INVS[0], (1, 1)), ("short", M.SHORT_INVS[0], (1, 0)),
+                              ("zx", (0.5, 0.5), (0, 1))):
+        xyz = M.batch_base_xyz(bn)
+        want = orc["L"].find_congruent(xyz, inv[0], inv[1], thr, lists[l1], lists[l6])
+        totals.append(len(want))
+        n_quads = sc.find_congruent_batch_lists(xyz[None], [inv], [(l1, l6)], thr)
+        assert n_quads.tolist() == [len(want)], (bn, l1, l6)
+        if len(want):
+            assert np.array_equal(sc.congruent_batch_quads(_all_picks(n_quads)), want), (bn, l1, l6)
+        assert np.array_equal(sc.find_congruent(xyz, inv[0], inv[1], thr, lists[l1], lists[l6]), want), (bn, l1, l6)
+    assert totals == [62208, 8, 0, 0]
 
 
 # ---------------- classic join ----------------

@@ -177,6 +177,23 @@ def test_batch_cases_are_non_trivial(world):
     assert sorted(np.unique(c).tolist()) == [4, 5] and (c == 4).sum() == 72 and (c == 5).sum() == 72
 
 
+def test_one_join_cases_are_non_trivial(world):
+    """the cases of the single-base call as a batch of one base"""
+    pts, orc, pairs = world
+    P, base = pairs["L"], M.bases_L()["zx"]
+    doubled = orc["L"].find_congruent(base, 0.5, 0.5, M.THR_COARSE, np.concatenate([P, P]), P)
+    once = orc["L"].find_congruent(base, 0.5, 0.5, M.THR_COARSE, P, P)
+    assert len(doubled) == 124416 > 65536                       # more keys than the first guess of a fresh context
+    assert np.array_equal(doubled[:62208], once) and np.array_equal(doubled[62208:], once)
+    assert len(orc["L"].find_congruent(base, 0.5, 40.0, M.THR_FINE, P, P)) == 0              # non-empty lists, no quads
+    n = [len(orc["L"].find_congruent(base, 0.5, 0.5, M.THR_COARSE, P[:nP], P[:nQ])) for nP in (1, 257) for nQ in (1, 257)]
+    assert n == [0, 48, 48, 10640]
+    S = orc["L"].extract_pairs(M.D_DIAG, 0.0)
+    short = M.batch_base_xyz("short")
+    assert len(orc["L"].find_congruent(short, *M.SHORT_INVS[0], M.THR_COARSE, S, S)) == 8
+    assert len(orc["L"].find_congruent(short, *M.SHORT_INVS[0], M.THR_COARSE, S, P)) == 0
+
+
 def test_classic_join_cases_are_non_trivial(world):
     pts, orc, pairs = world
     L = pts["L"]
