@@ -1315,6 +1315,64 @@ int pgp_multi_last_timing(pgp_multi* m, float* upload_ms, float* enqueue_ms, flo
 int pgp_set_kernel_timing(pgp_ctx* ctx, int enable);
 int pgp_get_kernel_timing(pgp_ctx* ctx, int* launches, float* total_ms, int reset);
 
+/* ---- model clouds from an object's mesh: surface sampling + farthest-point order -----------------------------------
+ * The node reads model_validation.ply and model_search.ply, prepared offline (PPE/data_layer/Objects.cpp:22-28).  These
+ * calls make both from the mesh that pgp_mcts_object / pgp_physics_add_shape already take: a dense oriented sample of
+ * the surface, put into farthest-point order.  Both rules are exact: tests/_model_prep_restate.py reproduces every
+ * output bit for bit in numpy.
+ *
+ * pgp_sample_mesh: n_samples points of the surface, uniform by area.  vertices: n_vert x vertex_stride floats (stride 3
+ * or 4, as in pgp_mcts_object), triangles: n_tri x 3 ints, 1 <= n_tri <= PGP_SAMPLE_MESH_MAX_TRIANGLES.  Out:
+ * xyz[n_samples][3], nrm[n_samples][3] (nullable), tri[n_samples] (nullable: the triangle a sample lies on).
+ *   Area.  e1 = v1 - v0 and e2 = v2 - v0 in double from the float vertices, c = e1 x e2, A_t = 0.5 sqrt((cx cx + cy cy)
+ *     + cz cz), every operation rounded on its own, the square root correctly rounded.
+ *   Integer weights.  A_max = the exact maximum; w_t = (uint64) floor((A_t / A_max) 2^32) with an IEEE double divide;
+ *     C_t = the inclusive prefix sums in uint64 and W = C_{n_tri - 1} < 2^55, so no order of summation shows.  A
+ *     triangle whose w_t is 0 -- no area, or less than 2^-32 of the largest -- is NEVER drawn.
+ *   Draws.  Sample s uses v_i = variate i (31 bits, i = 0 .. 3) of the counter-based stream (seed, s) that
+ *     pgp_sample_quads and pgp_fit_plane draw from.  r = v0 << 31 | v1 (62 bits); target = (r W) >> 62 from the 128-bit
+ *     product; the triangle is the first t with C_t > target.
+ *   Position.  a = float(v2) 2^-31, b = float(v3) 2^-31 (the integer converted round-to-nearest, then scaled); if a + b
+ *     > 1 then a = 1 - a, b = 1 - b; p = (v0 + a (v1 - v0)) + b (v2 - v0) per component in float, in that order, each
+ *     operation rounded on its own.
+ *   Normal.  (v1 - v0) x (v2 - v0) in float, normalised as Eigen's normalized() does (left as it is when its squared
+ *     norm is 0): the winding gives the side.
+ * PGP_EINVAL: a NaN or infinite vertex, an index outside [0, n_vert), W == 0 (no triangle has an area), bad counts or a
+ * bad stride.  The host form checks vertices and indices before anything is launched.  The _device form takes device
+ * arrays, is enqueued on `stream` and SYNCHRONISES that stream once, for the error flag; a flagged mesh is never read
+ * out of bounds, and the outputs are then left unwritten. */
+#define PGP_SAMPLE_MESH_MAX_TRIANGLES 4194304
+int pgp_sample_mesh(pgp_ctx* ctx, const float* vertices, int n_vert, int vertex_stride, const int* triangles, int n_tri,
+                    int n_samples, unsigned long long seed, float* xyz, float* nrm, int* tri);
+int pgp_sample_mesh_device(pgp_ctx* ctx, const float* d_vertices, int n_vert, int vertex_stride, const int* d_triangles,
+                           int n_tri, int n_samples, unsigned long long seed, float* d_xyz, float* d_nrm, int* d_tri,
+                           void* stream);
+
+/* The farthest-point order of a cloud: xyz n x 3 floats, 1 <= k <= n (else PGP_EINVAL); order[k], radius2[k] (nullable).
+ * order[0] = start; start == -1: the point of largest x, ties to the lowest index (pgp_convex_hull's rule).  Every
+ * point keeps d_i, the smallest squared distance to a point picked so far, computed in float as (dx dx + dy dy) + dz dz
+ * of the rounded differences p_i - p_pick, each operation rounded on its own; a picked point's d becomes -1, so a
+ * duplicate is never picked twice.  The next pick is the largest d under strict >, ties to the lowest index.
+ * radius2[0] = FLT_MAX, radius2[j] = d of pick j at the moment it was picked: non-increasing from j = 1 on, and the
+ * squared covering radius of the first j picks.  Every prefix of the order is the order of a smaller k.
+ * Two forms with identical results: n <= 16384 runs in ONE workgroup that keeps the cloud in registers for all k
+ * picks; a larger n takes one launch per pick over up to 256 workgroups (no workgroup waits for another), queued back to
+ * back.  PGP_FPS_FORM=multi in the environment forces the second form at any n (a checker path).
+ * The host form rejects non-finite points and start outside -1 .. n - 1.  The _device form takes float4 points
+ * {x, y, z, -} like the ICP calls, is enqueued on `stream` and does not synchronise; the multi-launch form may grow
+ * its workspace (an allocation) on first use. */
+int pgp_farthest_points(pgp_ctx* ctx, const float* xyz, int n, int k, int start, int* order, float* radius2);
+int pgp_farthest_points_device(pgp_ctx* ctx, const float* d_xyz4, int n, int k, int start, int* d_order, float* d_radius2,
+                               void* stream);
+
+/* Both in one call, the dense sample never leaving the device: pgp_sample_mesh(n_dense samples, seed), then
+ * pgp_farthest_points(k = n_model <= n_dense, start = -1) over them; xyz[n_model][3], nrm[n_model][3] (nullable),
+ * tri[n_model] (nullable) are the rows order[0 .. n_model) of the sample, radius2[n_model] (nullable) as above -- bit
+ * for bit the two calls composed.  Rows 0 .. m - 1 are the farthest-point subset of size m for EVERY m <= n_model: a
+ * model_validation cloud made this way holds its model_search cloud as its first rows.  Host pointers, synchronous. */
+int pgp_model_from_mesh(pgp_ctx* ctx, const float* vertices, int n_vert, int vertex_stride, const int* triangles, int n_tri,
+                        int n_dense, int n_model, unsigned long long seed, float* xyz, float* nrm, int* tri, float* radius2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,14 @@ SIGNATURES = {
     "pgp_mcts_default_options": (C.c_int, [C.c_void_p]),
     "pgp_mcts_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _f, _f, C.POINTER(Camera), _f, _i, _f, _f,
                                   C.c_void_p, C.c_void_p, C.c_int, _i]),
+    "pgp_sample_mesh": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_int, _i, C.c_int, C.c_int, C.c_ulonglong, _f, _f, _i]),
+    "pgp_sample_mesh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgp_farthest_points": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_int, C.c_int, _i, _f]),
+    "pgp_farthest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "pgp_model_from_mesh": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_int, _i, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _f, _f, _i,
+                                      _f]),
 }
 
 _lib = None

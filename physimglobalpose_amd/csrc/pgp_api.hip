@@ -263,7 +263,8 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
                     &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
-                    &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io};
+                    &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io,
+                    &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   for (PinBuf* b : {&ctx->h_pin, &ctx->h_sel_pin, &ctx->h_w_pin, &ctx->h_s_pin}) b->release();
@@ -3694,6 +3695,186 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
   };
   return chain_tail(ctx, ctx->d_s4_io, gather, b_ids.data(), nq.data(), nb, opt->seed, opt->max_per_base, centroid_P, centroid_Q,
                     ChainOut{n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose});
+}
+
+// ---- model preparation (model_prep.hip) ------------------------------------------------------------------------------------
+
+static int check_sample_args(const char* who, const void* vertices, int n_vert, int stride, const void* triangles, int n_tri,
+                             int n_samples, const void* xyz) {
+  if (!vertices || !triangles || !xyz || n_vert < 1 || (stride != 3 && stride != 4) || n_tri < 1 || n_tri > PGP_SAMPLE_MESH_MAX_TRIANGLES ||
+      n_samples < 1) {
+    set_error("%s: bad argument (n_vert=%d, vertex_stride=%d, n_tri=%d of 1 .. %d, n_samples=%d)", who, n_vert, stride, n_tri,
+              PGP_SAMPLE_MESH_MAX_TRIANGLES, n_samples);
+    return PGP_EINVAL;
+  }
+  return PGP_OK;
+}
+
+// what the host forms check before anything is launched
+static int check_mesh_host(const char* who, const float* vertices, int n_vert, int stride, const int* triangles, int n_tri) {
+  for (size_t i = 0; i < (size_t)n_vert; ++i)
+    for (int q = 0; q < 3; ++q)
+      if (!std::isfinite(vertices[i * (size_t)stride + q])) {
+        set_error("%s: vertex %zu is NaN or infinite", who, i);
+        return PGP_EINVAL;
+      }
+  for (size_t i = 0; i < 3 * (size_t)n_tri; ++i)
+    if (triangles[i] < 0 || triangles[i] >= n_vert) {
+      set_error("%s: triangle %zu names vertex %d outside [0, %d)", who, i / 3, triangles[i], n_vert);
+      return PGP_EINVAL;
+    }
+  return PGP_OK;
+}
+
+// the staged mesh and the dense sample of the host forms, one layout in ctx->d_prep_io
+struct PrepStage {
+  Carve cv;
+  Carve::Piece<float> vert, xyz, nrm, rad, oxyz, onrm;
+  Carve::Piece<int> tri, tid, order, otid;
+  Carve::Piece<float4> xyz4;
+};
+static int prep_stage(pgp_ctx* ctx, PrepStage& s, int n_vert, int stride, int n_tri, int n_samples, int n_model, bool fps) {
+  s.vert = s.cv.add<float>((size_t)n_vert * (size_t)stride, 256);
+  s.tri = s.cv.add<int>(3 * (size_t)n_tri, 256);
+  s.xyz = s.cv.add<float>(3 * (size_t)n_samples, 256);
+  s.nrm = s.cv.add<float>(3 * (size_t)n_samples, 256);
+  s.tid = s.cv.add<int>((size_t)n_samples, 256);
+  if (fps) {
+    s.xyz4 = s.cv.add<float4>((size_t)n_samples, 256);
+    s.order = s.cv.add<int>((size_t)n_model, 256);
+    s.rad = s.cv.add<float>((size_t)n_model, 256);
+    s.oxyz = s.cv.add<float>(3 * (size_t)n_model, 256);
+    s.onrm = s.cv.add<float>(3 * (size_t)n_model, 256);
+    s.otid = s.cv.add<int>((size_t)n_model, 256);
+  }
+  return s.cv.ensure(ctx->d_prep_io);
+}
+
+int pgp_sample_mesh(pgp_ctx* ctx, const float* vertices, int n_vert, int vertex_stride, const int* triangles, int n_tri,
+                    int n_samples, unsigned long long seed, float* xyz, float* nrm, int* tri) {
+  if (!ctx) {
+    set_error("pgp_sample_mesh: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  int rc = check_sample_args("pgp_sample_mesh", vertices, n_vert, vertex_stride, triangles, n_tri, n_samples, xyz);
+  if (rc != PGP_OK || (rc = check_mesh_host("pgp_sample_mesh", vertices, n_vert, vertex_stride, triangles, n_tri)) != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  PrepStage s;
+  if ((rc = prep_stage(ctx, s, n_vert, vertex_stride, n_tri, n_samples, 0, false)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(s.cv.at(s.vert), vertices, s.vert.bytes(), hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(s.cv.at(s.tri), triangles, s.tri.bytes(), hipMemcpyHostToDevice, st));
+  if ((rc = launch_sample_mesh(ctx, s.cv.at(s.vert), n_vert, vertex_stride, s.cv.at(s.tri), n_tri, n_samples, seed, s.cv.at(s.xyz),
+                               nrm ? s.cv.at(s.nrm) : nullptr, tri ? s.cv.at(s.tid) : nullptr, nullptr, st)) != PGP_OK)
+    return rc;
+  HostOut out(ctx, st);
+  if ((rc = out.to(xyz, s.cv.at(s.xyz), s.xyz.bytes())) != PGP_OK || (nrm && (rc = out.to(nrm, s.cv.at(s.nrm), s.nrm.bytes())) != PGP_OK) ||
+      (tri && (rc = out.to(tri, s.cv.at(s.tid), s.tid.bytes())) != PGP_OK))
+    return rc;
+  return out.sync();
+}
+
+int pgp_sample_mesh_device(pgp_ctx* ctx, const float* d_vertices, int n_vert, int vertex_stride, const int* d_triangles, int n_tri,
+                           int n_samples, unsigned long long seed, float* d_xyz, float* d_nrm, int* d_tri, void* stream) {
+  if (!ctx) {
+    set_error("pgp_sample_mesh_device: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  int rc = check_sample_args("pgp_sample_mesh_device", d_vertices, n_vert, vertex_stride, d_triangles, n_tri, n_samples, d_xyz);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx, false);
+  rc = launch_sample_mesh(ctx, d_vertices, n_vert, vertex_stride, d_triangles, n_tri, n_samples, seed, d_xyz, d_nrm, d_tri, nullptr,
+                          static_cast<hipStream_t>(stream));
+  note_device_work(ctx, static_cast<hipStream_t>(stream));
+  return rc;
+}
+
+static int check_fps_args(const char* who, const void* xyz, int n, int k, int start, const void* order) {
+  if (!xyz || !order || n < 1 || k < 1 || k > n || start < -1 || start >= n) {
+    set_error("%s: bad argument (n=%d, k=%d of 1 .. n, start=%d of -1 .. n - 1)", who, n, k, start);
+    return PGP_EINVAL;
+  }
+  return PGP_OK;
+}
+
+int pgp_farthest_points(pgp_ctx* ctx, const float* xyz, int n, int k, int start, int* order, float* radius2) {
+  if (!ctx) {
+    set_error("pgp_farthest_points: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  int rc = check_fps_args("pgp_farthest_points", xyz, n, k, start, order);
+  if (rc != PGP_OK) return rc;
+  for (size_t i = 0; i < 3 * (size_t)n; ++i)
+    if (!std::isfinite(xyz[i])) {
+      set_error("pgp_farthest_points: point %zu is NaN or infinite", i / 3);
+      return PGP_EINVAL;
+    }
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  Carve cv;
+  const auto c_in = cv.add<float>(3 * (size_t)n, 256);
+  const auto c_p4 = cv.add<float4>((size_t)n, 256);
+  const auto c_order = cv.add<int>((size_t)k, 256);
+  const auto c_rad = cv.add<float>((size_t)k, 256);
+  if ((rc = cv.ensure(ctx->d_prep_io)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(cv.at(c_in), xyz, c_in.bytes(), hipMemcpyHostToDevice, st));
+  if ((rc = launch_pad4(cv.at(c_in), n, cv.at(c_p4), st)) != PGP_OK ||
+      (rc = launch_farthest_points(ctx, cv.at(c_p4), n, k, start, cv.at(c_order), cv.at(c_rad), st)) != PGP_OK)
+    return rc;
+  HostOut out(ctx, st);
+  if ((rc = out.to(order, cv.at(c_order), c_order.bytes())) != PGP_OK ||
+      (radius2 && (rc = out.to(radius2, cv.at(c_rad), c_rad.bytes())) != PGP_OK))
+    return rc;
+  return out.sync();
+}
+
+int pgp_farthest_points_device(pgp_ctx* ctx, const float* d_xyz4, int n, int k, int start, int* d_order, float* d_radius2,
+                               void* stream) {
+  if (!ctx) {
+    set_error("pgp_farthest_points_device: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  int rc = check_fps_args("pgp_farthest_points_device", d_xyz4, n, k, start, d_order);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx, false);
+  rc = launch_farthest_points(ctx, reinterpret_cast<const float4*>(d_xyz4), n, k, start, d_order, d_radius2,
+                              static_cast<hipStream_t>(stream));
+  note_device_work(ctx, static_cast<hipStream_t>(stream));
+  return rc;
+}
+
+int pgp_model_from_mesh(pgp_ctx* ctx, const float* vertices, int n_vert, int vertex_stride, const int* triangles, int n_tri,
+                        int n_dense, int n_model, unsigned long long seed, float* xyz, float* nrm, int* tri, float* radius2) {
+  if (!ctx) {
+    set_error("pgp_model_from_mesh: ctx is NULL");
+    return PGP_EINVAL;
+  }
+  int rc = check_sample_args("pgp_model_from_mesh", vertices, n_vert, vertex_stride, triangles, n_tri, n_dense, xyz);
+  if (rc != PGP_OK) return rc;
+  if (n_model < 1 || n_model > n_dense) {
+    set_error("pgp_model_from_mesh: bad argument (n_model=%d of 1 .. n_dense=%d)", n_model, n_dense);
+    return PGP_EINVAL;
+  }
+  if ((rc = check_mesh_host("pgp_model_from_mesh", vertices, n_vert, vertex_stride, triangles, n_tri)) != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  PrepStage s;
+  if ((rc = prep_stage(ctx, s, n_vert, vertex_stride, n_tri, n_dense, n_model, true)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(s.cv.at(s.vert), vertices, s.vert.bytes(), hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(s.cv.at(s.tri), triangles, s.tri.bytes(), hipMemcpyHostToDevice, st));
+  if ((rc = launch_sample_mesh(ctx, s.cv.at(s.vert), n_vert, vertex_stride, s.cv.at(s.tri), n_tri, n_dense, seed, s.cv.at(s.xyz),
+                               s.cv.at(s.nrm), s.cv.at(s.tid), s.cv.at(s.xyz4), st)) != PGP_OK ||
+      (rc = launch_farthest_points(ctx, s.cv.at(s.xyz4), n_dense, n_model, -1, s.cv.at(s.order), s.cv.at(s.rad), st)) != PGP_OK ||
+      (rc = launch_model_gather(s.cv.at(s.order), n_model, s.cv.at(s.xyz), s.cv.at(s.nrm), s.cv.at(s.tid), s.cv.at(s.oxyz),
+                                s.cv.at(s.onrm), s.cv.at(s.otid), st)) != PGP_OK)
+    return rc;
+  HostOut out(ctx, st);
+  if ((rc = out.to(xyz, s.cv.at(s.oxyz), s.oxyz.bytes())) != PGP_OK ||
+      (nrm && (rc = out.to(nrm, s.cv.at(s.onrm), s.onrm.bytes())) != PGP_OK) ||
+      (tri && (rc = out.to(tri, s.cv.at(s.otid), s.otid.bytes())) != PGP_OK) ||
+      (radius2 && (rc = out.to(radius2, s.cv.at(s.rad), s.rad.bytes())) != PGP_OK))
+    return rc;
+  return out.sync();
 }
 
 }  // extern "C"

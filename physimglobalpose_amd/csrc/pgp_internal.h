@@ -364,6 +364,10 @@ struct pgp_ctx {
 
   // MCTS search (mcts.hip): step workspace (pose tables, settle inputs, descriptors, scores); two images per slot
   pgp::DevBuf d_mcts_ws, d_mcts_img;
+
+  // model preparation (model_prep.hip): sampling scratch (areas, weights, prefix sums, scan scratch); the multi-launch
+  // farthest-point form's d and partial keys; host-API staging and the dense sample of pgp_model_from_mesh
+  pgp::DevBuf d_prep_ws, d_fps_ws, d_prep_io;
 };
 
 namespace pgp {
@@ -661,6 +665,16 @@ int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_o
                      const float* table_params, const float* cam_pose, const pgp_camera* cam, const float* observed,
                      int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
                      int trace_cap, int* n_trace);
+
+// model_prep.hip.  launch_sample_mesh synchronises `st` once (the error flag); d_nrm, d_tri_out and d_xyz4 (the positions
+// again as float4, what launch_farthest_points reads) are nullable.
+int launch_sample_mesh(pgp_ctx* ctx, const float* d_vert, int n_vert, int stride, const int* d_tri, int n_tri, int n_samples,
+                       unsigned long long seed, float* d_xyz, float* d_nrm, int* d_tri_out, float4* d_xyz4, hipStream_t st);
+int launch_farthest_points(pgp_ctx* ctx, const float4* d_xyz4, int n, int k, int start, int* d_order, float* d_radius2,
+                           hipStream_t st);
+int launch_pad4(const float* d_xyz, int n, float4* d_out, hipStream_t st);
+int launch_model_gather(const int* d_order, int m, const float* d_xyz, const float* d_nrm, const int* d_tri, float* d_xyz_out,
+                        float* d_nrm_out, int* d_tri_out, hipStream_t st);
 
 // ppf_vote.hip
 int ppf_model_angles(pgp_ctx* ctx);   // alpha_m of every pair, when the table (with pairs) and a covering model are set

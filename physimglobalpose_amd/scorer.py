@@ -1205,6 +1205,81 @@ class LcpScorer:
         _lib.check(_lib.load().pgp_convex_hull(_fp(P), len(P), int(max_vertices), _fp(hv), C.byref(nv), _fp(pl), C.byref(npl)))
         return hv[:nv.value].copy(), pl[:npl.value].copy()
 
+    # ---- model clouds from a mesh (csrc/model_prep.hip) --------------------------------------------------------
+    @staticmethod
+    def _mesh(vertices, triangles):
+        """(vertices (n, 3 or 4) float32, stride, triangles (m, 3) int32), contiguous."""
+        V = np.ascontiguousarray(vertices, dtype=np.float32)
+        assert V.ndim == 2 and V.shape[1] in (3, 4), "vertices: (n, 3) or (n, 4)"
+        F = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        return V, int(V.shape[1]), F
+
+    @staticmethod
+    def _stream_of(stream, dev):
+        import torch
+        if stream is None:
+            return torch.cuda.current_stream(dev).cuda_stream
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+    def sample_mesh(self, vertices, triangles, n_samples, seed=0):
+        """pgp_sample_mesh: n_samples points of the surface, uniform by area -> (xyz (n,3), nrm (n,3), tri (n,))."""
+        V, stride, F = self._mesh(vertices, triangles)
+        n = int(n_samples)
+        xyz, nrm, tri = np.zeros((max(n, 0), 3), np.float32), np.zeros((max(n, 0), 3), np.float32), np.zeros(max(n, 0), np.int32)
+        _lib.check(self._lib.pgp_sample_mesh(self._h, _fp(V), len(V), stride, F.ctypes.data_as(_i), len(F), n,
+                                             C.c_ulonglong(int(seed)), _fp(xyz), _fp(nrm), tri.ctypes.data_as(_i)))
+        return xyz, nrm, tri
+
+    def sample_mesh_device(self, d_vertices, d_triangles, n_samples, seed=0, stream=None):
+        """pgp_sample_mesh_device: torch tensors on the device in (float32 (n, 3 or 4), int32 (m, 3)) and out
+        -> (d_xyz (n,3), d_nrm (n,3), d_tri (n,)).  Synchronises the stream once."""
+        import torch
+        assert d_vertices.is_cuda and d_vertices.dtype == torch.float32 and d_vertices.is_contiguous()
+        assert d_triangles.is_cuda and d_triangles.dtype == torch.int32 and d_triangles.is_contiguous()
+        dev, n = d_vertices.device, int(n_samples)
+        d_xyz = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+        d_nrm = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+        d_tri = torch.zeros(n, dtype=torch.int32, device=dev)
+        _lib.check(self._lib.pgp_sample_mesh_device(
+            self._h, C.c_void_p(d_vertices.data_ptr()), int(d_vertices.shape[0]), int(d_vertices.shape[1]),
+            C.c_void_p(d_triangles.data_ptr()), int(d_triangles.shape[0]), n, C.c_ulonglong(int(seed)),
+            C.c_void_p(d_xyz.data_ptr()), C.c_void_p(d_nrm.data_ptr()), C.c_void_p(d_tri.data_ptr()),
+            C.c_void_p(self._stream_of(stream, dev))))
+        return d_xyz, d_nrm, d_tri
+
+    def farthest_points(self, xyz, k, start=-1):
+        """pgp_farthest_points: the farthest-point order of a cloud -> (order (k,) int32, radius2 (k,) float32).
+        start = -1: the point of largest x (ties: the lowest index)."""
+        P = _f32(xyz, 3)
+        k = int(k)
+        order, rad = np.zeros(max(k, 0), np.int32), np.zeros(max(k, 0), np.float32)
+        _lib.check(self._lib.pgp_farthest_points(self._h, _fp(P), len(P), k, int(start), order.ctypes.data_as(_i), _fp(rad)))
+        return order, rad
+
+    def farthest_points_device(self, d_xyz4, k, start=-1, stream=None):
+        """pgp_farthest_points_device: d_xyz4 (n,4) float32 on the device -> (d_order (k,), d_radius2 (k,)); enqueued."""
+        import torch
+        assert d_xyz4.is_cuda and d_xyz4.dtype == torch.float32 and d_xyz4.is_contiguous() and d_xyz4.shape[1] == 4
+        dev, k = d_xyz4.device, int(k)
+        d_order = torch.zeros(k, dtype=torch.int32, device=dev)
+        d_rad = torch.zeros(k, dtype=torch.float32, device=dev)
+        _lib.check(self._lib.pgp_farthest_points_device(
+            self._h, C.c_void_p(d_xyz4.data_ptr()), int(d_xyz4.shape[0]), k, int(start), C.c_void_p(d_order.data_ptr()),
+            C.c_void_p(d_rad.data_ptr()), C.c_void_p(self._stream_of(stream, dev))))
+        return d_order, d_rad
+
+    def model_from_mesh(self, vertices, triangles, n_dense, n_model, seed=0):
+        """pgp_model_from_mesh: n_dense samples of the surface, the first n_model of their farthest-point order
+        -> (xyz (m,3), nrm (m,3), tri (m,), radius2 (m,)).  Rows [:j] are the farthest-point subset of size j."""
+        V, stride, F = self._mesh(vertices, triangles)
+        m = max(int(n_model), 0)
+        xyz, nrm = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        tri, rad = np.zeros(m, np.int32), np.zeros(m, np.float32)
+        _lib.check(self._lib.pgp_model_from_mesh(self._h, _fp(V), len(V), stride, F.ctypes.data_as(_i), len(F), int(n_dense),
+                                                 int(n_model), C.c_ulonglong(int(seed)), _fp(xyz), _fp(nrm),
+                                                 tri.ctypes.data_as(_i), _fp(rad)))
+        return xyz, nrm, tri, rad
+
     def physics_add_shape(self, xyz, margin=0.001, max_vertices=256):
         """Appends the hull of a mesh's vertices to the context's shape arena -> shape id (0 is the table box)."""
         P = _f32(xyz, 3)
