@@ -578,7 +578,75 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
                              int* n_bases, int* base_ids, float* base_invariants, int* n_hyp, float* T, double* pose, int* status,
                              float* scores, int* picks, int* best_index, float* best_score, float* best_T, double* best_pose);
 
-/* ICP refinement.  Replaces the inner loop behind pcl::recognition::TrimmedICP::align
+/* ---- The classic mode's pair gates: Match4PCSOptions::max_normal_difference, max_color_distance, max_translation_distance and
+ * max_angle (S4/shared4pcs.h:157-163) as PairCreationFunctor::process applies them (S4/pairCreationFunctor.h:167-253) ----------
+ * The fork ships all four switched off (S4/super4pcs_test.cc:91-99) and the calls above behave so.  The calls below apply them
+ * while the pair lists are made; the join, the sampling, the fits and the scores take the gated lists as they take any.
+ *
+ * Point attributes.  The scene's normals are the ones pgp_set_scene[_device] took.  pgp_set_scene_colors: rgb[n][3], n = the
+ * resident scene's count.  pgp_set_search_model_attributes: nrm[n][3] and rgb[n][3], either may be NULL, n = the resident
+ * search model's count; what is NULL becomes absent (a call replaces both).  A point with rgb[0] < 0 has no colour (Point3D's
+ * default, (-1, -1, -1)); absent normals count as zero normals, absent colours as (-1, -1, -1).  pgp_set_scene[_device]
+ * discards the scene's colours, pgp_set_search_model the search model's attributes.  A NaN or an infinite value, or a wrong n:
+ * PGP_EINVAL; no scene / no search model: PGP_ESTATE.  Host pointers, synchronous. */
+int pgp_set_scene_colors(pgp_ctx* ctx, const float* rgb, int n);
+int pgp_set_search_model_attributes(pgp_ctx* ctx, const float* nrm, const float* rgb, int n);
+
+/* The gates.  pgp_pair_gates_default switches everything off (host only, no context).  A NaN or an infinite field, or a
+ * max_angle above 180: PGP_EINVAL from the calls that take the struct.
+ *
+ * List k has a base edge, the scene ids (b1, b2) = base_ids[k]; its record is made on the device: pna = |n_b1 - n_b2|
+ * (base.cc:1956-1957), seg1 = (pos_b2 - pos_b1).normalized() (:157; Eigen's: v / sqrt(z) when z = |v|^2 > 0, else v), the two
+ * positions and the two colours.  For every i > j of the search model that passes pgp_extract_pairs' distance predicate
+ * (unchanged), p = Q[j], q = Q[i].  Every float operation is rounded on its own, three-vector reductions are x x + (y y + z z),
+ * square roots and divisions are correctly rounded, |v| is a float unless widened:
+ *   normals (:182-196), when max_normal_difference > 0 and |n_q|^2 > 0 and |n_p|^2 > 0:
+ *     thr = (float)(0.5 * (double)max_normal_difference * M_PI / 180.0); f = (double)|n_q - n_p|, s = (double)|n_q + n_p|;
+ *     d = (float)min(fabs(f - (double)pna), fabs(s - (double)pna)) (std::min: the second when it is smaller, else the first);
+ *     the pair is dropped when d > thr.
+ *   colour (:198-208), when max_color_distance > 0 and p, q, b1, b2 all have rgb[0] >= 0: dropped unless
+ *     (double)|rgb_p - rgb_b1| < (double)max and (double)|rgb_q - rgb_b2| < (double)max -- both strict.
+ *   translation (:210-216), when max_translation_distance > 0: dropped unless (double)|pos_p - pos_b1| < (double)max and
+ *     (double)|pos_q - pos_b2| < (double)max -- both strict.  Positions are the resident ones: centre both clouds as the
+ *     reference does (pgp_center).
+ *   angle (:238-251), when max_angle > 0: seg2 = (pos_q - pos_p).normalized(), c = (float)cos((double)max_angle * M_PI / 180.0)
+ *     (on the host); (j, i) is emitted iff dot(seg1, seg2) >= c, (i, j) iff dot(seg1, -seg2) >= c: either, both or neither; a NaN
+ *     dot emits nothing.  The reference writes acos(dot) <= max_angle * M_PI / 180.0: the cosine form decides differently only
+ *     for dots within rounding of the threshold, and keeps acos off the device.  With the gate off both pairs are emitted.
+ *   directed = 0 is the reference's rule: colour and translation are tested once per unordered pair, the lower index against
+ *     b1, and then both orders may come out -- so (i, j) can be emitted although q does not match b1.  directed = 1 tests each
+ *     ordered pair (a, b) in its own direction, a against b1 and b against b2, and emits it iff its own colour, translation and
+ *     angle tests pass.  The normal gate is symmetric either way.
+ * Order inside a list: rows i ascending, j ascending within a row, (j, i) before (i, j).
+ *
+ * pgp_extract_pairs_batch_gated leaves THE resident pair lists of the context, exactly as pgp_extract_pairs_batch does: the
+ * same buffer, the same limits (2^24 pairs per list, 2^31 in all, 131070 lists, 65536 points), the same discard rules;
+ * pgp_extract_pairs_batch_fetch, pgp_find_congruent_batch_lists and everything behind them work on them unchanged.
+ * base_ids[n_lists][2]: scene ids.  gates NULL or every gate off: the lists are bit-equal to pgp_extract_pairs_batch's and
+ * base_ids may be NULL.  A base id outside the scene: PGP_EINVAL; gates switched on with no scene: PGP_ESTATE.
+ *
+ * pgp_super4pcs_hypotheses_gated is pgp_super4pcs_hypotheses with step 2 gated: list 2 b has the base edge (ids 0, 1) of base
+ * b, list 2 b + 1 the edge (ids 2, 3) (base.cc:1964-1968).  gates NULL or all off: every output is bit-equal.
+ *
+ * Not here: the Euler-angle test that max_angle >= 0 also switches on in ComputeRigidTransformation (base.cc:1567-1582) -- the
+ * fit stays as shipped; gates on the tetrahedron mode's six pair sets (its bit matrices are symmetric) and in
+ * pgp_find_congruent_4pcs; the single-list pgp_extract_pairs; pgp_multi_*. */
+typedef struct pgp_pair_gates {
+  float max_normal_difference;    /* degrees; <= 0: off */
+  float max_color_distance;       /* <= 0: off */
+  float max_translation_distance; /* <= 0: off */
+  float max_angle;                /* degrees, (0, 180]; <= 0: off */
+  int directed;                   /* 0: the reference's rule; 1: every ordered pair in its own direction */
+} pgp_pair_gates;
+int pgp_pair_gates_default(pgp_pair_gates* gates);
+int pgp_extract_pairs_batch_gated(pgp_ctx* ctx, const float* dist, const int* base_ids, int n_lists, float eps,
+                                  const pgp_pair_gates* gates, int* n_pairs);
+int pgp_super4pcs_hypotheses_gated(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const pgp_pair_gates* gates,
+                                   const float centroid_P[3], const float centroid_Q[3], int* n_bases, int* base_ids,
+                                   float* base_invariants, int* n_hyp, float* T, double* pose, int* status, float* scores, int* picks,
+                                   int* best_index, float* best_score, float* best_T, double* best_pose);
+
+/* ICP refinement. Replaces the inner loop behind pcl::recognition::TrimmedICP::align
  * (PPE/hypothesis_verification/mcts/UCTState.cpp:137-139,194; PPE/misc/utilities.cpp:666-676) and
  * pcl::IterativeClosestPoint::align (utilities.cpp:697-703; PPE/data_layer/SceneCfg.cpp:101,135-141)
  * for a batch of n initial guesses at once.  PCL is not vendored in the reference, so the

@@ -92,6 +92,11 @@ class Super4pcsOptions(C.Structure):
                 ("max_base_diameter", C.c_float), ("eps", C.c_float), ("max_per_base", C.c_int)]
 
 
+class PairGates(C.Structure):
+    _fields_ = [("max_normal_difference", C.c_float), ("max_color_distance", C.c_float), ("max_translation_distance", C.c_float),
+                ("max_angle", C.c_float), ("directed", C.c_int)]
+
+
 class PhysicsOptions(C.Structure):
     _fields_ = [("dt", C.c_float), ("steps", C.c_int), ("gravity", C.c_float * 3), ("linear_damping", C.c_float),
                 ("angular_damping", C.c_float), ("friction", C.c_float), ("iterations", C.c_int), ("erp", C.c_float)]
@@ -310,6 +315,12 @@ SIGNATURES = {
     "pgp_super4pcs_default_options": (C.c_int, [C.POINTER(Super4pcsOptions)]),
     "pgp_super4pcs_hypotheses": (C.c_int, [C.c_void_p, C.POINTER(Super4pcsOptions), _f, _f, _i, _i, _f, _i, _f, C.POINTER(C.c_double),
                                            _i, _f, _i, _i, _f, _f, C.POINTER(C.c_double)]),
+    "pgp_set_scene_colors": (C.c_int, [C.c_void_p, _f, C.c_int]),
+    "pgp_set_search_model_attributes": (C.c_int, [C.c_void_p, _f, _f, C.c_int]),
+    "pgp_pair_gates_default": (C.c_int, [C.POINTER(PairGates)]),
+    "pgp_extract_pairs_batch_gated": (C.c_int, [C.c_void_p, _f, _i, C.c_int, C.c_float, C.POINTER(PairGates), _i]),
+    "pgp_super4pcs_hypotheses_gated": (C.c_int, [C.c_void_p, C.POINTER(Super4pcsOptions), C.POINTER(PairGates), _f, _f, _i, _i, _f, _i,
+                                                 _f, C.POINTER(C.c_double), _i, _f, _i, _i, _f, _f, C.POINTER(C.c_double)]),
     "pgp_physics_default_options": (C.c_int, [C.POINTER(PhysicsOptions)]),
     "pgp_convex_hull": (C.c_int, [_f, C.c_int, C.c_int, _f, _i, _f, _i]),
     "pgp_physics_add_shape": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, _i]),

@@ -263,7 +263,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
                     &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
-                    &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io,
+                    &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io, &ctx->d_Prgb, &ctx->d_Qs_nrm, &ctx->d_Qs_rgb,
                     &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
@@ -400,6 +400,7 @@ int pgp_set_scene(pgp_ctx* ctx, const float* xyz, const float* nrm, const float*
   ctx->prob_cdf_valid = false;
   ctx->nP = n;
   ctx->has_scene_normals = nrm != nullptr;
+  ctx->has_scene_colors = false;
   // packed {x, y, z, id} / {nx, ny, nz, w}: through a pinned staging buffer of this call's own for scenes up to 4 MB (the
   // uploads are then queued and nobody waits for them here: an event tells the side-stream index build when they are
   // through), through temporaries and a synchronisation beyond
@@ -1089,6 +1090,7 @@ int pgp_set_search_model(pgp_ctx* ctx, const float* xyz, int n) {
   ctx->v4_nb = 0;    // and so does a resident V4PCS batch
   ctx->s4_nl = 0;    // and the pair lists of pgp_extract_pairs_batch
   ctx->s4_off.clear();
+  ctx->has_search_normals = ctx->has_search_colors = false;   // the attributes belong to the old points
   std::vector<float4> hq((size_t)std::max(n, 1));
   for (int i = 0; i < n; ++i)
     hq[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2],
@@ -3637,20 +3639,51 @@ int pgp_super4pcs_default_options(pgp_super4pcs_options* opt) {
   return PGP_OK;
 }
 
-int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const float centroid_P[3], const float centroid_Q[3],
-                             int* n_bases, int* base_ids, float* base_invariants, int* n_hyp, float* T, double* pose, int* status,
-                             float* scores, int* picks, int* best_index, float* best_score, float* best_T, double* best_pose) {
+}  // extern "C"
+
+// the fields of a pgp_pair_gates that the calls refuse: a NaN, an infinity, a max_angle above 180
+static bool pair_gates_ok(const pgp_pair_gates* g) {
+  return !g || (std::isfinite(g->max_normal_difference) && std::isfinite(g->max_color_distance) &&
+                std::isfinite(g->max_translation_distance) && std::isfinite(g->max_angle) && !(g->max_angle > 180.f));
+}
+
+static bool all_finite(const float* v, size_t count) {
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+// n x 3 host floats -> float4 {x, y, z, 0} in `buf`, synchronously
+static int upload_xyz0(pgp_ctx* ctx, DevBuf& buf, const float* v, int n) {
+  std::vector<float4> h((size_t)n);
+  for (int i = 0; i < n; ++i) h[i] = make_float4(v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2], 0.f);
+  const int rc = buf.ensure(h.size() * sizeof(float4));
+  if (rc != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(buf.p, h.data(), h.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+  PGP_HIP(hipStreamSynchronize(ctx->stream));
+  return PGP_OK;
+}
+
+// pgp_super4pcs_hypotheses and pgp_super4pcs_hypotheses_gated (gates nullable: none)
+static int super4pcs_chain(pgp_ctx* ctx, const char* who, const pgp_super4pcs_options* opt, const pgp_pair_gates* gates,
+                           const float centroid_P[3], const float centroid_Q[3], int* n_bases, int* base_ids, float* base_invariants,
+                           int* n_hyp, float* T, double* pose, int* status, float* scores, int* picks, int* best_index,
+                           float* best_score, float* best_T, double* best_pose) {
   if (!ctx || !opt || !centroid_P || !centroid_Q || !n_hyp || !T || !status || !scores) {
-    set_error("pgp_super4pcs_hypotheses: bad argument");
+    set_error("%s: bad argument", who);
     return PGP_EINVAL;
   }
   if (opt->n_bases < 1 || opt->n_bases > 65535 || opt->max_attempts < 1 || opt->max_attempts > kV4MaxAttempts ||
       opt->triangle_trials < 0 || opt->triangle_trials > kV4MaxTrials || !(opt->max_base_diameter > 0.f) ||
       !std::isfinite(opt->max_base_diameter) || !(opt->eps >= 0.f) || !std::isfinite(opt->eps) || opt->max_per_base < 1 ||
       opt->max_per_base > kSampleMax) {
-    set_error("pgp_super4pcs_hypotheses: bad options (n_bases %d, max_attempts %d, trials %d, diameter %g, eps %g, max_per_base %d of "
-              "at most %d)", opt->n_bases, opt->max_attempts, opt->triangle_trials, (double)opt->max_base_diameter, (double)opt->eps,
+    set_error("%s: bad options (n_bases %d, max_attempts %d, trials %d, diameter %g, eps %g, max_per_base %d of "
+              "at most %d)", who, opt->n_bases, opt->max_attempts, opt->triangle_trials, (double)opt->max_base_diameter, (double)opt->eps,
               opt->max_per_base, kSampleMax);
+    return PGP_EINVAL;
+  }
+  if (!pair_gates_ok(gates)) {
+    set_error("%s: bad gates (a NaN, an infinity or max_angle above 180)", who);
     return PGP_EINVAL;
   }
   *n_hyp = 0;
@@ -3683,8 +3716,9 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
   if (base_ids && nb > 0) std::memcpy(base_ids, b_ids.data(), (size_t)nb * 16);
   if (base_invariants && nb > 0) std::memcpy(base_invariants, b_inv.data(), (size_t)nb * 8);
   if (nb == 0) return PGP_OK;
-  // 2. the pair lists of the bases' 2 nb distances, resident
-  if ((rc = launch_extract_pairs_batch(ctx, b_dist.data(), 2 * nb, opt->eps, nullptr, st)) != PGP_OK) return rc;
+  // 2. the pair lists of the bases' 2 nb distances, resident; b_ids read as [2 nb][2] names the base edge of every list:
+  //    (ids 0, 1) for pairs1, (ids 2, 3) for pairs6 (base.cc:1964-1968)
+  if ((rc = launch_extract_pairs_batch_gated(ctx, b_dist.data(), b_ids.data(), 2 * nb, opt->eps, gates, nullptr, st)) != PGP_OK) return rc;
   // 3. the join, fed from those lists
   std::vector<int> nq((size_t)nb);
   if ((rc = launch_find_congruent_batch_lists(ctx, b_xyz.data(), b_inv.data(), b_lists.data(), nb, opt->eps, nq.data(), st)) != PGP_OK)
@@ -3695,6 +3729,96 @@ int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, con
   };
   return chain_tail(ctx, ctx->d_s4_io, gather, b_ids.data(), nq.data(), nb, opt->seed, opt->max_per_base, centroid_P, centroid_Q,
                     ChainOut{n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose});
+}
+
+extern "C" {
+
+int pgp_super4pcs_hypotheses(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const float centroid_P[3], const float centroid_Q[3],
+                             int* n_bases, int* base_ids, float* base_invariants, int* n_hyp, float* T, double* pose, int* status,
+                             float* scores, int* picks, int* best_index, float* best_score, float* best_T, double* best_pose) {
+  return super4pcs_chain(ctx, "pgp_super4pcs_hypotheses", opt, nullptr, centroid_P, centroid_Q, n_bases, base_ids, base_invariants,
+                         n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose);
+}
+
+int pgp_super4pcs_hypotheses_gated(pgp_ctx* ctx, const pgp_super4pcs_options* opt, const pgp_pair_gates* gates,
+                                   const float centroid_P[3], const float centroid_Q[3], int* n_bases, int* base_ids,
+                                   float* base_invariants, int* n_hyp, float* T, double* pose, int* status, float* scores, int* picks,
+                                   int* best_index, float* best_score, float* best_T, double* best_pose) {
+  return super4pcs_chain(ctx, "pgp_super4pcs_hypotheses_gated", opt, gates, centroid_P, centroid_Q, n_bases, base_ids,
+                         base_invariants, n_hyp, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose);
+}
+
+// ---- the classic mode's pair gates (super4pcs.hip pair_lists_gated) ---------------------------------------------------------
+int pgp_pair_gates_default(pgp_pair_gates* gates) {
+  if (!gates) {
+    set_error("pgp_pair_gates_default: null");
+    return PGP_EINVAL;
+  }
+  gates->max_normal_difference = -1.f;   // S4/super4pcs_test.cc:91-99: the fork's settings, all off
+  gates->max_color_distance = -1.f;
+  gates->max_translation_distance = -1.f;
+  gates->max_angle = -1.f;
+  gates->directed = 0;
+  return PGP_OK;
+}
+
+int pgp_set_scene_colors(pgp_ctx* ctx, const float* rgb, int n) {
+  if (!ctx || !rgb || n < 0) {
+    set_error("pgp_set_scene_colors: bad argument (n=%d)", n);
+    return PGP_EINVAL;
+  }
+  if (ctx->nP <= 0 || !ctx->d_P.p) {
+    set_error("no scene: call pgp_set_scene first");
+    return PGP_ESTATE;
+  }
+  if (n != ctx->nP || !all_finite(rgb, 3 * (size_t)n)) {
+    set_error("pgp_set_scene_colors: %d colours for a scene of %d points, or a value that is not finite", n, ctx->nP);
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  ctx->has_scene_colors = false;
+  const int rc = upload_xyz0(ctx, ctx->d_Prgb, rgb, n);
+  if (rc == PGP_OK) ctx->has_scene_colors = true;
+  return rc;
+}
+
+int pgp_set_search_model_attributes(pgp_ctx* ctx, const float* nrm, const float* rgb, int n) {
+  if (!ctx || n < 0) {
+    set_error("pgp_set_search_model_attributes: bad argument (n=%d)", n);
+    return PGP_EINVAL;
+  }
+  if (ctx->nQs <= 0 || !ctx->d_Qs.p) {
+    set_error("no search model: call pgp_set_search_model first");
+    return PGP_ESTATE;
+  }
+  if (n != ctx->nQs || (nrm && !all_finite(nrm, 3 * (size_t)n)) || (rgb && !all_finite(rgb, 3 * (size_t)n))) {
+    set_error("pgp_set_search_model_attributes: %d attributes for a search model of %d points, or a value that is not finite", n,
+              ctx->nQs);
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  ctx->has_search_normals = ctx->has_search_colors = false;
+  int rc;
+  if (nrm) {
+    if ((rc = upload_xyz0(ctx, ctx->d_Qs_nrm, nrm, n)) != PGP_OK) return rc;
+    ctx->has_search_normals = true;
+  }
+  if (rgb) {
+    if ((rc = upload_xyz0(ctx, ctx->d_Qs_rgb, rgb, n)) != PGP_OK) return rc;
+    ctx->has_search_colors = true;
+  }
+  return PGP_OK;
+}
+
+int pgp_extract_pairs_batch_gated(pgp_ctx* ctx, const float* dist, const int* base_ids, int n_lists, float eps,
+                                  const pgp_pair_gates* gates, int* n_pairs) {
+  if (!ctx || n_lists < 0 || n_lists > 2 * 65535 || (n_lists > 0 && !dist) || !(eps >= 0.f) || !std::isfinite(eps) ||
+      !pair_gates_ok(gates)) {
+    set_error("pgp_extract_pairs_batch_gated: bad argument (%d lists; gates: a NaN, an infinity or max_angle above 180)", n_lists);
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  return launch_extract_pairs_batch_gated(ctx, dist, base_ids, n_lists, eps, gates, n_pairs, ctx->stream);
 }
 
 // ---- model preparation (model_prep.hip) ------------------------------------------------------------------------------------

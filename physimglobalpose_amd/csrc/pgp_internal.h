@@ -149,6 +149,8 @@ struct pgp_ctx {
   float delta = 0.f;
   pgp::DevBuf d_P;       // float4 {x,y,z,bits(i)}             [nP]
   pgp::DevBuf d_Pnw;     // float4 {nx,ny,nz,w}                [nP]
+  bool has_scene_colors = false;   // pgp_set_scene_colors; a new scene discards them
+  pgp::DevBuf d_Prgb;    // float4 {r,g,b,0}                   [nP]
   // index
   bool has_index = false;
   pgp::GridDesc grid{};
@@ -206,6 +208,9 @@ struct pgp_ctx {
   int nQs = 0;
   pgp::DevBuf d_Qs;      // float4 {x,y,z,bits(i)} original order [nQs]
   pgp::DevBuf d_Qs_unit; // float4 unit-cube image (PairCreationFunctor::points) [nQs]
+  bool has_search_normals = false, has_search_colors = false;   // pgp_set_search_model_attributes; a new search model discards them
+  pgp::DevBuf d_Qs_nrm;  // float4 {nx,ny,nz,0}                 [nQs]
+  pgp::DevBuf d_Qs_rgb;  // float4 {r,g,b,0}                    [nQs]
   float cs_gcenter[3] = {0.f, 0.f, 0.f};
   float cs_ratio = 1.f;
   pgp::DevBuf d_cs_cnt, d_cs_entries, d_cs_keys;   // congruent-set workspaces
@@ -223,7 +228,7 @@ struct pgp_ctx {
   // classic mode (super4pcs.hip): the pair lists of the last pgp_extract_pairs_batch stay on the device, in a buffer of their
   // own (d_ppf_pairs belongs to the pair-feature table), with their offsets on the host
   pgp::DevBuf d_s4_sel;                 // base selection: ids | invariants | distances | status
-  pgp::DevBuf d_s4_ws;                  // distances | list totals | list offsets | row counts | row starts
+  pgp::DevBuf d_s4_ws;                  // distances | list totals | list offsets | row counts | row starts | base ids | base records
   pgp::DevBuf d_s4_pairs;               // int2 pairs of all lists, list k at [s4_off[k], s4_off[k + 1])
   pgp::DevBuf d_s4_io;                  // the chain's ids and results
   int s4_nl = 0;                        // lists of the last batch; 0 once the search model is rewritten
@@ -537,6 +542,9 @@ int launch_v4pcs_gather(pgp_ctx* ctx, const int* h_picks, int m, int4* d_out, hi
 int launch_wide_bases(pgp_ctx* ctx, unsigned long long seed, int n_attempts, int triangle_trials, float max_base_diameter,
                       int* h_ids, float* h_inv, float* h_dist, int* h_status, float* h_xyz /* nullable: [n][4][3] */, hipStream_t st);
 int launch_extract_pairs_batch(pgp_ctx* ctx, const float* h_dist, int nl, float eps, int* h_n_pairs, hipStream_t st);
+// gates (nullable: none) are validated by the caller; h_base_ids[nl][2] (scene ids) is read only when a gate is on
+int launch_extract_pairs_batch_gated(pgp_ctx* ctx, const float* h_dist, const int* h_base_ids, int nl, float eps,
+                                     const pgp_pair_gates* gates, int* h_n_pairs, hipStream_t st);
 int extract_pairs_batch_fetch(pgp_ctx* ctx, int list, int* h_pairs, int cap, int* h_n_pairs, hipStream_t st);
 
 // lcp_score.hip

@@ -397,6 +397,7 @@ int set_scene_device(pgp_ctx* ctx, const float* d_xyz, const float* d_nrm, const
   ctx->prob_cdf_valid = false;
   ctx->nP = n;
   ctx->has_scene_normals = d_nrm != nullptr;
+  ctx->has_scene_colors = false;
   int rc;
   const size_t N = (size_t)(n > 0 ? n : 1);
   if ((rc = ctx->d_P.ensure(N * sizeof(float4))) != PGP_OK) return rc;

@@ -509,12 +509,53 @@ class LcpScorer:
     def super4pcs_options(max_base_diameter, **kw):
         return LcpScorer._options(_lib.Super4pcsOptions, "super4pcs", max_base_diameter=float(max_base_diameter), **kw)
 
-    def super4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), **opt):
+    def super4pcs_hypotheses(self, max_base_diameter, centroid_P=(0, 0, 0), centroid_Q=(0, 0, 0), gates=None, **opt):
         """pgp_super4pcs_hypotheses: wide bases, pair lists, join, sampling, fits and plain scores in one call.  Returns the
         dict of v4pcs_hypotheses (base_ids, T, pose, status, scores, picks, best_index, best_score, best_T, best_pose) plus
-        base_invariants."""
-        return self._chain(self._lib.pgp_super4pcs_hypotheses, self.super4pcs_options(max_base_diameter, **opt), centroid_P, centroid_Q,
-                           base_invariants=True)
+        base_invariants.  gates (a pair_gates(...) struct): pgp_super4pcs_hypotheses_gated."""
+        call = self._lib.pgp_super4pcs_hypotheses
+        if gates is not None:
+            def call(h, o, *rest):
+                return self._lib.pgp_super4pcs_hypotheses_gated(h, o, C.byref(gates), *rest)
+        return self._chain(call, self.super4pcs_options(max_base_diameter, **opt), centroid_P, centroid_Q, base_invariants=True)
+
+    # ---- the classic mode's pair gates (pairCreationFunctor.h:167-253) ----
+    def set_scene_colors(self, rgb):
+        rgb = _f32(rgb, 3)
+        _lib.check(self._lib.pgp_set_scene_colors(self._h, _fp(rgb), len(rgb)))
+
+    def set_search_model_attributes(self, nrm=None, rgb=None, n=None):
+        """Normals and / or colours of the resident search model ((n,3) each); n: the count when both are None."""
+        nrm, rgb = _f32(nrm, 3), _f32(rgb, 3)
+        if n is None:
+            n = len(nrm) if nrm is not None else (len(rgb) if rgb is not None else 0)
+        if any(a is not None and len(a) != n for a in (nrm, rgb)):
+            raise ValueError("attributes / count size mismatch")
+        _lib.check(self._lib.pgp_set_search_model_attributes(self._h, _fp(nrm), _fp(rgb), int(n)))
+
+    @staticmethod
+    def pair_gates(**kw):
+        """A pgp_pair_gates struct: pgp_pair_gates_default (everything off), then the keyword overrides."""
+        g = _lib.PairGates()
+        _lib.check(_lib.load().pgp_pair_gates_default(C.byref(g)))
+        for k, v in kw.items():
+            if not hasattr(g, k):
+                raise TypeError(f"pgp_pair_gates has no field {k!r}")
+            setattr(g, k, v)
+        return g
+
+    def extract_pairs_batch_gated(self, dist, base_ids, eps, gates=None):
+        """pgp_extract_pairs_batch_gated: base_ids (n_lists,2) scene ids (None allowed with no gate on); returns the pairs
+        per list (n_lists,) int32."""
+        d = _f32(dist).reshape(-1)
+        ids = None if base_ids is None else np.ascontiguousarray(base_ids, np.int32).reshape(-1, 2)
+        if ids is not None and len(ids) != len(d):
+            raise ValueError("base ids / distances size mismatch")
+        n = np.zeros(max(len(d), 1), np.int32)
+        _lib.check(self._lib.pgp_extract_pairs_batch_gated(self._h, _fp(d), None if ids is None else ids.ctypes.data_as(_i), len(d),
+                                                           C.c_float(eps), None if gates is None else C.byref(gates),
+                                                           n.ctypes.data_as(_i)))
+        return n[: len(d)]
 
     # ---- segment pre-processing (ObjectPoseCandidateSet.cpp:28-51) -----------------------------------
     def radius_outlier_filter(self, xyz, nrm=None, radius=0.03, min_neighbors=10):
