@@ -9,18 +9,20 @@
 // Mapping to the machine
 //   lane            = one validation-model point (kept in VGPRs for the whole block: it is
 //                     re-used by every hypothesis of the block's chunk, so it never needs LDS)
-//   workgroup       = 256 model points (4 wave64) x a chunk of `hpb` hypotheses (8 at C2; the last
-//                     10 % of a batch in chunks of 2 so that the launch ends on short workgroups)
+//   workgroup       = ONE wave64 = 64 model points (a "wave row"; four consecutive rows are a tile of 256, the
+//                     unit of the sum order) x a chunk of `hpb` hypotheses (8 at C2; the last 10 % of a
+//                     batch in chunks of 2 so that the launch ends on short workgroups).  A wave retires
+//                     by itself: no barrier, nothing to wait for behind a slower neighbour
 //   hypothesis      = wave-uniform: its 4x4 is read with scalar loads (one 64 B line) and lives
 //                     in SGPRs; the transform is 9 mul + 9 add per lane, no contraction
 //   cell look-up    = one v_fma per axis leaves the lattice cell in the mantissa (cell_bits), the block
 //                     coordinates are cut out with v_bfe: 9 VALU from position to word address
 //   inlier count    = __ballot + popcount per wave, packed per group of 4 hypotheses on the SCALAR unit;
 //                     weighted mode parks each lane's registered weight in LDS and reduces a group at
-//                     once; 4 wave totals combined in LDS in fixed order, one (tile, hypothesis) partial
-//                     per block, summed by finalize_scores in tile order => no atomics on the data
-//                     path, bit-reproducible run to run
-//   block -> (chunk, tile) is XCD-aware: blocks that share blockIdx%8 (one XCD, one L2) work on
+//                     once; one (wave row, hypothesis) partial per wave, stored straight to global
+//                     memory; finalize_scores adds the four rows of a tile in row order, then the tiles
+//                     in tile order => no atomics on the data path, bit-reproducible run to run
+//   block -> (chunk, row) is XCD-aware: blocks that share blockIdx%8 (one XCD, one L2) work on
 //                     the same hypothesis chunks, so the cells those poses touch stay in that L2.
 //
 // Float parity: every arithmetic expression that decides an inlier is evaluated in the order
@@ -48,8 +50,8 @@ namespace pgp {
 
 namespace {
 
-constexpr int kTile = 256;    // model points per workgroup (512 = 8 waves: +6 us per C2 step at its best hpb)
-constexpr int kMaxHpb = 64;   // hypotheses per workgroup (LDS partial slots)
+constexpr int kTile = 256;    // model points per tile = four wave rows: the unit of the sum order (finalize_scores)
+constexpr int kMaxHpb = 64;   // hypotheses per workgroup
 
 struct Xf {  // one hypothesis, wave-uniform (SGPRs)
   float m00, m10, m20, m01, m11, m21, m02, m12, m22, m03, m13, m23;
@@ -289,13 +291,15 @@ struct ScoreArgs {
   int nQ;
   const float* T;
   int n_h, hpb, n_tiles, n_chunks;
+  int n_rows;           // wave rows of the model = ceil(nQ / 64) (at least one): rows past it are not launched
   int n_big, hpb_tail;  // chunks [0, n_big) hold hpb hypotheses each, the rest hpb_tail (chunk_range)
   float sq_eps, gate_lo, gate_hi;
   float cell_c[3];      // 1.5 * 2^23 - k0 per axis (cell_bits)
   uint32_t last_word;   // number of occupancy words - 1
   int cell_hi;          // kMagicBits + (cells of the longest axis) - 1
-  uint2* partial;       // [n_tiles][n_h] {inlier count, bits of the weight sum (weighted only)}: ONE 8-byte
-                        // load per (tile, hypothesis) in finalize_scores
+  uint2* partial;       // {inlier count, bits of the weight sum (weighted only)} per (wave row, hypothesis),
+                        // [2 * n_tiles][n_h][2]: rows 2p and 2p + 1 side by side, so that finalize_scores
+                        // fetches the four rows of a (tile, hypothesis) with two 16-byte loads (partial_row)
   // pgp_set_exact_ties: the reference's kd-tree over the scene (kd_ties.hip), asked only when two different
   // candidates share the minimal distance; null = ties go to the lowest scene index
   const int4* kd_nodes;
@@ -371,26 +375,34 @@ __device__ __forceinline__ void chunk_range(const ScoreArgs& a, int chunk, int* 
   *h1 = min(*h0 + (chunk < a.n_big ? a.hpb : a.hpb_tail), a.n_h);
 }
 
+// The partials of wave row `row` (= tile * 4 + wave): hypothesis h at [2 * h] of the returned pointer.
+__device__ __forceinline__ uint2* partial_row(const ScoreArgs& a, int row) {
+  return a.partial + (size_t)(row >> 1) * (size_t)a.n_h * 2u + (size_t)(row & 1);
+}
+
+// XCD-aware decode of a one-wave workgroup: consecutive blocks are dealt round-robin over the 8 XCDs, so
+// blocks that agree in blockIdx%8 share an L2; each XCD gets its own hypothesis chunks, and the wave rows
+// of a chunk (those of a tile next to each other) follow one another on that XCD.  False: a padding block.
+__device__ __forceinline__ bool block_chunk_row(const ScoreArgs& a, int* chunk, int* row) {
+  const int L = blockIdx.x;
+  const int xcd = L & 7, seq = L >> 3;
+  *chunk = (seq / a.n_rows) * 8 + xcd;
+  *row = seq % a.n_rows;
+  return *chunk < a.n_chunks;
+}
+
 // U hypotheses are in flight per lane: their word loads, then their offset loads, then their
 // candidate trips are issued back to back, so a wave keeps U independent dependency chains in
 // the memory system instead of one (the kernel is latency-bound: 79 % of wave cycles were
 // s_waitcnt at U = 1, profiles/r01_a_*).  U = 1, 4, 8 measured within 2 % of U = 2 or slower.
 template <int MODE>
-__global__ __launch_bounds__(kTile) void score_hypotheses(ScoreArgs a) {
+__global__ __launch_bounds__(64) void score_hypotheses(ScoreArgs a) {
   constexpr int U = 2;
-  __shared__ int s_cnt[kTile / 64][kMaxHpb];
-  __shared__ float s_sum[kTile / 64][kMaxHpb];
+  int chunk, row;
+  if (!block_chunk_row(a, &chunk, &row)) return;
 
-  // XCD-aware decode: consecutive blocks are dealt round-robin over the 8 XCDs, so blocks that
-  // agree in blockIdx%8 share an L2; give each XCD its own hypothesis chunks.
-  const int L = blockIdx.x;
-  const int xcd = L & 7, seq = L >> 3;
-  const int chunk = (seq / a.n_tiles) * 8 + xcd;
-  const int tile = seq % a.n_tiles;
-  if (chunk >= a.n_chunks) return;  // whole block exits together (padding blocks)
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qi = tile * kTile + threadIdx.x;
+  const int lane = threadIdx.x;
+  const int qi = row * 64 + lane;
   const bool live = qi < a.nQ;
   float4 q = live ? a.Q[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
   float4 qn = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -398,6 +410,7 @@ __global__ __launch_bounds__(kTile) void score_hypotheses(ScoreArgs a) {
 
   int h0, h1;
   chunk_range(a, chunk, &h0, &h1);
+  uint2* prow = partial_row(a, row);
   for (int hb = h0; hb < h1; hb += U) {
     Xf m[U];
     float x[U], y[U], z[U];
@@ -434,24 +447,9 @@ __global__ __launch_bounds__(kTile) void score_hypotheses(ScoreArgs a) {
       }
       unsigned long long mask = __ballot(hit);
       if (MODE == PGP_MODE_WEIGHTED && mask) wsum = wave_sum(wsum);  // fixed association, same every run
-      if (lane == 0 && hb + u < h1) {
-        s_cnt[wave][hb + u - h0] = __popcll(mask);
-        if (MODE == PGP_MODE_WEIGHTED) s_sum[wave][hb + u - h0] = wsum;
-      }
+      if (lane == 0 && hb + u < h1)
+        prow[2 * (size_t)(hb + u)] = make_uint2((uint32_t)__popcll(mask), __float_as_uint(MODE == PGP_MODE_WEIGHTED ? wsum : 0.f));
     }
-  }
-  __syncthreads();
-  const int hh = threadIdx.x;
-  if (hh < h1 - h0) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < kTile / 64; ++w) c += s_cnt[w][hh];
-    float f = 0.f;
-    if (MODE == PGP_MODE_WEIGHTED) {
-#pragma unroll
-      for (int w = 0; w < kTile / 64; ++w) f += s_sum[w][hh];
-    }
-    a.partial[(size_t)tile * a.n_h + h0 + hh] = make_uint2((uint32_t)c, __float_as_uint(f));
   }
 }
 
@@ -571,27 +569,23 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
                                                 const float4* __restrict__ cand,
                                                 const float4* __restrict__ Pnw) {
   constexpr bool kW = MODE == PGP_MODE_WEIGHTED;
-  __shared__ int s_cnt[kTile / 64][kMaxHpb];
-  __shared__ float s_sum[kTile / 64][kMaxHpb];
-  __shared__ float4 s_ent[kTile / 64][64];                 // {x', y', z', bits(run start - prefix)}
-  __shared__ unsigned long long s_res[kTile / 64][64];     // plain: 0/1 ; weighted: min key
+  // the workgroup is ONE wave: everything below is the wave's own (3.7 KB in weighted mode, 32 waves per CU fit)
+  __shared__ float4 s_ent[64];                 // {x', y', z', bits(run start - prefix)}
+  __shared__ unsigned long long s_res[64];     // plain: 0/1 ; weighted: min key
   // run-start bits of the wave's concatenated runs; 4 spare words: the last batch may look one
   // to three chunks past the end (they stay zero)
-  __shared__ unsigned long long s_marks[kTile / 64][kFlatCap / 64 + 4];
-  __shared__ float s_w[kW ? kTile / 64 : 1][kW ? kSumGroup : 1][64];   // registered weight per (hypothesis, lane)
-  __shared__ float4 s_qn[kW ? kTile : 1];                                 // model normals of the tile
+  __shared__ unsigned long long s_marks[kFlatCap / 64 + 4];
+  __shared__ float s_w[kW ? kSumGroup : 1][kW ? 64 : 1];   // registered weight per (hypothesis, lane)
+  __shared__ float4 s_qn[kW ? 64 : 1];                     // model normals of the wave row
   // pgp_set_exact_ties: min key with the scene index complemented (= the highest index at the minimal distance)
-  __shared__ unsigned long long s_res_hi[TIES ? kTile / 64 : 1][TIES ? 64 : 1];
-  unsigned long long* res_hi = s_res_hi[TIES ? (threadIdx.x >> 6) : 0];
+  __shared__ unsigned long long s_res_hi[TIES ? 64 : 1];
+  unsigned long long* res_hi = s_res_hi;
 
-  const int L = blockIdx.x;
-  const int xcd = L & 7, seq = L >> 3;
-  const int chunk = (seq / a.n_tiles) * 8 + xcd;
-  const int tile = seq % a.n_tiles;
-  if (chunk >= a.n_chunks) return;
+  int chunk, row;
+  if (!block_chunk_row(a, &chunk, &row)) return;
 
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qi = tile * kTile + threadIdx.x;
+  const int lane = threadIdx.x;
+  const int qi = row * 64 + lane;
   const bool live = qi < a.nQ;
   // a lane past the end of the model carries a NaN point: it lands in some cell and can never pass
   // `d2 <= eps`, so the loop needs no liveness test
@@ -599,10 +593,10 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
   float4 q = live ? a.Q[qi] : make_float4(qnan, qnan, qnan, 0.f);
   // weighted mode: the model normal is needed once per trip with a neighbour; it waits in LDS (a linear,
   // conflict-free 16-byte read) instead of holding three registers through the candidate phase
-  if (kW) s_qn[threadIdx.x] = live ? a.Qn[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4* ent = s_ent[wave];
-  unsigned long long* res = s_res[wave];
-  unsigned long long* marks = s_marks[wave];
+  if (kW) s_qn[lane] = live ? a.Qn[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4* ent = s_ent;
+  unsigned long long* res = s_res;
+  unsigned long long* marks = s_marks;
   if (lane < kFlatCap / 64 + 4) marks[lane] = 0ull;
   const unsigned long long le_mask = (2ull << lane) - 1ull;  // bits 0..lane (lane 63: all ones)
   const uint32_t le_lo = (uint32_t)le_mask, le_hi = (uint32_t)(le_mask >> 32);
@@ -769,7 +763,7 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       float dot = 2.0f, pw = 0.0f;   // dot = 2 fails the gate
       if (nn_id >= 0) {
         const float4 pn = Pnw[nn_id];
-        const float4 qn = s_qn[threadIdx.x];
+        const float4 qn = s_qn[lane];
         const float nx = rot_row(m.m00, m.m01, m.m02, qn.x, qn.y, qn.z);
         const float ny = rot_row(m.m10, m.m11, m.m12, qn.x, qn.y, qn.z);
         const float nz = rot_row(m.m20, m.m21, m.m22, qn.x, qn.y, qn.z);
@@ -778,28 +772,30 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
       }
       hm = __ballot(gate_ok(dot, a.gate_lo, a.gate_hi));
       // this lane's registered weight (0 when it does not register), reduced once per group
-      s_w[wave][gs][lane] = sel_mask(hm, pw, 0.0f);
+      s_w[gs][lane] = sel_mask(hm, pw, 0.0f);
       wrote |= 1u << gs;
     }
     cnt_pack |= (unsigned long long)(uint32_t)__popcll(hm) << (8 * gs);
   };
 
-  // after the last hypothesis of a group (slots g0s .. g0s + n - 1 of the chunk): lane 16k publishes slot k
+  // after the last hypothesis of a group (slots g0s .. g0s + n - 1 of the chunk): lane 16k publishes slot k,
+  // {count, weight sum}, straight to the wave's row of the partial buffer -- the wave's last word on it
+  uint2* const prow = partial_row(a, row) + 2 * (size_t)h0;
   auto publish = [&](const int g0s, const int n) {
     int pl = lane;
     asm volatile("" : "+v"(pl));   // the lane arithmetic is redone here, once per group, not held in registers
     const int k = pl >> 4;
     const bool pub = (pl & 15) == 0 && k < n;
-    if (pub) s_cnt[wave][g0s + k] = (int)((cnt_pack >> (8 * k)) & 0xFFull);
+    const uint32_t cnt = (uint32_t)((cnt_pack >> (8 * k)) & 0xFFull);
+    float t = 0.0f;
     if (kW) {
       // lanes 16k .. 16k+15 (one DPP row) sum row k of the group: 4 consecutive floats each, in order, then
       // the four DPP steps that fold a row (xor 1, xor 2, half-row mirror, row mirror).  A FIXED association:
       // same bits every run; the reference's own (sequential) order is restored for near-ties by
       // finalize_scores.
-      float t = 0.0f;
       if (wrote != 0u) {
         __builtin_amdgcn_wave_barrier();
-        const float4 v0 = *reinterpret_cast<const float4*>(&s_w[wave][k][(pl & 15) * 4]);
+        const float4 v0 = *reinterpret_cast<const float4*>(&s_w[k][(pl & 15) * 4]);
         t = __fadd_rn(__fadd_rn(__fadd_rn(v0.x, v0.y), v0.z), v0.w);
         t = dpp_step<0xB1>(t);   // quad_perm [1,0,3,2]
         t = dpp_step<0x4E>(t);   // quad_perm [2,3,0,1]
@@ -809,8 +805,8 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
         t = ((wrote >> k) & 1u) != 0u ? t : 0.0f;
         __builtin_amdgcn_wave_barrier();
       }
-      if (pub) s_sum[wave][g0s + k] = t;
     }
+    if (pub) prow[2 * (g0s + k)] = make_uint2(cnt, __float_as_uint(t));
     cnt_pack = 0ull;
     wrote = 0u;
   };
@@ -826,26 +822,15 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     trip(hs, m);
     if (((hs & (kSumGroup - 1)) == kSumGroup - 1) || hs == n_slots - 1) publish(hs & ~(kSumGroup - 1), (hs & (kSumGroup - 1)) + 1);
   }
-  __syncthreads();
-  const int hh = threadIdx.x;
-  if (hh < h1 - h0) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < kTile / 64; ++w) c += s_cnt[w][hh];
-    float f = 0.f;
-    if (kW) {
-#pragma unroll
-      for (int w = 0; w < kTile / 64; ++w) f += s_sum[w][hh];
-    }
-    a.partial[(size_t)tile * a.n_h + h0 + hh] = make_uint2((uint32_t)c, __float_as_uint(f));
-  }
 }
 
-// 8 waves per SIMD: 64 VGPRs, 78 SGPRs, 20 KB of LDS per workgroup.  All three limits were hit while this
-// kernel was shaped (A/B runs of separately built libraries): a 7-wave build with 72 VGPRs is 6 %
-// slower, three-chunk weighted batches with spills 12 % slower, 8 KB more LDS = 7 workgroups per CU 7 %.
+// 8 waves per SIMD: 64 VGPRs, 78 SGPRs.  Both limits were hit while this kernel was shaped (A/B runs of
+// separately built libraries): a 7-wave build with 72 VGPRs is 6 % slower, three-chunk
+// weighted batches with spills 12 % slower.  (As a workgroup of four waves behind one barrier the kernel also
+// sat on the LDS limit -- 8 KB more = 7 workgroups per CU cost 7 % -- and 14 % of its waves' resident time was
+// spent in that barrier; one wave's 3.7 KB no longer cap anything.)
 template <int MODE>
-__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
     const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<MODE, 3, false>(a, Tm, words, occ_run, cand, Pnw);
@@ -853,7 +838,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 // pgp_set_exact_ties, weighted mode: the same kernel with the tie flags and the reference's tree for tied candidates
 template <bool SPARSE>
-__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_ties(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_ties(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
     const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<PGP_MODE_WEIGHTED, 3, SPARSE, true>(a, Tm, words, occ_run, cand, Pnw);
@@ -861,7 +846,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
 // the same kernel over the sparse block table (grid_index.hip): `words` is the uint4 table
 template <int MODE>
-__global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_sparse(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void score_hypotheses_flat_sparse(
     ScoreArgs a, const float* __restrict__ Tm, const uint2* __restrict__ words, const uint2* __restrict__ occ_run,
     const float4* __restrict__ cand, const float4* __restrict__ Pnw) {
   score_flat_body<MODE, 3, true>(a, Tm, words, occ_run, cand, Pnw);
@@ -1219,35 +1204,34 @@ __global__ __launch_bounds__(256) void finalize_scores(ScoreArgs /* read through
     int c = 0;
     float f = 0.f;
     // the partials were written by the kernel before this one, on every die: each load is a trip to the
-    // memory side, so sixteen tiles' loads are issued together and then added IN TILE ORDER (a dependent
-    // load-add chain took 20 round trips, ~9 of this kernel's 12 us at C2)
-    for (int t0 = 0; t0 < n_tiles; t0 += 16) {
-      uint2 pp[16];
+    // memory side, so twenty tiles' loads -- two 16-byte loads per tile, rows {0, 1} and {2, 3} (partial_row),
+    // each of them a contiguous KB per wave -- are issued together and then added IN ROW AND TILE ORDER (a
+    // dependent load-add chain took 20 round trips, ~9 of this kernel's 12 us at C2; the C2 model has 20 tiles).
+    // The float sum is the tree it was when a workgroup summed its four waves: per tile from +0.0f over the
+    // rows in order, then the tiles in order.  A row past the end of the model was not launched and counts
+    // as +0.0f -- what its wave would have stored, and x + 0.0f == x for every x such a sum can hold.
+    constexpr int kFinTiles = 20;
+    const uint4* p4 = reinterpret_cast<const uint4*>(partial);
+    const int n_rows = nQ > 0 ? (nQ + 63) >> 6 : 1;
+    const int last_pair = 2 * n_tiles - 1;
+    for (int t0 = 0; t0 < n_tiles; t0 += kFinTiles) {
+      uint4 pp[2 * kFinTiles];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) pp[j] = partial[(size_t)min(t0 + j, n_tiles - 1) * n_h + h];
-      // (the C2 model has 20 tiles: the second batch's four loads go out before the first batch is consumed)
-      uint2 pq[4];
-      const bool tail4 = n_tiles - (t0 + 16) > 0 && n_tiles - (t0 + 16) <= 4;
-      if (tail4) {
+      for (int j = 0; j < 2 * kFinTiles; ++j) pp[j] = p4[(size_t)min(2 * t0 + j, last_pair) * n_h + h];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pq[j] = partial[(size_t)min(t0 + 16 + j, n_tiles - 1) * n_h + h];
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        if (t0 + j < n_tiles) {
-          c += (int)pp[j].x;
-          f += __uint_as_float(pp[j].y);
+      for (int j = 0; j < kFinTiles; ++j) {
+        const int r0 = 4 * (t0 + j);   // the tile's first wave row
+        if (r0 < n_rows) {
+          const uint4 u = pp[2 * j], v = pp[2 * j + 1];
+          const bool e1 = r0 + 1 < n_rows, e2 = r0 + 2 < n_rows, e3 = r0 + 3 < n_rows;
+          c += (int)u.x + (e1 ? (int)u.z : 0) + (e2 ? (int)v.x : 0) + (e3 ? (int)v.z : 0);
+          float ft = 0.f;
+          ft += __uint_as_float(u.y);
+          ft += e1 ? __uint_as_float(u.w) : 0.f;
+          ft += e2 ? __uint_as_float(v.y) : 0.f;
+          ft += e3 ? __uint_as_float(v.w) : 0.f;
+          f += ft;
         }
-      }
-      if (tail4) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (t0 + 16 + j < n_tiles) {
-            c += (int)pq[j].x;
-            f += __uint_as_float(pq[j].y);
-          }
-        }
-        break;
       }
     }
     float score = (mode == PGP_MODE_PLAIN) ? __fdiv_rn((float)c, (float)nQ) : __fdiv_rn(f, (float)nQ);
@@ -1661,36 +1645,36 @@ void launch_variant(int mode, int unroll, dim3 grid, hipStream_t stream, const S
   // per-lane kernel, which finds cells by subtraction and truncation)
   if (unroll <= 0 && a.g.magic_ok && a.kd_nodes && mode == PGP_MODE_WEIGHTED) {   // exact ties (pgp_set_exact_ties)
     if (a.g.sparse)
-      hipExtLaunchKernelGGL(score_hypotheses_flat_ties<true>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T, a.words,
+      hipExtLaunchKernelGGL(score_hypotheses_flat_ties<true>, grid, dim3(64), 0, stream, ev0, ev1, 0, a, a.T, a.words,
                             a.occ_run, a.cand, a.Pnw);
     else
-      hipExtLaunchKernelGGL(score_hypotheses_flat_ties<false>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T, a.words,
+      hipExtLaunchKernelGGL(score_hypotheses_flat_ties<false>, grid, dim3(64), 0, stream, ev0, ev1, 0, a, a.T, a.words,
                             a.occ_run, a.cand, a.Pnw);
     return;
   }
   if (unroll <= 0 && a.g.magic_ok && a.g.sparse) {  // wave-flattened candidate phase over the sparse block table
     if (mode == PGP_MODE_PLAIN)
-      hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a,
+      hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_PLAIN>, grid, dim3(64), 0, stream, ev0, ev1, 0, a,
                             a.T, a.words, a.occ_run, a.cand, a.Pnw);
     else
-      hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0,
+      hipExtLaunchKernelGGL(score_hypotheses_flat_sparse<PGP_MODE_WEIGHTED>, grid, dim3(64), 0, stream, ev0, ev1, 0,
                             a, a.T, a.words, a.occ_run, a.cand, a.Pnw);
     return;
   }
   if (unroll <= 0 && a.g.magic_ok) {  // wave-flattened candidate phase (dense block array)
     if (mode == PGP_MODE_PLAIN)
-      hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a, a.T,
+      hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_PLAIN>, grid, dim3(64), 0, stream, ev0, ev1, 0, a, a.T,
                             a.words, a.occ_run, a.cand, a.Pnw);
     else
-      hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a,
+      hipExtLaunchKernelGGL(score_hypotheses_flat<PGP_MODE_WEIGHTED>, grid, dim3(64), 0, stream, ev0, ev1, 0, a,
                             a.T, a.words, a.occ_run, a.cand, a.Pnw);
     return;
   }
   // per-lane walk, two hypotheses in flight per lane
   if (mode == PGP_MODE_PLAIN)
-    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_PLAIN>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a);
+    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_PLAIN>, grid, dim3(64), 0, stream, ev0, ev1, 0, a);
   else
-    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_WEIGHTED>, grid, dim3(kTile), 0, stream, ev0, ev1, 0, a);
+    hipExtLaunchKernelGGL(score_hypotheses<PGP_MODE_WEIGHTED>, grid, dim3(64), 0, stream, ev0, ev1, 0, a);
 }
 
 // `stream`: the one the launch goes to -- which lists it reads is decided here (grid_index.hip nn_lists)
@@ -1733,6 +1717,7 @@ int fill_args(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_deg,
   a->T = d_T;
   a->n_h = n_h;
   a->n_tiles = tiles_for(ctx->nQ);
+  a->n_rows = ctx->nQ > 0 ? (ctx->nQ + 63) / 64 : 1;
   // delta*delta in float, as `sq_eps = epsilon*epsilon` (base.cc:1711)
   a->sq_eps = ctx->delta * ctx->delta;
   a->gate_lo = ctx->gate_lo;
@@ -1805,13 +1790,17 @@ int launch_score(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_d
       hpb = hpb < 2 ? 2 : (hpb > 4 ? 4 : hpb);
     }
     // more than 16 per block never paid (tools/tune.py: 16 384 hypotheses 313 us at 8..16 vs 325 us
-    // at 32; 65 536 hypotheses 1168 us at 16 vs 1201 us at 64); an explicit PGP_HPB may go to 64
+    // at 32; 65 536 hypotheses 1168 us at 16 vs 1201 us at 64); an explicit PGP_HPB may go to 64.
+    // Re-swept with one-wave workgroups (C2 weighted step, 4096 hypotheses, median of 7 x 200): 8 per block 78.4 us;
+    // 4: 82.0, 6: 80.3, 10: 80.4, 12: 80.5, 16: 84.6 -- the divisor stays
     if (ctx->hpb_override <= 0 && hpb > 16) hpb = 16;
     if (hpb > kMaxHpb) hpb = kMaxHpb;
     a.hpb = hpb;
     // the last tail_pct % of the hypotheses go in chunks of hpb_tail (C2, tools/tune.py: 10 % in chunks
     // of 2 -> 87-88 us plain / 114-116 us weighted against 90.5 / 119.5 us with uniform chunks; 20-40 %
-    // or chunks of 1, 3, 4 gain less)
+    // or chunks of 1, 3, 4 gain less).  With one-wave workgroups, weighted / plain: 10 % in chunks of 2 -> 78.4 / 67.2 us;
+    // 0 %: 82.0 / 70.1, 5 %: 79.6 / 68.1, 20 %: 79.4 / 67.9, 30 %: 81.4 / 69.9; chunks of 1, 3, 4: 78.9, 78.5, 79.1
+    // weighted (spread of a setting 0.1 us): both stay
     static const int tail_pct = getenv("PGP_TAIL_PCT") ? atoi(getenv("PGP_TAIL_PCT")) : 10;
     static const int tail_hpb = getenv("PGP_TAIL_HPB") ? atoi(getenv("PGP_TAIL_HPB")) : 2;
     a.hpb_tail = tail_hpb > 0 && tail_hpb <= hpb ? tail_hpb : hpb;
@@ -1820,8 +1809,14 @@ int launch_score(pgp_ctx* ctx, const float* d_T, int n_h, int mode, float gate_d
     n_tail_h = n_h - a.n_big * hpb;
     a.n_chunks = a.n_big + (n_tail_h + a.hpb_tail - 1) / a.hpb_tail;
     a.partial = ctx->d_partial.as<uint2>();
-    int chunks_pad = (a.n_chunks + 7) / 8 * 8;
-    dim3 grid((unsigned)(chunks_pad * a.n_tiles));
+    // one workgroup = one wave row of the model under one chunk; the rows of the last tile past the end of
+    // the model are not launched (C2: 79 rows, not 80)
+    const long long n_blocks = (long long)((a.n_chunks + 7) / 8 * 8) * a.n_rows;
+    if (n_blocks > 0x7FFFFFFFll) {
+      set_error("scoring launch of %lld workgroups exceeds the grid limit", n_blocks);
+      return PGP_EINVAL;
+    }
+    dim3 grid((unsigned)n_blocks);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ctx->timing > 0 && (ctx->timing_seq++ % (unsigned)ctx->timing) == 0) {
       if (ctx->ev_used + 2 > ctx->ev.size()) {

@@ -722,7 +722,8 @@ static int reserve_impl(pgp_ctx* ctx, int max_hypotheses) {
   size_t cap = (size_t)max_hypotheses;
   size_t tiles = (size_t)tiles_for(ctx->nQ);
   if ((rc = ctx->d_T.ensure(cap * 16 * sizeof(float))) != PGP_OK) return rc;
-  if ((rc = ctx->d_partial.ensure(tiles * cap * (sizeof(int) + sizeof(float)))) != PGP_OK) return rc;
+  // one row per WAVE of the model: four per tile (lcp_score.hip partial_row)
+  if ((rc = ctx->d_partial.ensure(4 * tiles * cap * (sizeof(int) + sizeof(float)))) != PGP_OK) return rc;
   if ((rc = ctx->d_scores.ensure(cap * sizeof(float))) != PGP_OK) return rc;
   if ((rc = ctx->d_counts.ensure(cap * sizeof(int))) != PGP_OK) return rc;
   if ((rc = ctx->d_eo_ws.ensure(cap * sizeof(int) + 64)) != PGP_OK) return rc;

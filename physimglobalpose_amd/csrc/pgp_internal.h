@@ -304,7 +304,8 @@ struct pgp_ctx {
   // scoring workspace
   int cap_h = 0;
   pgp::DevBuf d_T;        // staged transforms (host API)            [cap_h*16] float
-  pgp::DevBuf d_partial;  // per (tile, hypothesis) partials          [n_tiles*cap_h] int2/float
+  pgp::DevBuf d_partial;  // per (wave row, hypothesis) partials      [4*n_tiles*cap_h] {int, float}, the rows of a tile
+                          // interleaved in pairs (lcp_score.hip partial_row)
   pgp::DevBuf d_scores;   // [cap_h] float
   pgp::DevBuf d_counts;   // [cap_h] int
   pgp::DevBuf d_best;     // 2 x uint64 packed argmax + {index, score bits}
