@@ -183,6 +183,7 @@ def main():
     test_scene_case()
     near_ties_case()
     stocs_case()
+    stocs_edges_case()
     test_scene_frame_case()
     hausdorff_case()
     dead_code_case()
@@ -349,6 +350,30 @@ def stocs_case():
     np.savez_compressed(path, **out)
     print(f"stocs: n={n} keys={len(keys)} pairs with a key {int((feat[:, 0] >= 0).sum())}, chains present",
           [c["present"] for c in chains], f"{os.path.getsize(path)/1024:.0f} KiB")
+
+
+def stocs_edges_case():
+    """(15b) the reference harness's results on the edge scenes of tests/_stocs_scenes.py (generated there, not stored): the features
+    of up to 1000 pairs per scene (int16), the chains of stage weights the GPU test walks and the lattice's hand-picked stage-4 bases.
+    Recorded results only; the stage weights are stored sparsely (indices and values of the non-zeros)."""
+    from _checkers import RefStocs
+    import _stocs_scenes as S
+    out = {}
+    for name in S.SCENES:
+        sc = S.scene(name)
+        ref = RefStocs(sc["P"], sc["N"], sc["prob"], sc["keys"])
+        assert np.array_equal(ref.normals().view(np.uint32), sc["N"].view(np.uint32)), name
+        pr = S.probe_pairs(name, S.FIXTURE_PAIRS)
+        out[f"{name}/digest"] = S.digest(sc)
+        out[f"{name}/feat"] = np.array([ref.ppf(i, j) for i, j in pr.tolist()], np.int32).astype(np.int16)
+        for k, v in S.chain_records(name, ref.stage).items():
+            out[f"{name}/{k}"] = v.astype(np.uint16) if k == "idx" else v
+        if name == "lattice":
+            for k, v in S.triple_records(ref.stage).items():
+                out[f"lattice/triple_{k}"] = v
+    path = os.path.join(HERE, "stocs_edges.npz")
+    np.savez_compressed(path, **out)
+    print(f"stocs_edges: {len(S.SCENES)} scenes, {os.path.getsize(path)/1024:.0f} KiB")
 
 
 def test_scene_frame_case():
@@ -685,6 +710,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "stocs":
         stocs_case()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "stocs_edges":
+        stocs_edges_case()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "near_ties":
         near_ties_case()
