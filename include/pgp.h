@@ -854,6 +854,61 @@ int pgp_backproject_depth(pgp_ctx* ctx, const void* image, int raw16, const unsi
                           int cols, const float K[9], double z_min, double z_max, float* xyz_out, int cap,
                           int* n_out);
 
+/* ---- The segment front end on device arrays: radius filter, centring, weights, and the chain as one call ----
+ * pgp_radius_outlier_filter with DEVICE pointers, and with what the host form leaves to its caller done on the
+ * device too: the same rule (k = points with squared distance STRICTLY below radius^2, the point itself included;
+ * kept iff k > min_neighbors), then ONE ordered compaction.  min(*n_kept, cap) rows are written IN INPUT ORDER:
+ * d_out_xyz the position, d_out_index (nullable) the input index, d_out_nrm (nullable; written when d_nrm is given
+ * too) the normal flipped towards (0,0,0) when (0 - p).n < 0 and divided by its magnitude, float operations in the
+ * host form's order -- a zero normal gives NaN, as there.  *n_kept (host) = the full count; `stream` is synchronised
+ * for it.  As the host form, it builds the index of d_xyz with delta = radius in the context: the RESIDENT SCENE IS
+ * REPLACED by it, so call it before pgp_set_scene / pgp_set_scene_device.  Outputs that overlap the inputs or each
+ * other, and radius <= 0, are PGP_EINVAL; n == 0 is PGP_OK with *n_kept = 0. */
+int pgp_radius_outlier_filter_device(pgp_ctx* ctx, const float* d_xyz, const float* d_nrm, int n, float radius,
+                                     int min_neighbors, float* d_out_xyz, float* d_out_nrm, int* d_out_index, int cap,
+                                     int* n_kept, void* stream);
+
+/* pgp_center for ONE cloud of n x 3 device floats, in place: centroid += pos in index order in float, / (float)n,
+ * every point minus the centroid (base.cc:242-264) -- the same bits as pgp_center.  The sum is sequential (one lane
+ * adds; a tree sum gives other bits), so the call costs time proportional to n.  centroid[3] (host) receives the
+ * centroid; `stream` is synchronised for it.  n == 0 is PGP_EINVAL (the host helper divides by zero there).
+ * pgp_shift_device subtracts a vector the caller has (the models are centred on centroid_Q) the same way; it is
+ * enqueued and not synchronised. */
+int pgp_center_device(pgp_ctx* ctx, float* d_xyz, int n, float centroid[3], void* stream);
+int pgp_shift_device(pgp_ctx* ctx, float* d_xyz, int n, const float shift[3], void* stream);
+
+/* pgp_weights_from_image with DEVICE pointers (d_xyz_centred: n x 3, d_img: rows x cols u16, d_weights: n): the same
+ * arithmetic per point, the same bits; a point outside the image gets weight 0.  Enqueued on `stream`, not
+ * synchronised. */
+int pgp_weights_from_image_device(pgp_ctx* ctx, const float* d_xyz_centred, int n, const float centroid_P[3],
+                                  const float K[9], const unsigned short* d_img, int rows, int cols, float* d_weights,
+                                  void* stream);
+
+/* Depth image -> scene in one call, every intermediate in a workspace of the context (it grows on demand):
+ * pgp_backproject_depth_device -> pgp_voxel_grid_device -> pgp_mls_normals_device -> pgp_radius_outlier_filter_device
+ * -> pgp_center_device -> pgp_weights_from_image_device -> pgp_set_scene_device with normals and weights; the result
+ * is what those calls give one after the other.  d_prob (nullable): the probability image, rows x cols u16; without
+ * it every weight is 1.  counts[4] = points back-projected, voxel leaves, MLS rows, rows the filter kept.  When the
+ * filter keeps at most min_points rows the node bails out (ObjectPoseCandidateSet.cpp:34-37): *installed = 0, PGP_OK,
+ * and the context has NO scene (scoring returns PGP_ESTATE).  Otherwise *installed = 1, centroid_P the centroid the
+ * scene was centred on, and the scene is the centred, oriented, weighted segment: pgp_score_lcp in
+ * PGP_MODE_WEIGHTED works on it at once.  `stream` is synchronised once per stage count. */
+typedef struct pgp_segment_options {
+  double z_min, z_max;     /* 0.1, 2.0 */
+  float voxel_leaf;        /* 0.01 */
+  float mls_radius;        /* 0.02 */
+  float filter_radius;     /* 0.03 */
+  int   min_neighbors;     /* 10 */
+  int   min_points;        /* 30: at most this many kept -> no scene, as the node bails */
+  float delta;             /* 0.005 */
+} pgp_segment_options;
+int pgp_segment_default_options(pgp_segment_options* opt);
+int pgp_segment_from_depth_device(pgp_ctx* ctx, const pgp_segment_options* opt, const void* d_image, int raw16,
+                                  const unsigned char* d_mask, int rows, int cols, const float K[9],
+                                  const unsigned short* d_prob /*nullable: weights 1*/,
+                                  int counts[4] /* back-projected, voxels, MLS rows, kept */, int* installed,
+                                  float centroid_P[3], void* stream);
+
 /* ---- Table-plane removal (SceneCfg::removeTable / getTableParams, PPE/data_layer/SceneCfg.cpp:38-157) ----
  * Replaces pcl::SACSegmentation with SACMODEL_PLANE, SAC_MSAC, setDistanceThreshold(0.005),
  * setMaxIterations(1000), setOptimizeCoefficients(true), and the loop that zeroes the depth pixels near the

@@ -61,6 +61,11 @@ class ClusterParams(C.Structure):
     _fields_ = [("accept_fraction", C.c_float), ("rot_thresh_deg", C.c_float), ("trans_thresh", C.c_float)]
 
 
+class SegmentOptions(C.Structure):
+    _fields_ = [("z_min", C.c_double), ("z_max", C.c_double), ("voxel_leaf", C.c_float), ("mls_radius", C.c_float),
+                ("filter_radius", C.c_float), ("min_neighbors", C.c_int), ("min_points", C.c_int), ("delta", C.c_float)]
+
+
 PGP_PLANE_STOP_ADAPTIVE = 0
 PGP_PLANE_STOP_ALL = 1
 
@@ -231,6 +236,15 @@ SIGNATURES = {
     "pgp_pose_hausdorff": (C.c_int, [C.c_void_p, _f, C.c_int, _f, C.c_int, _i, C.c_int, _f, _f]),
     "pgp_backproject_depth_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _f,
                                                C.c_double, C.c_double, C.c_void_p, C.c_int, _i, C.c_void_p]),
+    "pgp_radius_outlier_filter_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i, C.c_void_p]),
+    "pgp_center_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _f, C.c_void_p]),
+    "pgp_shift_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _f, C.c_void_p]),
+    "pgp_weights_from_image_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _f, _f, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p]),
+    "pgp_segment_default_options": (C.c_int, [C.POINTER(SegmentOptions)]),
+    "pgp_segment_from_depth_device": (C.c_int, [C.c_void_p, C.POINTER(SegmentOptions), C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_int, _f, C.c_void_p, _i, _i, _f, C.c_void_p]),
     "pgp_cluster_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, _f,
                                            C.POINTER(ClusterParams), C.c_void_p, C.c_void_p, _i, C.c_void_p]),
     "pgp_depth_cost": (C.c_int, [C.c_void_p, _f, _f, C.c_int, C.c_int, C.c_int, C.c_float, _f, _i]),

@@ -264,7 +264,8 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
                     &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io, &ctx->d_Prgb, &ctx->d_Qs_nrm, &ctx->d_Qs_rgb,
-                    &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io};
+                    &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io,
+                    &ctx->d_seg_ws, &ctx->d_seg_c, &ctx->d_seg_cloud, &ctx->d_seg_leaves, &ctx->d_seg_rows};
   for (DevBuf* b : bufs) b->release();
   ctx->d_out.release();
   for (PinBuf* b : {&ctx->h_pin, &ctx->h_sel_pin, &ctx->h_w_pin, &ctx->h_s_pin}) b->release();
@@ -2454,6 +2455,174 @@ int pgp_backproject_depth_device(pgp_ctx* ctx, const void* d_image, int raw16, c
   uint32_t* d_scan = reinterpret_cast<uint32_t*>(ctx->d_bp.as<unsigned char>() + ctr_bytes);
   return launch_backproject(ctx, d_image, raw16 != 0, d_mask, rows, cols, K, z_min, z_max, d_ctr, d_scan, d_xyz_out, cap,
                             n_out, static_cast<hipStream_t>(stream));
+}
+
+// ---- the segment front end on device arrays (segment.hip) -----------------------------------------------------------
+namespace {
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+}  // namespace
+
+int pgp_radius_outlier_filter_device(pgp_ctx* ctx, const float* d_xyz, const float* d_nrm, int n, float radius,
+                                     int min_neighbors, float* d_out_xyz, float* d_out_nrm, int* d_out_index, int cap,
+                                     int* n_kept, void* stream) {
+  if (!ctx || n < 0 || cap < 0 || !n_kept || !(radius > 0.f) || !std::isfinite(radius) || (n > 0 && !d_xyz) ||
+      (cap > 0 && !d_out_xyz)) {
+    set_error("pgp_radius_outlier_filter_device: bad argument");
+    return PGP_EINVAL;
+  }
+  {
+    const void* in[2] = {d_xyz, d_nrm};
+    const void* out[3] = {d_out_xyz, d_out_nrm, d_out_index};
+    const size_t out_bytes[3] = {(size_t)cap * 12, (size_t)cap * 12, (size_t)cap * 4};
+    bool clash = false;
+    for (int o = 0; o < 3; ++o) {
+      for (int i = 0; i < 2; ++i) clash = clash || ranges_overlap(in[i], (size_t)n * 12, out[o], out_bytes[o]);
+      for (int p = o + 1; p < 3; ++p) clash = clash || ranges_overlap(out[o], out_bytes[o], out[p], out_bytes[p]);
+    }
+    if (clash) {
+      set_error("pgp_radius_outlier_filter_device: the outputs overlap the inputs or each other");
+      return PGP_EINVAL;
+    }
+  }
+  *n_kept = 0;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  PGP_HIP(hipStreamSynchronize(st));   // the producer of d_xyz
+  PGP_HIP(hipDeviceSynchronize());     // queued launches may still read the scene replaced below
+  int rc = launch_radius_filter(ctx, d_xyz, d_nrm, n, radius, min_neighbors, d_out_xyz, d_out_nrm, d_out_index, cap, n_kept, st);
+  if (rc != PGP_OK) return rc;
+  return index_settled(ctx);   // the stream that waited for the temporary index has been synchronised
+}
+
+int pgp_center_device(pgp_ctx* ctx, float* d_xyz, int n, float centroid[3], void* stream) {
+  if (!ctx || n <= 0 || !d_xyz || !centroid) {   // n == 0: the host helper divides by zero there
+    set_error("pgp_center_device: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = ctx->d_seg_c.ensure(256);
+  if (rc != PGP_OK) return rc;
+  if ((rc = launch_center(d_xyz, n, ctx->d_seg_c.as<float>(), nullptr, st)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(centroid, ctx->d_seg_c.p, 12, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+int pgp_shift_device(pgp_ctx* ctx, float* d_xyz, int n, const float shift[3], void* stream) {
+  if (!ctx || n < 0 || (n > 0 && !d_xyz) || !shift) {
+    set_error("pgp_shift_device: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx, false);
+  return launch_center(d_xyz, n, nullptr, shift, static_cast<hipStream_t>(stream));
+}
+
+int pgp_weights_from_image_device(pgp_ctx* ctx, const float* d_xyz_centred, int n, const float centroid_P[3],
+                                  const float K[9], const unsigned short* d_img, int rows, int cols, float* d_weights,
+                                  void* stream) {
+  if (!ctx || n < 0 || rows < 0 || cols < 0 || (n > 0 && (!d_xyz_centred || !d_weights)) || !centroid_P || !K ||
+      ((size_t)rows * cols > 0 && !d_img)) {
+    set_error("pgp_weights_from_image_device: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx, false);
+  return launch_weights_from_image(d_xyz_centred, n, centroid_P, K, d_img, rows, cols, d_weights,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int pgp_segment_default_options(pgp_segment_options* opt) {
+  if (!opt) {
+    set_error("pgp_segment_default_options: bad argument");
+    return PGP_EINVAL;
+  }
+  opt->z_min = 0.1;             // utilities.cpp:197
+  opt->z_max = 2.0;
+  opt->voxel_leaf = 0.01f;      // Segmentation.cpp:235
+  opt->mls_radius = 0.02f;      // Segmentation.cpp:243
+  opt->filter_radius = 0.03f;   // ObjectPoseCandidateSet.cpp:30
+  opt->min_neighbors = 10;      // :31
+  opt->min_points = 30;         // :34
+  opt->delta = 0.005f;          // super4pcs_test.cc:20
+  return PGP_OK;
+}
+
+// A composition of the entry points above: every stage is the single call a caller would make, on the context's workspace.
+int pgp_segment_from_depth_device(pgp_ctx* ctx, const pgp_segment_options* opt, const void* d_image, int raw16,
+                                  const unsigned char* d_mask, int rows, int cols, const float K[9],
+                                  const unsigned short* d_prob, int counts[4], int* installed, float centroid_P[3],
+                                  void* stream) {
+  if (!ctx || !opt || rows < 0 || cols < 0 || !K || !counts || !installed || !centroid_P ||
+      ((size_t)rows * cols > 0 && !d_image) || (size_t)rows * cols > ((size_t)1 << 30) || !(opt->voxel_leaf > 0.f) ||
+      !(opt->mls_radius > 0.f) || !(opt->filter_radius > 0.f) || !(opt->delta > 0.f) || !std::isfinite(opt->delta) ||
+      opt->min_points < 0) {
+    set_error("pgp_segment_from_depth_device: bad argument");
+    return PGP_EINVAL;
+  }
+  for (int k = 0; k < 4; ++k) counts[k] = 0;
+  for (int k = 0; k < 3; ++k) centroid_P[k] = 0.f;
+  *installed = 0;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t n_pix = (size_t)rows * cols;
+  int rc;
+  // 1. back-projection: the buffer holds what the last frames needed; a mask that keeps more runs the pass again
+  if (ctx->d_seg_cloud.cap < 12 && (rc = ctx->d_seg_cloud.ensure(std::min<size_t>(std::max<size_t>(n_pix, 1), 65536) * 12)) != PGP_OK)
+    return rc;
+  int cap0 = (int)std::min<size_t>(ctx->d_seg_cloud.cap / 12, n_pix);
+  rc = pgp_backproject_depth_device(ctx, d_image, raw16, d_mask, rows, cols, K, opt->z_min, opt->z_max,
+                                    ctx->d_seg_cloud.as<float>(), cap0, &counts[0], stream);
+  if (rc != PGP_OK) return rc;
+  if (counts[0] > cap0) {
+    if ((rc = ctx->d_seg_cloud.ensure((size_t)counts[0] * 12)) != PGP_OK) return rc;
+    rc = pgp_backproject_depth_device(ctx, d_image, raw16, d_mask, rows, cols, K, opt->z_min, opt->z_max,
+                                      ctx->d_seg_cloud.as<float>(), counts[0], &counts[0], stream);
+    if (rc != PGP_OK) return rc;
+  }
+  // 2. voxel grid
+  const int n0 = counts[0];
+  if ((rc = ctx->d_seg_leaves.ensure((size_t)std::max(n0, 1) * 12)) != PGP_OK) return rc;
+  rc = pgp_voxel_grid_device(ctx, ctx->d_seg_cloud.as<float>(), n0, opt->voxel_leaf, ctx->d_seg_leaves.as<float>(), n0,
+                             &counts[1], stream);
+  if (rc != PGP_OK) return rc;
+  // 3. MLS normals; 4. filter + flip
+  const int n1 = counts[1];
+  Carve lay;
+  const size_t r1 = (size_t)std::max(n1, 1);
+  const auto p_mx = lay.add<float>(3 * r1, 256), p_mn = lay.add<float>(3 * r1, 256), p_fx = lay.add<float>(3 * r1, 256),
+             p_fn = lay.add<float>(3 * r1, 256), p_w = lay.add<float>(r1, 256);
+  if ((rc = lay.ensure(ctx->d_seg_rows)) != PGP_OK) return rc;
+  rc = pgp_mls_normals_device(ctx, ctx->d_seg_leaves.as<float>(), n1, opt->mls_radius, lay.at(p_mx), lay.at(p_mn), nullptr,
+                              nullptr, n1, &counts[2], stream);
+  if (rc != PGP_OK) return rc;
+  const int n2 = counts[2];
+  int n3 = 0;
+  if (n2 > 0) {
+    rc = pgp_radius_outlier_filter_device(ctx, lay.at(p_mx), lay.at(p_mn), n2, opt->filter_radius, opt->min_neighbors,
+                                          lay.at(p_fx), lay.at(p_fn), nullptr, n1, &n3, stream);
+    if (rc != PGP_OK) return rc;
+  }
+  counts[3] = n3;
+  if (n3 <= opt->min_points) {   // the node bails out here (ObjectPoseCandidateSet.cpp:34-37): no scene
+    if ((rc = pgp_set_scene_device(ctx, nullptr, nullptr, nullptr, 0, opt->delta, stream)) != PGP_OK) return rc;
+    ctx->has_index = false;
+    return PGP_OK;
+  }
+  // 5. centring; 6. weights; 7. the scene
+  if ((rc = pgp_center_device(ctx, lay.at(p_fx), n3, centroid_P, stream)) != PGP_OK) return rc;
+  if (d_prob) {
+    rc = pgp_weights_from_image_device(ctx, lay.at(p_fx), n3, centroid_P, K, d_prob, rows, cols, lay.at(p_w), stream);
+    if (rc != PGP_OK) return rc;
+  }
+  rc = pgp_set_scene_device(ctx, lay.at(p_fx), lay.at(p_fn), d_prob ? lay.at(p_w) : nullptr, n3, opt->delta, stream);
+  if (rc != PGP_OK) return rc;
+  *installed = 1;
+  return PGP_OK;
 }
 
 int pgp_cluster_poses_device(pgp_ctx* ctx, const float* d_T, const float* d_scores, int n_h, float best_score,

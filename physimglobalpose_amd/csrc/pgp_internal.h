@@ -264,6 +264,9 @@ struct pgp_ctx {
   pgp::DevBuf d_mls_ws;                      // mls.hip: sort keys, sorted cloud, per-point results
   pgp::DevBuf d_plane_ws, d_plane_io;        // plane.hip: candidate / partial workspace; host-API staging
   bool hd_attr_set = false;
+  // segment.hip: the filter's counts | workgroup counters | scan scratch, and the centroid of pgp_center_device (d_seg_c);
+  // the intermediates of pgp_segment_from_depth_device: dense cloud, voxel leaves, the MLS and filter rows + weights
+  pgp::DevBuf d_seg_ws, d_seg_c, d_seg_cloud, d_seg_leaves, d_seg_rows;
 
   pgp::DevBuf d_depth;   // depth-cost staging: observed | rendered[n] | counts
   pgp::DevBuf d_render_ws, d_render_io;   // render.hip: projected vertices [n][n_vert]; host-API staging
@@ -703,6 +706,13 @@ int launch_pose_hausdorff(pgp_ctx* ctx, const float4* d_hull, int n_hull, const 
                           const int2* d_pairs, int m, float* d_max, float* d_sum, hipStream_t st);
 int set_scene_device(pgp_ctx* ctx, const float* d_xyz, const float* d_nrm, const float* d_w, int n, float delta,
                      hipStream_t st);
+
+// segment.hip
+int launch_radius_filter(pgp_ctx* ctx, const float* d_xyz, const float* d_nrm, int n, float radius, int min_neighbors,
+                         float* d_out_xyz, float* d_out_nrm, int* d_out_index, int cap, int* n_kept, hipStream_t st);
+int launch_center(float* d_xyz, int n, float* d_centroid, const float shift[3], hipStream_t st);
+int launch_weights_from_image(const float* d_xyz, int n, const float c[3], const float K[9], const unsigned short* d_img,
+                              int rows, int cols, float* d_weights, hipStream_t st);
 
 // mls.hip
 int launch_mls(pgp_ctx* ctx, const float* d_xyz, int n, float radius, float* d_out_xyz, float* d_out_nrm,

@@ -645,6 +645,74 @@ class LcpScorer:
             C.c_void_p(d_weight.data_ptr()) if d_weight is not None else None, int(n), C.c_float(delta), C.c_void_p(st)))
         self.nP, self.delta = int(n), float(delta)
 
+    def radius_outlier_filter_device(self, d_xyz, n, d_nrm, radius, min_neighbors, d_out_xyz, d_out_nrm=None,
+                                     d_out_index=None):
+        """The filter, the flip and the compaction on device arrays: min(kept, rows of d_out_xyz) rows in input order;
+        returns the full count.  Replaces the resident scene (the index of d_xyz at delta = radius)."""
+        import torch
+        kept = C.c_int(0)
+        st = torch.cuda.current_stream(d_xyz.device).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_radius_outlier_filter_device(
+            self._h, p(d_xyz), p(d_nrm), int(n), C.c_float(radius), int(min_neighbors), p(d_out_xyz), p(d_out_nrm),
+            p(d_out_index), int(d_out_xyz.shape[0]), C.byref(kept), C.c_void_p(st)))
+        self.nP, self.delta = int(n), float(radius)
+        return kept.value
+
+    def center_device(self, d_xyz, n):
+        """base.cc:242-264 for one device cloud, in place; returns the centroid (3,) float32."""
+        import torch
+        c = np.zeros(3, np.float32)
+        st = torch.cuda.current_stream(d_xyz.device).cuda_stream
+        _lib.check(self._lib.pgp_center_device(self._h, C.c_void_p(d_xyz.data_ptr()), int(n), _fp(c), C.c_void_p(st)))
+        return c
+
+    def shift_device(self, d_xyz, n, shift):
+        import torch
+        s = np.ascontiguousarray(shift, np.float32).reshape(3)
+        st = torch.cuda.current_stream(d_xyz.device).cuda_stream
+        _lib.check(self._lib.pgp_shift_device(self._h, C.c_void_p(d_xyz.data_ptr()), int(n), _fp(s), C.c_void_p(st)))
+
+    def weights_from_image_device(self, d_xyz_centred, n, centroid_P, K, d_img, d_weights):
+        """base.cc:317-340 on device arrays; d_img (rows, cols) 16-bit.  Enqueued on the current stream."""
+        import torch
+        assert d_img.is_cuda and d_img.is_contiguous() and d_img.dtype in (torch.uint16, torch.int16)
+        rows, cols = d_img.shape
+        c, K9 = np.ascontiguousarray(centroid_P, np.float32).reshape(3), np.ascontiguousarray(K, np.float32).reshape(9)
+        st = torch.cuda.current_stream(d_img.device).cuda_stream
+        _lib.check(self._lib.pgp_weights_from_image_device(
+            self._h, C.c_void_p(d_xyz_centred.data_ptr()), int(n), _fp(c), _fp(K9), C.c_void_p(d_img.data_ptr()), rows, cols,
+            C.c_void_p(d_weights.data_ptr()), C.c_void_p(st)))
+
+    @staticmethod
+    def segment_options(**kw):
+        """pgp_segment_options with the node's values, fields overridden by keyword."""
+        o = _lib.SegmentOptions()
+        _lib.check(_lib.load().pgp_segment_default_options(C.byref(o)))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError(f"pgp_segment_options has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def segment_from_depth_device(self, d_image, K, d_mask, d_prob=None, options=None):
+        """Depth image -> centred, oriented, weighted scene in one call, every intermediate in HBM.  Returns
+        (counts (4,) int32: back-projected, voxels, MLS rows, kept; installed bool; centroid_P (3,) float32)."""
+        import torch
+        rows, cols = d_image.shape
+        assert d_image.is_cuda and d_image.is_contiguous() and d_image.dtype in (torch.uint16, torch.int16, torch.float32)
+        raw16 = int(d_image.dtype != torch.float32)
+        o = options if options is not None else self.segment_options()
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        counts, installed, c = np.zeros(4, np.int32), C.c_int(0), np.zeros(3, np.float32)
+        st = torch.cuda.current_stream(d_image.device).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_segment_from_depth_device(
+            self._h, C.byref(o), p(d_image), raw16, p(d_mask), rows, cols, _fp(K9), p(d_prob), counts.ctypes.data_as(_i),
+            C.byref(installed), _fp(c), C.c_void_p(st)))
+        self.nP, self.delta = (int(counts[3]), float(o.delta)) if installed.value else (0, None)
+        return counts, bool(installed.value), c
+
     def cluster_poses_device(self, d_T, d_scores, best_score, d_rep, d_assign, sym_deg=(0, 0, 0), accept_fraction=0.5,
                              rot_thresh_deg=10.0, trans_thresh=0.02):
         import torch
