@@ -40,9 +40,11 @@ using exact::sub;
 
 constexpr int kPoseStride = 12;  // per sorted pose: 9 floats of a 3x3 (row-major) + translation
 
-// float -> uint32 whose unsigned order is the float order (NaN never reaches here)
+// float -> uint32 whose unsigned order is the float order (NaN never reaches here).  -0.0f == +0.0f as floats, so both
+// get +0.0f's key: equal scores differ in the index alone ("equal scores in index order", include/pgp.h)
 __device__ __forceinline__ uint32_t orderable(float f) {
-  const uint32_t b = __float_as_uint(f);
+  uint32_t b = __float_as_uint(f);
+  if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
