@@ -1297,7 +1297,7 @@ int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_ob
  * is bound at run time and only when the group has more than one device (or
  * PGP_MULTI_FORCE_COLLECTIVE=1).  Every member's worker thread queues its slice, its own ncclAllReduce (one
  * communicator per device) and, on member 0, the arg-max and the copy back: one rendezvous of the calling thread per
- * call (PGP_MULTI_COLL=grouped issues the collective for all members from the calling thread inside one group instead).
+ * call.
  * Member 0 holds all transforms (it settles near-ties across slices), the others copy their slice only.
  * Calls on one pgp_multi must not overlap. */
 typedef struct pgp_multi pgp_multi;

@@ -10,8 +10,8 @@
 // arrays a single-device pgp_score_lcp returns.
 //
 // One process, one host thread + one stream per device (the worker owns hipSetDevice for its
-// thread); the calling thread only copies the transforms into a pinned buffer, posts one job per
-// worker, issues the grouped collective and waits for device 0.  RCCL is bound at run time
+// thread); the calling thread copies the transforms into a pinned buffer, posts one job per worker
+// and runs member 0's share itself; every member issues its own collective.  RCCL is bound at run time
 // (dlopen of librccl.so.1, the library torch's "nccl" backend is): libpgp.so has no link-time
 // dependency on it and a single-device group needs no collective at all (PGP_MULTI_FORCE_COLLECTIVE=1
 // runs a one-rank communicator anyway -- the GPU test of the exchange path on a 1-GPU box).
@@ -128,7 +128,7 @@ struct ShmExchange {
 constexpr size_t kShmCap = (size_t)16 << 20;   // per buffer: 2 M hypotheses
 
 constexpr int kSlots = 16;        // resident hypothesis batches of the streaming form
-constexpr int kEmulateMax = 16;   // members of an emulated group the streaming form's sum kernel takes
+constexpr int kEmulateMax = 16;   // members of an emulated group: what the sum kernel takes by value (create_group refuses more)
 
 struct pgp_multi {
   int n = 0;                      // members in THIS process
@@ -142,12 +142,12 @@ struct pgp_multi {
   std::vector<hipStream_t> stream;
   std::vector<Worker*> worker;
   bool use_coll = false;
-  bool grouped = false;   // PGP_MULTI_COLL=grouped: the collective is issued for all members by the calling thread
-  bool emulate = false;   // PGP_MULTI_EMULATE: members share one device, exchange = emulate_sum
+  bool emulate = false;   // PGP_MULTI_EMULATE: members share one device, exchange = emulate_sum_args
   bool emulate_ranked = false;   // PGP_MULTI_EMULATE_RANKED: a ranked group's exchange through shared memory (ShmExchange)
   ShmExchange shm;
   std::vector<hipEvent_t> ev;   // emulate: one event per member
-  DevBuf d_sum;                 // emulate: the summed vector before it is handed to every member
+  DevBuf d_sum;                 // emulate: the summed vector before it is handed to every member (sized by the uploads)
+  int fail[kEmulateMax] = {};   // emulate: member k's slice failed to queue (exchange(): its owner's before the first barrier)
   Rccl rccl;
   std::vector<ncclComm_t> comm;
   // per device: the transform list (member 0: all of it; the others: their slice, in place) and the full-length
@@ -201,13 +201,16 @@ namespace {
 
 // out[i] = sum over members of in[k][i] over the 2 n_h 32-bit words {scores | counts}, as INTEGERS -- what the one
 // RCCL all-reduce of the production path computes (every element is non-zero in at most one member, so the sum of
-// the bit patterns is that member's pattern, for the float scores too)
-__global__ __launch_bounds__(256) void emulate_sum(const float* const* __restrict__ in, int n_members, int n_h,
-                                                   float* __restrict__ out) {
+// the bit patterns is that member's pattern, for the float scores too).  The members' vectors are passed by value:
+// nothing to upload, nothing to wait for on the host.
+struct SumPtrs {
+  const float* p[kEmulateMax];
+};
+__global__ __launch_bounds__(256) void emulate_sum_args(SumPtrs in, int n_members, int n_h, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 2 * n_h) return;
   int s = 0;
-  for (int k = 0; k < n_members; ++k) s += reinterpret_cast<const int*>(in[k])[i];
+  for (int k = 0; k < n_members; ++k) s += reinterpret_cast<const int*>(in.p[k])[i];
   reinterpret_cast<int*>(out)[i] = s;
 }
 
@@ -227,36 +230,22 @@ int on_caller(pgp_multi* m, const std::function<int()>& job) {
 // fn(k) for every member: members 1 .. n-1 on their worker threads, member 0 -- the one whose work ends the call: the arg-max
 // and the way home -- on the calling thread itself: a hand-off to a worker and back costs the call ~20 us (0.146 against
 // 0.127 ms for a one-member group's host-pointer call), and a group of one then hands nothing off at all.
-// PGP_MULTI_CALLER_RUNS=0: every member on its worker (the form up to round 5).
 int run_all(pgp_multi* m, const std::function<int(int)>& fn) {
-  static const bool caller_runs = !(getenv("PGP_MULTI_CALLER_RUNS") && atoi(getenv("PGP_MULTI_CALLER_RUNS")) == 0);
-  const int first = caller_runs ? 1 : 0;
-  for (int k = first; k < m->n; ++k) m->worker[k]->post([&fn, k] { return fn(k); });
-  int rc = PGP_OK;
-  if (caller_runs) {
-    char keep[512] = "";
-    rc = on_caller(m, [&fn] { return fn(0); });
-    if (rc != PGP_OK) {   // (the text is this thread's own already: keep it across the waits below)
-      std::strncpy(keep, pgp_last_error(), sizeof keep - 1);
-      keep[sizeof keep - 1] = 0;
-    }
-    for (int k = 1; k < m->n; ++k) {
-      const int r = m->worker[k]->wait();
-      if (r != PGP_OK && rc == PGP_OK) {
-        rc = r;
-        set_error("device %d: %s", m->dev[k], m->worker[k]->err);
-      }
-    }
-    if (keep[0]) set_error("device %d: %s", m->dev[0], keep);
-    return rc;
+  for (int k = 1; k < m->n; ++k) m->worker[k]->post([&fn, k] { return fn(k); });
+  char keep[512] = "";
+  int rc = on_caller(m, [&fn] { return fn(0); });
+  if (rc != PGP_OK) {   // (the text is this thread's own already: keep it across the waits below)
+    std::strncpy(keep, pgp_last_error(), sizeof keep - 1);
+    keep[sizeof keep - 1] = 0;
   }
-  for (int k = 0; k < m->n; ++k) {
-    int r = m->worker[k]->wait();
+  for (int k = 1; k < m->n; ++k) {
+    const int r = m->worker[k]->wait();
     if (r != PGP_OK && rc == PGP_OK) {
       rc = r;
       set_error("device %d: %s", m->dev[k], m->worker[k]->err);
     }
   }
+  if (keep[0]) set_error("device %d: %s", m->dev[0], keep);
   return rc;
 }
 
@@ -313,6 +302,131 @@ int shm_exchange(pgp_multi* m, float* d_s, int N, hipStream_t st) {
   return PGP_OK;
 }
 
+// A contiguous piece of a member's slice into {d_scores, d_counts} on `st`.  The passes over the COMPLETE vector --
+// exact records (pgp_set_exact_records on member 0's context) and Verify's early termination, which depends on ALL earlier
+// hypotheses of the object -- are off for the call and back on whichever way it returns: they belong to complete_tail.
+// d_best: null, or where the call publishes the best of its piece (the streaming form's empty batch).
+int score_piece(pgp_ctx* c, const float* d_T, int n, int mode, float gate_deg, float* d_scores, int* d_counts, int* d_best,
+                hipStream_t st) {
+  struct PassesOff {
+    pgp_ctx* c;
+    const bool records, early;
+    explicit PassesOff(pgp_ctx* ctx) : c(ctx), records(ctx->exact_records), early(ctx->verify_early_out) {
+      c->exact_records = false;
+      c->verify_early_out = false;
+    }
+    ~PassesOff() {
+      c->exact_records = records;
+      c->verify_early_out = early;
+    }
+  } off(c);
+  return pgp_score_lcp_device(c, d_T, n, mode, gate_deg, d_scores, d_counts, d_best, st);
+}
+
+// Which of a group's per-member things one exchange works on: the flat form's (b < 0) or ring[b] of the streaming form.
+struct Lane {
+  int b;
+  float* vec(pgp_multi* m, int j) const { return (b < 0 ? m->d_all[j] : m->s2[(size_t)j].ring[b]).as<float>(); }   // what is reduced
+  hipStream_t stream(pgp_multi* m, int j) const { return b < 0 ? m->stream[j] : m->s2[(size_t)j].x; }   // where the exchange runs
+  hipEvent_t queued(pgp_multi* m, int j) const { return b < 0 ? m->ev[j] : m->s2[(size_t)j].scored[b]; }   // j's slice is queued
+  hipEvent_t handed_out(pgp_multi* m) const { return b < 0 ? m->ev[0] : m->ev_sum[b]; }   // emulate: every member has the sum
+};
+
+// The emulated exchange's device side, by member 0 on its exchange stream: wait for every slice, sum, hand the sum out.
+int emulated_sum(pgp_multi* m, Lane lane, int N) {
+  hipStream_t X = lane.stream(m, 0);
+  SumPtrs ptrs{};
+  for (int j = 0; j < m->n; ++j) {
+    ptrs.p[j] = lane.vec(m, j);
+    if (j > 0) PGP_HIP(hipStreamWaitEvent(X, lane.queued(m, j), 0));
+  }
+  float* d_out = m->d_sum.as<float>();
+  hipLaunchKernelGGL(emulate_sum_args, dim3((2 * N + 255) / 256), dim3(256), 0, X, ptrs, m->n, N, d_out);
+  PGP_HIP(hipGetLastError());
+  for (int j = 0; j < m->n; ++j) PGP_HIP(hipMemcpyAsync(lane.vec(m, j), d_out, (size_t)N * 8, hipMemcpyDeviceToDevice, X));
+  PGP_HIP(hipEventRecord(lane.handed_out(m), X));
+  return PGP_OK;
+}
+
+// ONE all-reduce over the 8 N bytes {scores | counts} of lane.vec, summed as 32-bit integers: every element is non-zero on
+// exactly one member (its owner) and all-zero bits elsewhere, and x + 0 + ... + 0 over the BIT PATTERNS returns x's pattern --
+// exact for the float scores too (scores are >= +0: no -0, no NaN).  At 4096 hypotheses the exchange is latency-bound (32 KB
+// per member), so two collectives cost twice what one does.  Member k calls this from its own thread, behind its slice on
+// stream[k]; rc_slice is what queueing that slice returned.  Three transports: RCCL (one communicator per member, the
+// multi-thread form RCCL documents), the shared segment of a ranked emulation, and on ONE device (PGP_MULTI_EMULATE) member
+// 0's sum kernel.  The contract, for all of them:
+//  - every member reaches the collective, or BOTH barriers of the emulated exchange, whether or not its own slice failed to
+//    queue: the others' streams (threads) would wait for it forever;
+//  - a member returns its own error first, then the exchange's, then "another member of the group failed";
+//  - member 0 sums only when nobody failed, and members k > 0 make their exchange stream wait for the hand-out only when
+//    everything succeeded;
+//  - fail[] is written by its owner before the first barrier and by member 0 between the two, and read after each.
+int exchange(pgp_multi* m, int k, Lane lane, int N, int rc_slice) {
+  hipStream_t S = m->stream[k], X = lane.stream(m, k);
+  if (rc_slice == PGP_OK && (m->emulate || X != S)) {   // the slice is queued: X (and member 0's sum) behind it
+    if (hipEventRecord(lane.queued(m, k), S) != hipSuccess) rc_slice = PGP_EHIP;
+    if (rc_slice == PGP_OK && X != S && hipStreamWaitEvent(X, lane.queued(m, k), 0) != hipSuccess) rc_slice = PGP_EHIP;
+  }
+  int rc_x = PGP_OK;
+  if (!m->emulate) {
+    if (m->emulate_ranked) {
+      rc_x = shm_exchange(m, lane.vec(m, k), N, X);   // (host-synchronous: X is behind the slice)
+    } else {
+      float* d_s = lane.vec(m, k);
+      const ncclResult_t nr = m->rccl.AllReduce(d_s, d_s, 2 * (size_t)N, ncclInt32, ncclSum, m->comm[(size_t)k], X);
+      if (nr != ncclSuccess) {
+        set_error("ncclAllReduce failed: %s", m->rccl.GetErrorString(nr));
+        rc_x = PGP_EHIP;
+      }
+    }
+    return rc_slice != PGP_OK ? rc_slice : rc_x;
+  }
+  m->fail[k] = rc_slice != PGP_OK;
+  m->barrier();   // every member's slice is queued (or has failed)
+  bool any = false;
+  for (int j = 0; j < m->n; ++j) any = any || m->fail[j];
+  if (k == 0 && !any) {
+    rc_x = emulated_sum(m, lane, N);
+    m->fail[0] = rc_x != PGP_OK;
+  }
+  m->barrier();   // the sum is queued
+  if (rc_slice != PGP_OK) return rc_slice;
+  if (rc_x != PGP_OK) return rc_x;
+  if (any || m->fail[0]) {
+    set_error("another member of the group failed");
+    return PGP_EHIP;
+  }
+  if (k > 0) PGP_HIP(hipStreamWaitEvent(X, lane.handed_out(m), 0));
+  return PGP_OK;
+}
+
+// Member 0's passes over the COMPLETE vector {d_s | d_c} of one object, on `st`: the arg-max with the exact near-tie
+// settlement into d_best (seq_ws: the settlement's re-score workspace, null = the context's), then the opt-in passes --
+// pgp_set_exact_records / pgp_set_verify_early_out on member 0's context of the object cover the group's calls.
+int complete_tail(pgp_ctx* c, const float* d_T, int n, int mode, float gate_deg, float* d_s, int* d_c, int* d_best,
+                  hipStream_t st, float* seq_ws) {
+  int r = launch_settle_best(c, d_T, n, mode, gate_deg, d_s, d_best, st, seq_ws);
+  c->device_work_pending = true;   // (work queued outside the context's stream: the next host-pointer call drains the device)
+  if (r != PGP_OK) return r;
+  if (c->exact_records && (r = pgp_settle_records_device(c, d_T, n, mode, gate_deg, d_s, st)) != PGP_OK) return r;
+  if (c->verify_early_out && mode == PGP_MODE_PLAIN && n > 0) return pgp_verify_early_out_device(c, d_T, n, d_s, d_c, st);
+  return PGP_OK;
+}
+
+// the pinned image {scores | counts | best per object} into the caller's arrays (each may be null)
+void image_to_caller(const unsigned char* pin, int N, int n_obj, float* scores, int* counts, int* best_index, float* best_score) {
+  if (N > 0) {
+    if (scores) std::memcpy(scores, pin, (size_t)N * 4);
+    if (counts) std::memcpy(counts, pin + (size_t)N * 4, (size_t)N * 4);
+  }
+  for (int o = 0; o < n_obj; ++o) {
+    int best[2];
+    std::memcpy(best, pin + (size_t)N * 8 + (size_t)o * 8, sizeof best);
+    if (best_index) best_index[o] = best[0];
+    if (best_score) std::memcpy(best_score + o, &best[1], 4);
+  }
+}
+
 // The scoring call over whatever pgp_multi_upload[_objects] left on the devices.  scores / counts: flat, object after
 // object; best_index / best_score: one entry per object.
 int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* counts, int* best_index, float* best_score) {
@@ -321,7 +435,6 @@ int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* count
   int rc = m->h_pin.ensure((size_t)N * 72 + (size_t)n_obj * 8 + 256);   // nothing uploaded yet: an empty batch still returns {-1, 0}
   if (rc != PGP_OK) return rc;
   unsigned char* pin_out = m->h_pin.as<unsigned char>() + (((size_t)N * 64 + 63) & ~(size_t)63);
-  std::vector<int> fail((size_t)m->n, 0);   // emulate: a member that failed to queue its slice (the others still meet it)
   double t_enq = t0;
 
   // every member: its pieces of the flat space into a zeroed full-length vector (the sum over members is the gather)
@@ -334,16 +447,8 @@ int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* count
     for (int o = 0; o < n_obj; ++o) {
       const int a = std::max(lo, m->off[o]), b = std::min(hi, m->off[o + 1]);
       if (b <= a) continue;
-      pgp_ctx* c = m->octx[o][k];
-      // the exact-records pass (pgp_set_exact_records on member 0's context) belongs to the COMPLETE vector, below;
-      // Verify's early termination depends on ALL earlier hypotheses of the object: below as well
-      const bool records = c->exact_records, early = c->verify_early_out;
-      c->exact_records = false;
-      c->verify_early_out = false;
-      const int r = pgp_score_lcp_device(c, m->d_T[k].as<float>() + 16 * (size_t)a, b - a, mode, gate_deg, d_s + a, d_c + a,
-                                         nullptr, m->stream[k]);
-      c->exact_records = records;
-      c->verify_early_out = early;
+      const int r = score_piece(m->octx[o][k], m->d_T[k].as<float>() + 16 * (size_t)a, b - a, mode, gate_deg, d_s + a, d_c + a,
+                                nullptr, m->stream[k]);
       if (r != PGP_OK) return r;
     }
     return PGP_OK;
@@ -354,17 +459,11 @@ int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* count
     int* d_b = m->d_best[0].as<int>();
     hipStream_t st = m->stream[0];
     if (m->rest_pending) PGP_HIP(hipStreamWaitEvent(st, m->ev_rest, 0));   // the transforms outside member 0's slice (upload_flat)
-    for (int o = 0; o < n_obj; ++o) {
-      pgp_ctx* c = m->octx[o][0];
+    for (int o = 0; o < n_obj; ++o) {   // (an empty object gets its {-1, 0})
       const int a = m->off[o], cnt = m->off[o + 1] - a;
-      const float* d_To = m->d_T[0].as<float>() + 16 * (size_t)a;
-      int r = pgp_settle_best_device(c, d_To, cnt, mode, gate_deg, d_s + a, d_b + 2 * o, st);
+      const int r = complete_tail(m->octx[o][0], m->d_T[0].as<float>() + 16 * (size_t)a, cnt, mode, gate_deg, d_s + a,
+                                  reinterpret_cast<int*>(d_s + N) + a, d_b + 2 * o, st, nullptr);
       if (r != PGP_OK) return r;
-      // pgp_set_exact_records / pgp_set_verify_early_out on member 0's context of the object cover the group's calls
-      if (c->exact_records && (r = pgp_settle_records_device(c, d_To, cnt, mode, gate_deg, d_s + a, st)) != PGP_OK) return r;
-      if (c->verify_early_out && mode == PGP_MODE_PLAIN && cnt > 0 &&
-          (r = pgp_verify_early_out_device(c, d_To, cnt, d_s + a, reinterpret_cast<int*>(d_s + N) + a, st)) != PGP_OK)
-        return r;
     }
     t_enq = now_ms();
     // home: by ONE kernel and a completion word while the arrays are small (pgp::publish_and_wait), else two copies and the stream
@@ -377,113 +476,16 @@ int score_flat(pgp_multi* m, int mode, float gate_deg, float* scores, int* count
     PGP_HIP(hipStreamSynchronize(st));
     return PGP_OK;
   };
-  // the exchange on ONE device (PGP_MULTI_EMULATE): member 0's stream waits for every slice, sums the vectors and hands
-  // the sum to every member, whose streams then wait for it
-  auto emulate_exchange = [&](int k, int rc_mine) -> int {
-    if (rc_mine == PGP_OK && hipEventRecord(m->ev[k], m->stream[k]) != hipSuccess) rc_mine = PGP_EHIP;
-    fail[(size_t)k] = rc_mine != PGP_OK;
-    m->barrier();
-    bool any = false;
-    for (int f : fail) any = any || f;
-    int r = PGP_OK;
-    if (k == 0 && !any) {
-      r = [&]() -> int {
-        hipStream_t st = m->stream[0];
-        int q;
-        if ((q = m->d_sum.ensure((size_t)N * 8 + (size_t)m->n * sizeof(float*) + 64)) != PGP_OK) return q;
-        float* d_out = m->d_sum.as<float>();
-        const float** d_ptrs = reinterpret_cast<const float**>(m->d_sum.as<unsigned char>() + (((size_t)N * 8 + 15) & ~(size_t)15));
-        std::vector<const float*> ptrs((size_t)m->n);
-        for (int j = 0; j < m->n; ++j) {
-          ptrs[(size_t)j] = m->d_all[j].as<float>();
-          if (j > 0) PGP_HIP(hipStreamWaitEvent(st, m->ev[j], 0));
-        }
-        PGP_HIP(hipMemcpyAsync(d_ptrs, ptrs.data(), (size_t)m->n * sizeof(float*), hipMemcpyHostToDevice, st));
-        PGP_HIP(hipStreamSynchronize(st));   // ptrs is a stack temporary
-        hipLaunchKernelGGL(emulate_sum, dim3((2 * N + 255) / 256), dim3(256), 0, st, d_ptrs, m->n, N, d_out);
-        PGP_HIP(hipGetLastError());
-        for (int j = 0; j < m->n; ++j)
-          PGP_HIP(hipMemcpyAsync(m->d_all[j].p, d_out, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
-        PGP_HIP(hipEventRecord(m->ev[0], st));
-        return PGP_OK;
-      }();
-      fail[0] = r != PGP_OK;
-    }
-    m->barrier();
-    if (rc_mine != PGP_OK) return rc_mine;
-    if (r != PGP_OK) return r;
-    if (any || fail[0]) {
-      set_error("another member of the group failed");
-      return PGP_EHIP;
-    }
-    if (k > 0) PGP_HIP(hipStreamWaitEvent(m->stream[k], m->ev[0], 0));
-    return PGP_OK;
-  };
-  // ONE all-reduce per call over the 8 N bytes {scores | counts}, summed as 32-bit integers: every element is non-zero
-  // on exactly one member (its owner) and all-zero bits elsewhere, and x + 0 + ... + 0 over the BIT PATTERNS returns
-  // x's pattern -- exact for the float scores too (scores are >= +0: no -0, no NaN).  At 4096 hypotheses the exchange is
-  // latency-bound (32 KB per member), so two collectives cost twice what one does.
-  auto own_allreduce = [&](int k) -> int {
-    float* d_s = m->d_all[k].as<float>();
-    if (m->emulate_ranked) return shm_exchange(m, d_s, N, m->stream[k]);
-    const ncclResult_t nr = m->rccl.AllReduce(d_s, d_s, 2 * (size_t)N, ncclInt32, ncclSum, m->comm[k], m->stream[k]);
-    if (nr != ncclSuccess) {
-      set_error("ncclAllReduce failed: %s", m->rccl.GetErrorString(nr));
-      return PGP_EHIP;
-    }
-    return PGP_OK;
-  };
-
-  const bool exchange = m->exchange();
-  if (exchange && N > 0) ++m->n_exchanges;
-  if (m->emulate && m->n > 1 && N > 0) {
-    rc = run_all(m, [&](int k) -> int {
-      int r = emulate_exchange(k, score_slice(k));
-      if (r == PGP_OK && k == 0) r = tail();
-      return r;
-    });
-  } else if (exchange && m->use_coll && !m->emulate && N > 0 && (!m->grouped || m->emulate_ranked)) {
-    // default: every member's worker thread queues its slice, its own all-reduce call (one communicator per device, the
-    // multi-thread form RCCL documents) and, on member 0, the tail -- ONE rendezvous of the calling thread per call.
-    // A member whose slice failed to queue still joins the collective: the others' streams would wait for it forever.
-    rc = run_all(m, [&](int k) -> int {
-      const int r1 = score_slice(k);
-      const int r2 = own_allreduce(k);
-      if (r1 != PGP_OK) return r1;
-      if (r2 != PGP_OK) return r2;
-      return k == 0 ? tail() : PGP_OK;
-    });
-  } else {
-    // PGP_MULTI_COLL=grouped (and the single-member group without a collective): slices, then the collective for all
-    // members from the calling thread inside one group, then the tail
-    rc = run_all(m, score_slice);
-    if (rc != PGP_OK) return rc;
-    if (m->use_coll && !m->emulate && N > 0) {
-      ncclResult_t nr = m->rccl.GroupStart();
-      for (int k = 0; k < m->n && nr == ncclSuccess; ++k) {
-        float* d_s = m->d_all[k].as<float>();
-        nr = m->rccl.AllReduce(d_s, d_s, 2 * (size_t)N, ncclInt32, ncclSum, m->comm[k], m->stream[k]);
-      }
-      ncclResult_t ge = m->rccl.GroupEnd();
-      if (nr == ncclSuccess) nr = ge;
-      if (nr != ncclSuccess) {
-        set_error("ncclAllReduce failed: %s", m->rccl.GetErrorString(nr));
-        return PGP_EHIP;
-      }
-    }
-    rc = on_caller(m, tail);
-  }
+  // every member: its slice, the exchange when there is one, and on member 0 the tail -- ONE rendezvous of the calling thread
+  const bool exchanging = m->exchange() && N > 0;
+  if (exchanging) ++m->n_exchanges;
+  rc = run_all(m, [&](int k) -> int {
+    int r = score_slice(k);
+    if (exchanging) r = exchange(m, k, Lane{-1}, N, r);
+    return r == PGP_OK && k == 0 ? tail() : r;
+  });
   if (rc != PGP_OK) return rc;
-  if (N > 0) {
-    if (scores) std::memcpy(scores, pin_out, (size_t)N * 4);
-    if (counts) std::memcpy(counts, pin_out + (size_t)N * 4, (size_t)N * 4);
-  }
-  for (int o = 0; o < n_obj; ++o) {
-    int best[2];
-    std::memcpy(best, pin_out + (size_t)N * 8 + (size_t)o * 8, sizeof best);
-    if (best_index) best_index[o] = best[0];
-    if (best_score) std::memcpy(best_score + o, &best[1], 4);
-  }
+  image_to_caller(pin_out, N, n_obj, scores, counts, best_index, best_score);
   m->last_ms[1] = (float)(t_enq - t0);
   m->last_ms[2] = (float)(now_ms() - t0);
   return PGP_OK;
@@ -520,6 +522,7 @@ int upload_flat(pgp_multi* m, const float* const* T, const int* n_h, int n_obj) 
     if ((r = m->d_T[k].ensure(nT)) != PGP_OK) return r;
     if ((r = m->d_all[k].ensure((size_t)N * 8)) != PGP_OK) return r;
     if ((r = m->d_best[k].ensure((size_t)n_obj * 8 + 16)) != PGP_OK) return r;
+    if (k == 0 && m->emulate && (r = m->d_sum.ensure((size_t)N * 8 + 64)) != PGP_OK) return r;
     for (int o = 0; o < n_obj; ++o) {
       // member 0 also works on every object's complete vector (settlement, exact records, Verify's early termination)
       const int a = std::max(lo, m->off[o]), b = std::min(hi, m->off[o + 1]);
@@ -620,6 +623,10 @@ int create_group(pgp_multi** out, const int* device_ids, int n_dev, int rank0, i
     set_error("pgp_multi_create_ranked: PGP_MULTI_EMULATE applies to single-process groups");
     return PGP_EINVAL;
   }
+  if (emulate > kEmulateMax) {
+    set_error("pgp_multi_create: PGP_MULTI_EMULATE=%d, an emulated group has at most %d members", emulate, kEmulateMax);
+    return PGP_EINVAL;
+  }
   if (emulate >= 2) n_dev = emulate;   // n logical members on the first listed device
   if (n_dev <= 0) n_dev = visible;  // every visible device
   if (ranked && (world < n_dev || rank0 + n_dev > world || !id)) {
@@ -673,7 +680,6 @@ int create_group(pgp_multi** out, const int* device_ids, int n_dev, int rank0, i
   });
   const char* force = getenv("PGP_MULTI_FORCE_COLLECTIVE");
   m->use_coll = m->world > 1 || (force && atoi(force) != 0);
-  if (const char* v = getenv("PGP_MULTI_COLL")) m->grouped = std::strcmp(v, "grouped") == 0;
   if (rc == PGP_OK && m->emulate) {
     m->ev.assign(n_dev, nullptr);
     rc = run_all(m, [m](int k) -> int {
@@ -1048,18 +1054,6 @@ int pgp_multi_score_objects(pgp_multi* m, const float* const* T, const int* n_h,
 
 // ---- streaming form: resident batches, steps queued without a host wait, the exchange under the next step's scoring ----
 namespace {
-struct SumPtrs {
-  const float* p[kEmulateMax];
-};
-// emulate_sum with the members' vectors passed by value (nothing to upload, nothing to wait for on the host)
-__global__ __launch_bounds__(256) void emulate_sum_args(SumPtrs in, int n_members, int n_h, float* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 2 * n_h) return;
-  int s = 0;
-  for (int k = 0; k < n_members; ++k) s += reinterpret_cast<const int*>(in.p[k])[i];
-  reinterpret_cast<int*>(out)[i] = s;
-}
-
 int streaming_ready(pgp_multi* m, int k) {
   Streaming& z = m->s2[(size_t)k];
   if (z.x) return PGP_OK;
@@ -1076,28 +1070,16 @@ int streaming_ready(pgp_multi* m, int k) {
   return PGP_OK;
 }
 
-// member 0, on its EXCHANGE stream behind the all-reduce of ring[b]: the arg-max over the complete vector with the near-tie
-// settlement (and the opt-in passes over the complete vector), exactly score_flat's tail -- beside the next step's scoring on the
-// member's other stream (a settle over 32 768 scores is ~15 us: an eighth of a step that the scoring stream does not wait for).
-// The settlement's re-score workspace is the tail's own (finalize_scores on the scoring stream uses the context's); the opt-in
-// passes' workspaces are not touched by the slices' scoring (score_slice switches those passes off).
+// member 0, on its EXCHANGE stream behind the all-reduce of ring[b]: score_flat's tail (complete_tail) -- beside the next
+// step's scoring on the member's other stream (a settle over 32 768 scores is ~15 us: an eighth of a step that the scoring
+// stream does not wait for).  The settlement's re-score workspace is the tail's own (finalize_scores on the scoring stream
+// uses the context's); the opt-in passes' workspaces are not touched by the slices' scoring (score_piece switches them off).
 int queue_tail(pgp_multi* m, int b) {
-  Streaming& z = m->s2[0];
-  hipStream_t st = z.x;
-  const int N = m->pend_n[b], mode = m->pend_mode[b];
-  const float gate = m->pend_gate[b];
+  const int N = m->pend_n[b];
   if (N <= 0) return PGP_OK;   // (the empty batch: its {-1, 0} was published by the scoring call)
-  pgp_ctx* c = m->octx[0][0];
-  float* d_s = z.ring[b].as<float>();
-  const float* d_T = m->slot_T[(size_t)m->pend_slot[b]][0].as<float>();
-  int r = launch_settle_best(c, d_T, N, mode, gate, d_s, m->d_best2.as<int>() + 2 * b, st, m->d_tail_seq.as<float>());
-  c->device_work_pending = true;   // (what pgp_settle_best_device's guard notes: work queued outside the context's stream)
-  if (r != PGP_OK) return r;
-  if (c->exact_records && (r = pgp_settle_records_device(c, d_T, N, mode, gate, d_s, st)) != PGP_OK) return r;
-  if (c->verify_early_out && mode == PGP_MODE_PLAIN &&
-      (r = pgp_verify_early_out_device(c, d_T, N, d_s, reinterpret_cast<int*>(d_s + N), st)) != PGP_OK)
-    return r;
-  return PGP_OK;
+  float* d_s = m->s2[0].ring[b].as<float>();
+  return complete_tail(m->octx[0][0], m->slot_T[(size_t)m->pend_slot[b]][0].as<float>(), N, m->pend_mode[b], m->pend_gate[b], d_s,
+                       reinterpret_cast<int*>(d_s + N), m->d_best2.as<int>() + 2 * b, m->s2[0].x, m->d_tail_seq.as<float>());
 }
 }  // namespace
 
@@ -1109,10 +1091,6 @@ int pgp_multi_upload_slot(pgp_multi* m, int slot, const float* T, int n_h) {
   if (m->step != 0) {
     set_error("pgp_multi_upload_slot: %lld steps are in flight (pgp_multi_collect first)", m->step);
     return PGP_ESTATE;
-  }
-  if (m->emulate && m->n > kEmulateMax) {
-    set_error("pgp_multi_upload_slot: the streaming form emulates at most %d members", kEmulateMax);
-    return PGP_EINVAL;
   }
   const int N = n_h;
   const size_t nT = (size_t)N * 64;
@@ -1150,13 +1128,12 @@ int pgp_multi_enqueue_slot(pgp_multi* m, int slot, int mode, float gate_deg) {
   }
   const int N = m->slot_n[(size_t)slot];
   const int b = (int)(m->step & 1);
-  const bool exchange = m->exchange() && N > 0;
-  std::vector<int> fail((size_t)m->n, 0);
+  const bool exchanging = m->exchange() && N > 0;
   m->pend_slot[b] = slot;
   m->pend_mode[b] = mode;
   m->pend_gate[b] = gate_deg;
   m->pend_n[b] = N;
-  if (exchange) ++m->n_exchanges;
+  if (exchanging) ++m->n_exchanges;
   const long long step = m->step;
   const int rc = run_all(m, [&, m](int k) -> int {
     Streaming& z = m->s2[(size_t)k];
@@ -1174,64 +1151,15 @@ int pgp_multi_enqueue_slot(pgp_multi* m, int slot, int mode, float gate_deg) {
       // ring[b] was last used two steps ago: its exchange (and, on member 0, its tail behind it) must be through
       if (step >= 2) PGP_HIP(hipStreamWaitEvent(S, z.reduced[b], 0));
       if (N > 0 && m->world > 1) PGP_HIP(hipMemsetAsync(d_s, 0, (size_t)N * 8, S));
-      const bool records = c->exact_records, early = c->verify_early_out;
-      c->exact_records = false;   // they belong to the complete vector (queue_tail)
-      c->verify_early_out = false;
-      const int r = hi > lo || N == 0
-                        ? pgp_score_lcp_device(c, m->slot_T[(size_t)slot][(size_t)k].as<float>() + 16 * (size_t)lo, hi - lo, mode,
-                                               gate_deg, d_s + lo, d_c + lo, N == 0 && k == 0 ? m->d_best2.as<int>() + 2 * b : nullptr, S)
-                        : PGP_OK;
-      c->exact_records = records;
-      c->verify_early_out = early;
-      return r;
+      if (hi <= lo && N > 0) return PGP_OK;   // (more members than hypotheses: none of them is this member's)
+      // (the empty batch: the call with no hypotheses publishes member 0's {-1, 0})
+      return score_piece(c, m->slot_T[(size_t)slot][(size_t)k].as<float>() + 16 * (size_t)lo, hi - lo, mode, gate_deg, d_s + lo,
+                         d_c + lo, N == 0 && k == 0 ? m->d_best2.as<int>() + 2 * b : nullptr, S);
     }();
-    if (!exchange) return r1;   // (one member without a collective, or the empty batch: nothing to exchange, nothing to settle)
+    if (!exchanging) return r1;   // (one member without a collective, or the empty batch: nothing to exchange, nothing to settle)
     // ---- the exchange of ring[b] on the second stream ----
-    if (r1 == PGP_OK && hipEventRecord(z.scored[b], S) != hipSuccess) r1 = PGP_EHIP;
-    if (r1 == PGP_OK && hipStreamWaitEvent(X, z.scored[b], 0) != hipSuccess) r1 = PGP_EHIP;
-    int r2 = PGP_OK;
-    if (m->emulate) {
-      fail[(size_t)k] = r1 != PGP_OK;
-      m->barrier();   // every member's slice is queued (or has failed)
-      bool any = false;
-      for (int f : fail) any = any || f;
-      if (k == 0 && !any) {
-        r2 = [&]() -> int {
-          SumPtrs ptrs{};
-          for (int j = 0; j < m->n; ++j) {
-            ptrs.p[j] = m->s2[(size_t)j].ring[b].as<float>();
-            if (j > 0) PGP_HIP(hipStreamWaitEvent(X, m->s2[(size_t)j].scored[b], 0));
-          }
-          float* d_out = m->d_sum.as<float>();
-          hipLaunchKernelGGL(emulate_sum_args, dim3((2 * N + 255) / 256), dim3(256), 0, X, ptrs, m->n, N, d_out);
-          PGP_HIP(hipGetLastError());
-          for (int j = 0; j < m->n; ++j)
-            PGP_HIP(hipMemcpyAsync(m->s2[(size_t)j].ring[b].p, d_out, (size_t)N * 8, hipMemcpyDeviceToDevice, X));
-          PGP_HIP(hipEventRecord(m->ev_sum[b], X));
-          return PGP_OK;
-        }();
-        fail[0] = r2 != PGP_OK;
-      }
-      m->barrier();   // the sum is queued
-      if (r1 == PGP_OK && r2 == PGP_OK && (any || fail[0])) {
-        set_error("another member of the group failed");
-        r2 = PGP_EHIP;
-      }
-      if (r1 == PGP_OK && r2 == PGP_OK && k > 0) PGP_HIP(hipStreamWaitEvent(X, m->ev_sum[b], 0));
-    } else {
-      // (a member whose slice failed to queue still joins the collective: the others' streams would wait for it forever)
-      if (m->emulate_ranked) {
-        r2 = shm_exchange(m, d_s, N, X);   // (host-synchronous: X has waited for the slice)
-      } else {
-        const ncclResult_t nr = m->rccl.AllReduce(d_s, d_s, 2 * (size_t)N, ncclInt32, ncclSum, m->comm[(size_t)k], X);
-        if (nr != ncclSuccess) {
-          set_error("ncclAllReduce failed: %s", m->rccl.GetErrorString(nr));
-          r2 = PGP_EHIP;
-        }
-      }
-    }
+    r1 = exchange(m, k, Lane{b}, N, r1);
     if (r1 != PGP_OK) return r1;
-    if (r2 != PGP_OK) return r2;
     // member 0: the step's tail behind its exchange, on the exchange stream -- beside the next step's scoring
     if (k == 0) {
       if (m->d_tail_seq.cap < c->d_seq.cap) {   // (the model changed since the batches went up)
@@ -1277,14 +1205,7 @@ int pgp_multi_collect(pgp_multi* m, float* scores, int* counts, int* best_index,
   });
   m->step = 0;
   if (rc != PGP_OK) return rc;
-  if (N > 0) {
-    if (scores) std::memcpy(scores, pin_out, (size_t)N * 4);
-    if (counts) std::memcpy(counts, pin_out + (size_t)N * 4, (size_t)N * 4);
-  }
-  int best[2];
-  std::memcpy(best, pin_out + (size_t)N * 8, sizeof best);
-  if (best_index) *best_index = best[0];
-  if (best_score) std::memcpy(best_score, &best[1], 4);
+  image_to_caller(pin_out, N, 1, scores, counts, best_index, best_score);
   return PGP_OK;
 }
 
