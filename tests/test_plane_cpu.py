@@ -4,7 +4,7 @@ import math
 
 import numpy as np
 
-from test_plane_gpu import plane_coeffs, draw_triples, stop_rule, score
+from _plane_restate import plane_coeffs, draw_triples, stop_rule, score
 
 EPS = np.finfo(float).eps
 
