@@ -1002,7 +1002,8 @@ int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, c
  * rendered depth images against one observed image (all rows x cols float, row-major, metres):
  * render_score[i] = obScore + renScore - intScore with the pixel tests of the reference and
  * threshold = explanationThreshold (0.01 there, UCTState.cpp:8).  counts (nullable) receives the
- * three integer tallies per image.  Host pointers, synchronous. */
+ * three integer tallies per image.  Host pointers, synchronous.  At most 65535 images per call (this
+ * form and the device form): more is PGP_EINVAL, nothing is launched. */
 int pgp_depth_cost(pgp_ctx* ctx, const float* observed, const float* rendered, int n, int rows, int cols,
                    float threshold, float* render_score, int* counts);
 
@@ -1022,13 +1023,16 @@ int pgp_depth_cost_device(pgp_ctx* ctx, const float* d_observed, const float* d_
  *   T: n x 16 column-major float, object -> camera frame (convertToWorld/convertToCamera done by the caller)
  *   parent (nullable): parent_stride == 0: ONE rows x cols image under all n; else image i at parent + i * parent_stride
  *   depth: n x rows x cols floats, metres, 0 = no surface
- * The rasterisation rules (pixel centres, inclusive edges, perspective-correct depth, atomic-min z-buffer)
- * are stated in csrc/render.hip; OpenGL's are implementation-defined, so parity with the reference's
- * renderer is unpinned and tests/_checkers.py restates the rules in numpy float32, bit for bit. */
+ *   n: at most 65535 images per call, vertex_stride 3 or 4, rows * cols at most 2^28: else PGP_EINVAL
+ * The rasterisation rules (pixel centres, inclusive edges, perspective-correct depth, near-plane clipping,
+ * atomic-min z-buffer) are stated in csrc/render.hip; OpenGL's are implementation-defined, so parity with
+ * the reference's renderer is unpinned.  oracle/render_oracle.py restates the rules in numpy float32, bit
+ * for bit, and tests/_render_raycast.py checks that restatement against a float64 ray caster. */
 typedef struct {
   int rows, cols;
   float fx, fy, cx, cy;
-  float z_near;   /* points / triangles with a vertex at z <= z_near are dropped (<= 0: 0) */
+  float z_near;   /* points at z <= z_near are dropped (<= 0: 0); a triangle with one or two vertices there is
+                     CLIPPED against z = z_near (1e-4 when z_near is 0), with all three it is dropped */
   float z_max;    /* fragments with z > z_max are dropped (<= 0: no limit); the reference uses 1.0 */
 } pgp_camera;
 int pgp_render_depth_device(pgp_ctx* ctx, const float* d_vertices, int vertex_stride, int n_vert, const int* d_triangles,

@@ -72,6 +72,10 @@ int launch_depth_cost(pgp_ctx* ctx, const float* d_obs, const float* d_ren, int 
                       int* d_counts, hipStream_t stream) {
   (void)ctx;
   if (n <= 0) return PGP_OK;
+  if (n > 65535) {   // the image index is gridDim.y
+    set_error("depth cost: at most 65535 images per call (%d)", n);
+    return PGP_EINVAL;
+  }
   PGP_HIP(hipMemsetAsync(d_counts, 0, (size_t)n * 3 * sizeof(int), stream));
   if (n_pix <= 0) return PGP_OK;
   int bx = (n_pix / 4 + 255) / 256;

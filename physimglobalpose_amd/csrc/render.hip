@@ -10,7 +10,7 @@
 //
 // OpenGL's rasteriser is not specified to the bit (fill rule on shared edges, depth-buffer quantisation,
 // driver), so there is nothing to be bit-identical WITH; this file states its own rules and
-// tests/_checkers.py restates them in numpy float32, operation for operation:
+// oracle/render_oracle.py restates them in numpy float32, operation for operation:
 //   camera point   c = R v + t           rows as ((r0 x + r1 y) + r2 z) + t, float
 //   pixel          px = (fx c.x) / c.z + cx,  py = (fy c.y) / c.z + cy;  dropped unless c.z > z_near
 //   splat (no triangles): the pixel (rint(px), rint(py)) takes min(depth, c.z)
@@ -118,7 +118,7 @@ struct TriBox {
 };
 __device__ __forceinline__ bool tri_box(const RenderArgs& a, const float4 v0, const float4 v1, const float4 v2, TriBox* b) {
   b->area = edge_fn(v0.x, v0.y, v1.x, v1.y, v2.x, v2.y);
-  if (!(b->area != 0.f)) return false;   // degenerate (or NaN)
+  if (!(b->area > 0.f || b->area < 0.f)) return false;   // degenerate (or NaN: no fragment of it would pass tri_pixel)
   b->sgn = b->area > 0.f ? 1.f : -1.f;
   // pixel centres (i + 0.5) inside [min, max]:  i >= min - 0.5, i <= max - 0.5
   const float minx = fminf(v0.x, fminf(v1.x, v2.x)), maxx = fmaxf(v0.x, fmaxf(v1.x, v2.x));
