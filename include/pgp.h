@@ -998,6 +998,90 @@ int pgp_mask_plane_depth_device(pgp_ctx* ctx, void* d_image, int raw16, int rows
 int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, const float K[9], float leaf,
                      const pgp_plane_options* opt, float coeff[4], int* n_masked);
 
+/* ---- Object proposals: connected components of a depth image (csrc/components.hip) ----
+ * What stands on the table once pgp_remove_table has zeroed it: Euclidean clustering on the organised image, i.e.
+ * connected-component labelling with a 3-D distance test between neighbouring pixels (PCL's
+ * OrganizedConnectedComponentSegmentation + EuclideanClusterComparator).  The reference has no such step -- its masks
+ * come from a CNN or a ground-truth file (Segmentation.cpp) -- so nothing of its bits is pinned; the rules, all of them:
+ *   validity   pixel (u, v) is valid iff (mask == NULL or mask[u, v] != 0) and z_min < depth < z_max (both strict, NaN
+ *              invalid): pgp_backproject_depth's rule, decode (raw16) and point: x = (v - cx) * depth / fx,
+ *              y = (u - cy) * depth / fy, z = depth, float operations in that order.
+ *   edges      connectivity 4: the right and the down neighbour; 8: both diagonals as well.  Two neighbouring valid
+ *              pixels are connected iff ((dx dx + dy dy) + dz dz) <= tolerance * tolerance, every product and sum
+ *              rounded to float on its own, the comparison inclusive.
+ *   labels     roots[u cols + v] = the smallest row-major pixel index of the pixel's component, -1 for an invalid
+ *              pixel: independent of scheduling.
+ *   table      per component: pixel count, inclusive bounding box (rows u, columns v), depth range, and per coordinate
+ *              the sum over its pixels of llrint((double)coord * 1e6) -- integers, so the same bits on every run;
+ *              centroid = sum_um / pixels / 1e6.  (-0 counts as below +0 in the depth range.)
+ *   selection  kept iff pixels >= min_pixels and (max_pixels <= 0 or pixels <= max_pixels); the kept ones ranked by
+ *              descending pixels, ties by ascending root; the first min(kept, cap) get ids 1, 2, ... and info rows
+ *              0, 1, ... in that order (further rows of info are not written).  ids[u cols + v] = the id of the
+ *              pixel's component, 0 for invalid pixels, unkept components and kept ones beyond cap.
+ *   counts     [0] kept components (the full number, it may exceed cap), [1] components of any size, [2] valid pixels.
+ * Touching objects are one component: that is the method's limit, not an error.
+ * tolerance <= 0 or not finite, a connectivity other than 4 or 8, min_pixels < 1, cap < 0, cap > 0 without info,
+ * rows * cols > 2^30 and outputs that overlap the inputs or each other are PGP_EINVAL; rows == 0 or cols == 0 is PGP_OK
+ * with zero counts. */
+typedef struct pgp_components_options {
+  double z_min, z_max;   /* 0.1, 2.0 */
+  float  tolerance;      /* 0.01 m */
+  int    connectivity;   /* 4 (default) or 8 */
+  int    min_pixels;     /* 500: ours, the reference has no such step */
+  int    max_pixels;     /* 0 = no upper bound */
+} pgp_components_options;
+int pgp_components_default_options(pgp_components_options* opt);
+
+typedef struct pgp_component_info {
+  int root;            /* canonical label: smallest row-major pixel index */
+  int pixels;
+  int u_min, u_max, v_min, v_max;      /* bounding box, rows u, columns v, inclusive */
+  float z_min, z_max;                  /* depth range */
+  long long sum_um[3];                 /* sum over the pixels of llrint((double)coord * 1e6), coord = x, y, z:
+                                          centroid = sum_um / pixels / 1e6, the same bits on every run */
+} pgp_component_info;
+
+/* image: rows x cols, float metres (raw16 == 0) or the raw 16-bit encoding (raw16 != 0); mask (nullable): rows x cols
+ * bytes; K: 3x3 row-major; roots, ids (nullable): rows x cols ints; info (nullable when cap == 0): cap rows; counts[3].
+ * Host pointers, synchronous. */
+int pgp_depth_components(pgp_ctx* ctx, const pgp_components_options* opt, const void* image, int raw16,
+                         const unsigned char* mask, int rows, int cols, const float K[9], int* roots, int* ids,
+                         pgp_component_info* info, int cap, int counts[3]);
+/* The same on DEVICE arrays, results in device memory (d_counts: 3 ints).  Enqueued on `stream` with no host
+ * synchronisation and sized by bounds (rows * cols), not by counts read home, so it chains behind
+ * pgp_mask_plane_depth_device; the workspace lives in the context and grows on demand. */
+int pgp_depth_components_device(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_image, int raw16,
+                                const unsigned char* d_mask, int rows, int cols, const float K[9], int* d_roots,
+                                int* d_ids, pgp_component_info* d_info, int cap, int* d_counts, void* stream);
+
+/* mask[u, v] = (ids[u, v] == id) as 1 / 0: the byte mask pgp_segment_from_depth_device and
+ * pgp_backproject_depth_device read.  Host pointers, synchronous; the _device form is enqueued and not synchronised. */
+int pgp_component_mask(pgp_ctx* ctx, const int* ids, int rows, int cols, int id, unsigned char* mask);
+int pgp_component_mask_device(pgp_ctx* ctx, const int* d_ids, int rows, int cols, int id, unsigned char* d_mask,
+                              void* stream);
+
+/* Which component does each object's 2-D mask fall into, and which objects can share a search tree
+ * (MCTSSelection::selectBestPoses builds `independentTrees` and then puts every object into one,
+ * HypothesisSelection.cpp:242-247): objects whose pixels lie in different components cannot touch.
+ * classes: the reference's class image (GTSegmentation, Segmentation.cpp:187-206; FCNSegmentation, :118-129), rows x cols
+ * of class_bytes = 1 (uchar) or 2 (ushort) bytes; object o is the pixels with classes == class_values[o]; ids: what
+ * pgp_depth_components wrote, values in [0, min(rows * cols, 65535)] (an id names a component of at least one pixel;
+ * anything else is PGP_EINVAL).  Per object:
+ *   pixels_total[o]  pixels of its class with ids != 0
+ *   component[o]     the id that holds most of them, the lower id on ties; 0 when pixels_total[o] == 0
+ *   pixels_in[o]     that count
+ *   group[o]         objects with the same non-zero component share a group, an object with component 0 is a group of
+ *                    its own; groups are numbered from 0 in the order of their first object.
+ * The votes are an n_objects x (ids' bound + 1) integer histogram filled with integer atomics.  n_objects outside 1..64
+ * and class_bytes other than 1 or 2 are PGP_EINVAL; an empty image gives all-zero counts and one group per object.  Host
+ * pointers, synchronous; the _device form takes device images, writes HOST result arrays and synchronises `stream` once. */
+int pgp_assign_masks_to_components(pgp_ctx* ctx, const int* ids, const void* classes, int class_bytes, int rows, int cols,
+                                   const int* class_values, int n_objects, int* component, int* pixels_in,
+                                   int* pixels_total, int* group);
+int pgp_assign_masks_to_components_device(pgp_ctx* ctx, const int* d_ids, const void* d_classes, int class_bytes, int rows,
+                                          int cols, const int* class_values, int n_objects, int* component,
+                                          int* pixels_in, int* pixels_total, int* group, void* stream);
+
 /* Replaces UCTState::computeCost (PPE/hypothesis_verification/mcts/UCTState.cpp:93-116) for n
  * rendered depth images against one observed image (all rows x cols float, row-major, metres):
  * render_score[i] = obScore + renScore - intScore with the pixel tests of the reference and

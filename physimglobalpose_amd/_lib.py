@@ -81,6 +81,16 @@ class PlaneInfo(C.Structure):
                 ("sampled", C.c_float * 4)]
 
 
+class ComponentsOptions(C.Structure):
+    _fields_ = [("z_min", C.c_double), ("z_max", C.c_double), ("tolerance", C.c_float), ("connectivity", C.c_int),
+                ("min_pixels", C.c_int), ("max_pixels", C.c_int)]
+
+
+class ComponentInfo(C.Structure):
+    _fields_ = [("root", C.c_int), ("pixels", C.c_int), ("u_min", C.c_int), ("u_max", C.c_int), ("v_min", C.c_int),
+                ("v_max", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float), ("sum_um", C.c_longlong * 3)]
+
+
 class PpfOptions(C.Structure):
     _fields_ = [("ref_step", C.c_int), ("n_bins", C.c_int), ("peaks_per_ref", C.c_int), ("min_vote_fraction", C.c_float),
                 ("min_votes", C.c_int)]
@@ -306,6 +316,18 @@ SIGNATURES = {
                                               C.c_void_p, C.c_void_p]),
     "pgp_remove_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _f, C.c_float,
                                    C.POINTER(PlaneOptions), _f, _i]),
+    "pgp_components_default_options": (C.c_int, [C.POINTER(ComponentsOptions)]),
+    "pgp_depth_components": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_int, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i]),
+    "pgp_depth_components_device": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_int, C.c_int, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    "pgp_component_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "pgp_component_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pgp_assign_masks_to_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _i, C.c_int,
+                                                 _i, _i, _i, _i]),
+    "pgp_assign_masks_to_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _i,
+                                                        C.c_int, _i, _i, _i, _i, C.c_void_p]),
     "pgp_ppf_default_options": (C.c_int, [C.POINTER(PpfOptions)]),
     "pgp_set_ppf_model": (C.c_int, [C.c_void_p, _f, _f, C.c_int]),
     "pgp_ppf_vote_device": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -14,26 +14,13 @@
 // HBM-bound streaming: 2 or 4 B of depth (+1 B of mask) per pixel in, 12 B per kept pixel out.
 
 #include "pgp_internal.h"
+#include "depth_pixel.h"
 
 namespace pgp {
 
 namespace {
 
 constexpr int kBpThreads = 256;
-
-template <bool RAW16>
-__device__ __forceinline__ float depth_at(const void* img, size_t i) {
-  if (RAW16) {
-    unsigned short s = static_cast<const unsigned short*>(img)[i];
-    s = (unsigned short)((s << 13) | (s >> 3));  // utilities.cpp:57 (APC encoding)
-    return __fdiv_rn((float)s, 10000.0f);        // :59 (float)depthShort/10000
-  }
-  return static_cast<const float*>(img)[i];
-}
-
-__device__ __forceinline__ bool depth_ok(float d, double z_min, double z_max) {
-  return (double)d > z_min && (double)d < z_max;  // utilities.cpp:197 / :218
-}
 
 // pass 1: kept pixels per workgroup; pass 2 (WRITE): ranked write behind the scanned offsets
 template <bool RAW16, bool WRITE>
@@ -66,9 +53,10 @@ __global__ __launch_bounds__(kBpThreads) void backproject(const void* __restrict
   for (int w = 0; w < wave; ++w) rank += s_wave[w];
   if (rank >= cap) return;
   const int u = (int)(i / (size_t)cols), v = (int)(i - (size_t)u * cols);
-  xyz[3 * (size_t)rank] = __fdiv_rn(__fmul_rn(__fsub_rn((float)v, cx), d), fx);
-  xyz[3 * (size_t)rank + 1] = __fdiv_rn(__fmul_rn(__fsub_rn((float)u, cy), d), fy);
-  xyz[3 * (size_t)rank + 2] = d;
+  const float3 p = depth_point(u, v, d, fx, fy, cx, cy);   // depth_pixel.h
+  xyz[3 * (size_t)rank] = p.x;
+  xyz[3 * (size_t)rank + 1] = p.y;
+  xyz[3 * (size_t)rank + 2] = p.z;
 }
 
 }  // namespace

@@ -261,7 +261,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_cc_ws, &ctx->d_cc_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
                     &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io, &ctx->d_Prgb, &ctx->d_Qs_nrm, &ctx->d_Qs_rgb,
                     &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io,
@@ -3061,6 +3061,248 @@ int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, c
   if (coeff) std::memcpy(coeff, h_c, 16);
   if (n_masked) *n_masked = h_cnt[1];
   return PGP_OK;
+}
+
+}  // extern "C"
+
+// ---- object proposals: connected components of a depth image (components.hip) ---------------------------------------
+namespace {
+bool components_args_ok(const pgp_ctx* ctx, const pgp_components_options* opt, const void* image, const unsigned char* mask,
+                        int raw16, int rows, int cols, const float* K, const int* roots, const int* ids,
+                        const pgp_component_info* info, int cap, const int* counts, const char* who) {
+  if (!ctx || !opt || rows < 0 || cols < 0 || !K || !counts || cap < 0 || (cap > 0 && !info) ||
+      ((size_t)rows * cols > 0 && !image) || (size_t)rows * cols > ((size_t)1 << 30)) {
+    set_error("%s: bad argument (cap >= 0, info with cap > 0, rows * cols <= 2^30)", who);
+    return false;
+  }
+  if (!(opt->tolerance > 0.f) || !std::isfinite(opt->tolerance) || (opt->connectivity != 4 && opt->connectivity != 8) ||
+      opt->min_pixels < 1) {
+    set_error("%s: bad options (tolerance > 0 and finite, connectivity 4 or 8, min_pixels >= 1)", who);
+    return false;
+  }
+  const size_t n = (size_t)rows * cols;
+  const void* in[2] = {image, mask};
+  const size_t in_bytes[2] = {n * (raw16 ? 2 : 4), n};
+  const void* out[4] = {roots, ids, info, counts};
+  const size_t out_bytes[4] = {n * 4, n * 4, (size_t)cap * sizeof(pgp_component_info), 12};
+  bool clash = false;
+  for (int o = 0; o < 4; ++o) {
+    for (int i = 0; i < 2; ++i) clash = clash || ranges_overlap(in[i], in_bytes[i], out[o], out_bytes[o]);
+    for (int p = o + 1; p < 4; ++p) clash = clash || ranges_overlap(out[o], out_bytes[o], out[p], out_bytes[p]);
+  }
+  if (clash) {
+    set_error("%s: the outputs overlap the inputs or each other", who);
+    return false;
+  }
+  return true;
+}
+
+bool assign_args_ok(const pgp_ctx* ctx, const int* ids, const void* classes, int class_bytes, int rows, int cols,
+                    const int* class_values, int n_objects, const int* component, const int* pixels_in,
+                    const int* pixels_total, const int* group, const char* who) {
+  if (!ctx || rows < 0 || cols < 0 || (size_t)rows * cols > ((size_t)1 << 30) || (class_bytes != 1 && class_bytes != 2) ||
+      n_objects < 1 || n_objects > kAssignMaxObjects || !class_values || !component || !pixels_in || !pixels_total || !group ||
+      ((size_t)rows * cols > 0 && (!ids || !classes))) {
+    set_error("%s: bad argument (class_bytes 1 or 2, 1 <= n_objects <= %d, rows * cols <= 2^30)", who, kAssignMaxObjects);
+    return false;
+  }
+  const size_t n = (size_t)rows * cols, row = (size_t)n_objects * 4;
+  const void* in[3] = {ids, classes, class_values};
+  const size_t in_bytes[3] = {n * 4, n * (size_t)class_bytes, row};
+  const void* out[4] = {component, pixels_in, pixels_total, group};
+  bool clash = false;
+  for (int o = 0; o < 4; ++o) {
+    for (int i = 0; i < 3; ++i) clash = clash || ranges_overlap(in[i], in_bytes[i], out[o], row);
+    for (int p = o + 1; p < 4; ++p) clash = clash || ranges_overlap(out[o], row, out[p], row);
+  }
+  if (clash) {
+    set_error("%s: the outputs overlap the inputs or each other", who);
+    return false;
+  }
+  return true;
+}
+
+// component 0 is a group of its own; equal non-zero components share one; numbered in the order of their first object
+void groups_of(const int* component, int n_objects, int* group) {
+  int next = 0;
+  for (int o = 0; o < n_objects; ++o) {
+    int g = -1;
+    for (int p = 0; p < o && g < 0; ++p)
+      if (component[o] != 0 && component[p] == component[o]) g = group[p];
+    group[o] = g >= 0 ? g : next++;
+  }
+}
+
+int assign_finish(const int* h_result, int n_objects, int* component, int* pixels_in, int* pixels_total, int* group,
+                  const char* who) {
+  if (h_result[3 * n_objects] != 0) {
+    set_error("%s: an id outside [0, min(rows * cols, %d)]", who, kAssignMaxId);
+    return PGP_EINVAL;
+  }
+  for (int o = 0; o < n_objects; ++o) {
+    component[o] = h_result[3 * o];
+    pixels_in[o] = h_result[3 * o + 1];
+    pixels_total[o] = h_result[3 * o + 2];
+  }
+  groups_of(component, n_objects, group);
+  return PGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pgp_components_default_options(pgp_components_options* opt) {
+  if (!opt) {
+    set_error("pgp_components_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->z_min = 0.1;
+  opt->z_max = 2.0;
+  opt->tolerance = 0.01f;
+  opt->connectivity = 4;
+  opt->min_pixels = 500;
+  opt->max_pixels = 0;
+  return PGP_OK;
+}
+
+int pgp_depth_components_device(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_image, int raw16,
+                                const unsigned char* d_mask, int rows, int cols, const float K[9], int* d_roots, int* d_ids,
+                                pgp_component_info* d_info, int cap, int* d_counts, void* stream) {
+  if (!components_args_ok(ctx, opt, d_image, d_mask, raw16, rows, cols, K, d_roots, d_ids, d_info, cap, d_counts,
+                          "pgp_depth_components_device"))
+    return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_depth_components(ctx, opt, d_image, raw16 != 0, d_mask, rows, cols, K, d_roots, d_ids, d_info, cap,
+                                         d_counts, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_depth_components(pgp_ctx* ctx, const pgp_components_options* opt, const void* image, int raw16,
+                         const unsigned char* mask, int rows, int cols, const float K[9], int* roots, int* ids,
+                         pgp_component_info* info, int cap, int counts[3]) {
+  if (!components_args_ok(ctx, opt, image, mask, raw16, rows, cols, K, roots, ids, info, cap, counts, "pgp_depth_components"))
+    return PGP_EINVAL;
+  counts[0] = counts[1] = counts[2] = 0;
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t rows_cap = std::min((size_t)cap, n / (size_t)opt->min_pixels);   // info rows the device can write
+  Carve cv;
+  const auto c_img = cv.add<unsigned char>(n * (raw16 ? 2 : 4), 256), c_mask = cv.add<unsigned char>(mask ? n : 0, 256);
+  const auto c_roots = cv.add<int>(roots ? n : 0, 256), c_ids = cv.add<int>(ids ? n : 0, 256);
+  const auto c_info = cv.add<pgp_component_info>(rows_cap, 256);
+  const auto c_counts = cv.add<int>(3, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(cv.at(c_img), image, c_img.bytes(), hipMemcpyHostToDevice, st));
+  if (mask) PGP_HIP(hipMemcpyAsync(cv.at(c_mask), mask, n, hipMemcpyHostToDevice, st));
+  if ((rc = launch_depth_components(ctx, opt, cv.at(c_img), raw16 != 0, mask ? cv.at(c_mask) : nullptr, rows, cols, K,
+                                    roots ? cv.at(c_roots) : nullptr, ids ? cv.at(c_ids) : nullptr,
+                                    rows_cap ? cv.at(c_info) : nullptr, (int)rows_cap, cv.at(c_counts), st)) != PGP_OK)
+    return rc;
+  int h_counts[3] = {0, 0, 0};
+  if (roots) PGP_HIP(hipMemcpyAsync(roots, cv.at(c_roots), n * 4, hipMemcpyDeviceToHost, st));
+  if (ids) PGP_HIP(hipMemcpyAsync(ids, cv.at(c_ids), n * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(h_counts, cv.at(c_counts), 12, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  const size_t written = std::min((size_t)h_counts[0], rows_cap);   // rows beyond the kept count stay as the caller left them
+  if (written) {
+    PGP_HIP(hipMemcpyAsync(info, cv.at(c_info), written * sizeof(pgp_component_info), hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipStreamSynchronize(st));
+  }
+  std::memcpy(counts, h_counts, 12);
+  return PGP_OK;
+}
+
+int pgp_component_mask_device(pgp_ctx* ctx, const int* d_ids, int rows, int cols, int id, unsigned char* d_mask, void* stream) {
+  const size_t n = rows >= 0 && cols >= 0 ? (size_t)rows * cols : 0;
+  if (!ctx || rows < 0 || cols < 0 || n > ((size_t)1 << 30) || (n > 0 && (!d_ids || !d_mask)) ||
+      ranges_overlap(d_ids, n * 4, d_mask, n)) {
+    set_error("pgp_component_mask_device: bad argument");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_component_mask(d_ids, n, id, d_mask, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_component_mask(pgp_ctx* ctx, const int* ids, int rows, int cols, int id, unsigned char* mask) {
+  const size_t n = rows >= 0 && cols >= 0 ? (size_t)rows * cols : 0;
+  if (!ctx || rows < 0 || cols < 0 || n > ((size_t)1 << 30) || (n > 0 && (!ids || !mask)) || ranges_overlap(ids, n * 4, mask, n)) {
+    set_error("pgp_component_mask: bad argument");
+    return PGP_EINVAL;
+  }
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  Carve cv;
+  const auto c_ids = cv.add<int>(n, 256);
+  const auto c_mask = cv.add<unsigned char>(n, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(cv.at(c_ids), ids, n * 4, hipMemcpyHostToDevice, st));
+  if ((rc = launch_component_mask(cv.at(c_ids), n, id, cv.at(c_mask), st)) != PGP_OK) return rc;
+  PGP_HIP(hipMemcpyAsync(mask, cv.at(c_mask), n, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+int pgp_assign_masks_to_components_device(pgp_ctx* ctx, const int* d_ids, const void* d_classes, int class_bytes, int rows,
+                                          int cols, const int* class_values, int n_objects, int* component, int* pixels_in,
+                                          int* pixels_total, int* group, void* stream) {
+  const char* who = "pgp_assign_masks_to_components_device";
+  if (!assign_args_ok(ctx, d_ids, d_classes, class_bytes, rows, cols, class_values, n_objects, component, pixels_in,
+                      pixels_total, group, who))
+    return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int rc = ctx->d_cc_io.ensure(256 + (3 * (size_t)kAssignMaxObjects + 1) * 4);
+  if (rc != PGP_OK) return rc;
+  int* d_result = ctx->d_cc_io.as<int>();
+  if ((rc = launch_assign_masks(ctx, d_ids, d_classes, class_bytes, (size_t)rows * cols, class_values, n_objects, d_result,
+                                st)) != PGP_OK)
+    return rc;
+  int h_result[3 * kAssignMaxObjects + 1];
+  PGP_HIP(hipMemcpyAsync(h_result, d_result, (3 * (size_t)n_objects + 1) * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return assign_finish(h_result, n_objects, component, pixels_in, pixels_total, group, who);
+}
+
+int pgp_assign_masks_to_components(pgp_ctx* ctx, const int* ids, const void* classes, int class_bytes, int rows, int cols,
+                                   const int* class_values, int n_objects, int* component, int* pixels_in, int* pixels_total,
+                                   int* group) {
+  const char* who = "pgp_assign_masks_to_components";
+  if (!assign_args_ok(ctx, ids, classes, class_bytes, rows, cols, class_values, n_objects, component, pixels_in, pixels_total,
+                      group, who))
+    return PGP_EINVAL;
+  const size_t n = (size_t)rows * cols;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  Carve cv;
+  const auto c_res = cv.add<int>(3 * (size_t)kAssignMaxObjects + 1, 256);
+  const auto c_ids = cv.add<int>(n, 256);
+  const auto c_cls = cv.add<unsigned char>(n * (size_t)class_bytes, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK) return rc;
+  if (n > 0) {
+    PGP_HIP(hipMemcpyAsync(cv.at(c_ids), ids, n * 4, hipMemcpyHostToDevice, st));
+    PGP_HIP(hipMemcpyAsync(cv.at(c_cls), classes, n * (size_t)class_bytes, hipMemcpyHostToDevice, st));
+  }
+  if ((rc = launch_assign_masks(ctx, cv.at(c_ids), cv.at(c_cls), class_bytes, n, class_values, n_objects, cv.at(c_res), st)) !=
+      PGP_OK)
+    return rc;
+  int h_result[3 * kAssignMaxObjects + 1];
+  PGP_HIP(hipMemcpyAsync(h_result, cv.at(c_res), (3 * (size_t)n_objects + 1) * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return assign_finish(h_result, n_objects, component, pixels_in, pixels_total, group, who);
 }
 
 }  // extern "C"

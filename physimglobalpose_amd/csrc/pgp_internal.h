@@ -263,6 +263,7 @@ struct pgp_ctx {
   pgp::DevBuf d_pre_ws, d_vg_ws, d_pre_io;   // preprocess.hip: bbox partials, voxel-grid workspace, host-API staging
   pgp::DevBuf d_mls_ws;                      // mls.hip: sort keys, sorted cloud, per-point results
   pgp::DevBuf d_plane_ws, d_plane_io;        // plane.hip: candidate / partial workspace; host-API staging
+  pgp::DevBuf d_cc_ws, d_cc_io;              // components.hip: parents | roots | counts | sort keys; host-API staging
   bool hd_attr_set = false;
   // segment.hip: the filter's counts | workgroup counters | scan scratch, and the centroid of pgp_center_device (d_seg_c);
   // the intermediates of pgp_segment_from_depth_device: dense cloud, voxel leaves, the MLS and filter rows + weights
@@ -748,6 +749,16 @@ int launch_fit_plane(pgp_ctx* ctx, const float* d_xyz, int n, const pgp_plane_op
                      hipStream_t st);
 int launch_mask_plane_depth(pgp_ctx* ctx, void* d_img, bool raw16, int rows, int cols, const float K[9],
                             const float* coeff, const float* d_coeff, double thr, int* d_n_masked, hipStream_t st);
+
+// components.hip
+int launch_depth_components(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_img, bool raw16,
+                            const unsigned char* d_mask, int rows, int cols, const float K[9], int* d_roots, int* d_ids,
+                            pgp_component_info* d_info, int cap, int* d_counts, hipStream_t st);
+int launch_component_mask(const int* d_ids, size_t n, int id, unsigned char* d_mask, hipStream_t st);
+constexpr int kAssignMaxId = 65535, kAssignMaxObjects = 64;
+// d_result: n_objects x {component, pixels_in, pixels_total} followed by one flag word (non-zero: an id outside the bound)
+int launch_assign_masks(pgp_ctx* ctx, const int* d_ids, const void* d_classes, int class_bytes, size_t n,
+                        const int* class_values, int n_objects, int* d_result, hipStream_t st);
 
 // rigid_fit.hip
 int launch_rigid(pgp_ctx* ctx, const int* d_base_ids, const int* d_quad_ids, int n, const float cP[3],

@@ -846,6 +846,119 @@ class LcpScorer:
                                               cols, _fp(K9), C.c_float(leaf), C.byref(opt), _fp(coeff), C.byref(m)))
         return image, coeff, m.value
 
+    # ---- object proposals: connected components of a depth image --------------------------------------
+    COMPONENT_INFO_DTYPE = np.dtype([("root", "<i4"), ("pixels", "<i4"), ("u_min", "<i4"), ("u_max", "<i4"), ("v_min", "<i4"),
+                                     ("v_max", "<i4"), ("z_min", "<f4"), ("z_max", "<f4"), ("sum_um", "<i8", (3,))])
+
+    @staticmethod
+    def components_options(**kw):
+        """pgp_components_options with the defaults (0.1 < z < 2.0, tolerance 0.01, connectivity 4, min_pixels 500,
+        max_pixels 0), fields overridden by keyword."""
+        o = _lib.ComponentsOptions()
+        _lib.check(_lib.load().pgp_components_default_options(C.byref(o)))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError(f"pgp_components_options has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def depth_components(self, image, K, mask=None, cap=64, want_roots=True, want_ids=True, options=None, **kw):
+        """Connected components of a depth image (uint16 raw or float32 metres) with a 3-D distance test between
+        neighbouring pixels -> (roots (rows, cols) int32 or None, ids (rows, cols) int32 or None, info: structured array
+        of the min(kept, cap) written pgp_component_info rows, counts (3,) int32: kept, components, valid pixels).
+        Keywords are fields of pgp_components_options."""
+        image = np.ascontiguousarray(image)
+        assert image.dtype in (np.uint16, np.float32) and image.ndim == 2
+        rows, cols = image.shape
+        o = options if options is not None else self.components_options(**kw)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        roots = np.full((rows, cols), -2, np.int32) if want_roots else None
+        ids = np.full((rows, cols), -2, np.int32) if want_ids else None
+        info = np.zeros(max(cap, 1), self.COMPONENT_INFO_DTYPE)
+        counts = np.zeros(3, np.int32)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.pgp_depth_components(self._h, C.byref(o), vp(image), int(image.dtype == np.uint16), vp(m), rows,
+                                                  cols, _fp(K9), vp(roots), vp(ids), vp(info) if cap > 0 else None, int(cap),
+                                                  counts.ctypes.data_as(_i)))
+        return roots, ids, info[: min(int(counts[0]), cap)].copy(), counts
+
+    def depth_components_device(self, d_image, K, d_mask=None, cap=64, d_roots=None, d_ids=None, d_info=None, d_counts=None,
+                                want_roots=True, want_ids=True, options=None, stream=None, **kw):
+        """pgp_depth_components_device on torch tensors, queued on `stream` (default: the current stream) with no host
+        synchronisation.  Returns (d_roots, d_ids (rows, cols) int32 or None, d_info (cap, 56) uint8 -- the rows of
+        pgp_component_info, LcpScorer.component_info(d_info, n) reads them --, d_counts (3,) int32)."""
+        import torch
+        rows, cols = d_image.shape
+        assert d_image.is_cuda and d_image.is_contiguous() and d_image.dtype in (torch.uint16, torch.int16, torch.float32)
+        dev = d_image.device
+        o = options if options is not None else self.components_options(**kw)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        if d_roots is None and want_roots:
+            d_roots = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+        if d_ids is None and want_ids:
+            d_ids = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+        if d_info is None and cap > 0:
+            d_info = torch.zeros((cap, self.COMPONENT_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(3, dtype=torch.int32, device=dev) if d_counts is None else d_counts
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_depth_components_device(self._h, C.byref(o), p(d_image), int(d_image.dtype != torch.float32),
+                                                         p(d_mask), rows, cols, _fp(K9), p(d_roots), p(d_ids), p(d_info),
+                                                         int(cap), p(d_counts), C.c_void_p(st)))
+        return d_roots, d_ids, d_info, d_counts
+
+    @classmethod
+    def component_info(cls, d_info, n):
+        """The first n rows of a device (or numpy uint8) pgp_component_info table as a structured array."""
+        b = np.ascontiguousarray(d_info.cpu().numpy() if hasattr(d_info, "cpu") else d_info, np.uint8).reshape(-1)
+        return b[: n * cls.COMPONENT_INFO_DTYPE.itemsize].view(cls.COMPONENT_INFO_DTYPE).copy()
+
+    def component_mask(self, ids, id):
+        """(ids == id) as the uint8 mask pgp_segment_from_depth_device / pgp_backproject_depth read."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        rows, cols = ids.shape
+        mask = np.zeros((rows, cols), np.uint8)
+        _lib.check(self._lib.pgp_component_mask(self._h, ids.ctypes.data_as(C.c_void_p), rows, cols, int(id),
+                                                mask.ctypes.data_as(C.c_void_p)))
+        return mask
+
+    def component_mask_device(self, d_ids, id, d_mask=None, stream=None):
+        import torch
+        rows, cols = d_ids.shape
+        assert d_ids.is_cuda and d_ids.is_contiguous() and d_ids.dtype == torch.int32
+        d_mask = torch.empty((rows, cols), dtype=torch.uint8, device=d_ids.device) if d_mask is None else d_mask
+        st = (stream or torch.cuda.current_stream(d_ids.device)).cuda_stream
+        _lib.check(self._lib.pgp_component_mask_device(self._h, C.c_void_p(d_ids.data_ptr()), rows, cols, int(id),
+                                                       C.c_void_p(d_mask.data_ptr()), C.c_void_p(st)))
+        return d_mask
+
+    def assign_masks_to_components(self, ids, classes, class_values):
+        """Which component each object's 2-D mask (classes == class_values[o]; classes uint8 or uint16) falls into ->
+        (component, pixels_in, pixels_total, group), each (n_objects,) int32.  ids / classes: numpy arrays, or torch
+        device tensors (the device form: the current stream is synchronised once)."""
+        vals = np.ascontiguousarray(class_values, np.int32).reshape(-1)
+        n = len(vals)
+        out = [np.zeros(max(n, 1), np.int32) for _ in range(4)]
+        ip = [a.ctypes.data_as(_i) for a in out]
+        rows, cols = ids.shape
+        if hasattr(ids, "is_cuda"):
+            import torch
+            assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32 and classes.is_contiguous()
+            assert classes.dtype in (torch.uint8, torch.uint16, torch.int16) and tuple(classes.shape) == (rows, cols)
+            st = torch.cuda.current_stream(ids.device).cuda_stream
+            _lib.check(self._lib.pgp_assign_masks_to_components_device(
+                self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(classes.data_ptr()), classes.element_size(), rows, cols,
+                vals.ctypes.data_as(_i), n, *ip, C.c_void_p(st)))
+        else:
+            ids = np.ascontiguousarray(ids, np.int32)
+            classes = np.ascontiguousarray(classes)
+            assert classes.dtype in (np.uint8, np.uint16) and classes.shape == ids.shape
+            _lib.check(self._lib.pgp_assign_masks_to_components(
+                self._h, ids.ctypes.data_as(C.c_void_p), classes.ctypes.data_as(C.c_void_p), classes.dtype.itemsize, rows,
+                cols, vals.ctypes.data_as(_i), n, *ip))
+        return tuple(a[:n] for a in out)
+
     def depth_cost(self, observed, rendered, threshold=0.01):
         """observed (rows,cols) f32, rendered (n,rows,cols) f32 -> (render_score (n,), counts (n,3))."""
         obs = np.ascontiguousarray(observed, np.float32)
