@@ -1231,6 +1231,11 @@ int pgp_ppf_model_angles(pgp_ctx* ctx, float* alpha, long long n);
  * matched bit for bit: the device runs the stepping rules stated exactly in csrc/physics.hip (vertex-face contacts,
  * at most 4 per body pair, sequential impulses, first-order quaternion update), restated in numpy float32 by
  * tests/_physics_restate.py.  Only one body moves, so its mass cancels: impulses are per unit mass.
+ * Vertex-face contacts alone miss two hulls that meet without a vertex of either inside the other (crossed bars, a
+ * yawed box on a box): the dynamic body falls through.  pgp_physics_set_edge_contacts adds edge-edge contacts, off by
+ * default (the rule: csrc/physics.hip step 3e, restated by tests/_physics_edges_restate.py).  Its limits: a body
+ * thinner than `reach` can pick up an edge pair of its far side; an overlap deeper than `reach` falls back to
+ * vertex-face contacts; it is still not GJK/EPA (no face-face clipping, no closest features of separated hulls).
  * Shapes live in a per-context arena until pgp_destroy.  Shape 0 is the built-in table box (8 vertices, 6 planes,
  * margin 0); pgp_physics_add_shape hands out 1, 2, ... */
 #define PGP_PHYSICS_TABLE_SHAPE 0
@@ -1274,6 +1279,18 @@ int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, i
 /* What the device holds for a shape: hull_xyz (256 x 3), planes (512 x 4), inertia[3], margin (each nullable). */
 int pgp_physics_shape_info(pgp_ctx* ctx, int shape_id, float* hull_xyz, int* n_vert, float* planes, int* n_planes,
                            float inertia[3], float* margin);
+/* The hull edges the device holds for a shape: rows (v0, v1, f0, f1), v0 < v1 two hull vertices, f0 < f1 the two
+ * planes that meet there (indices into pgp_physics_shape_info's vertices and planes), ascending by (v0, v1).  An edge
+ * between coplanar triangles that merged into one plane is none.  edges ((3 x 256 - 6) x 4 ints) and n_edges are
+ * nullable; a hull of V vertices has at most 3 V - 6 edges, the table box 12. */
+#define PGP_PHYSICS_MAX_EDGES (3 * PGP_PHYSICS_MAX_VERTICES - 6)
+int pgp_physics_shape_edges(pgp_ctx* ctx, int shape_id, int* edges, int* n_edges);
+/* Edge-edge contacts in every later settle of this context (pgp_physics_settle, _settle_device, _trace,
+ * pgp_mcts_search); a context setting like pgp_set_exact_ties, off by default: while off, the settle kernel is the
+ * vertex-face one, bit for bit.  reach (metres, > 0, finite): the largest distance between the closest
+ * points of two edges that still makes a contact.  PGP_EINVAL: NULL context or a bad reach (nothing changes). */
+#define PGP_PHYSICS_EDGE_REACH_DEFAULT 0.01f
+int pgp_physics_set_edge_contacts(pgp_ctx* ctx, int on, float reach);
 /* correctPhysics for n_states independent states, one dynamic body each: state i drops dyn_shape[i] at T[i] among the
  * table and its statics static_shape[j] at static_T[j], j in [static_offsets[i], static_offsets[i + 1]) (at most 16).
  * Poses are 16 floats column-major, object -> camera frame like every T of this header; world = cam_pose . T

@@ -361,6 +361,8 @@ SIGNATURES = {
     "pgp_convex_hull": (C.c_int, [_f, C.c_int, C.c_int, _f, _i, _f, _i]),
     "pgp_physics_add_shape": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_float, C.c_int, _i]),
     "pgp_physics_shape_info": (C.c_int, [C.c_void_p, C.c_int, _f, _i, _f, _i, _f, _f]),
+    "pgp_physics_shape_edges": (C.c_int, [C.c_void_p, C.c_int, _i, _i]),
+    "pgp_physics_set_edge_contacts": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "pgp_physics_settle": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, _i, _f, _i, _i, _f, _f, _f, _f,
                                      C.POINTER(PhysicsInfo)]),
     "pgp_physics_settle_device": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, C.c_void_p, C.c_void_p,

@@ -3562,20 +3562,27 @@ int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, i
   }
   std::vector<int> hv;
   std::vector<std::array<double, 4>> pl;
-  int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_physics_add_shape");
+  std::vector<int4> ed;
+  int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_physics_add_shape", &ed);
   if (rc != PGP_OK) return rc;
+  if ((int)ed.size() > PGP_PHYSICS_MAX_EDGES) {   // a closed hull of V vertices has at most 3 V - 6 edges
+    set_error("pgp_physics_add_shape: %d hull edges (at most %d)", (int)ed.size(), PGP_PHYSICS_MAX_EDGES);
+    return PGP_EINVAL;
+  }
   CtxGuard guard(ctx);
   if ((rc = physics_arena_init(ctx)) != PGP_OK) return rc;
   std::vector<float4> v, p;
   for (int i : hv) v.push_back(make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f));
   for (const auto& e : pl) p.push_back(make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]));
   PGP_HIP(hipDeviceSynchronize());   // a queued settle may still read the arena that is about to grow
-  arena_append(ctx, v, p, margin);
+  arena_append(ctx, v, p, ed, margin);
   if ((rc = arena_upload(ctx)) != PGP_OK) {
     const PhysShape s = ctx->phys_shapes.back();
     ctx->phys_shapes.pop_back();
     ctx->phys_verts.resize(s.vert_off);
     ctx->phys_planes.resize(s.plane_off);
+    ctx->phys_edges.resize(ctx->phys_eslices.back().edge_off);
+    ctx->phys_eslices.pop_back();
     return rc;
   }
   *shape_id = (int)ctx->phys_shapes.size() - 1;
@@ -3613,6 +3620,37 @@ int pgp_physics_shape_info(pgp_ctx* ctx, int shape_id, float* hull_xyz, int* n_v
   if (inertia)
     for (int i = 0; i < 3; ++i) inertia[i] = s.inertia[i];
   if (margin) *margin = s.margin;
+  return PGP_OK;
+}
+
+int pgp_physics_shape_edges(pgp_ctx* ctx, int shape_id, int* edges, int* n_edges) {
+  if (!ctx) {
+    set_error("pgp_physics_shape_edges: null context");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  int rc = physics_arena_init(ctx);
+  if (rc != PGP_OK) return rc;
+  if (shape_id < 0 || shape_id >= (int)ctx->phys_shapes.size()) {
+    set_error("pgp_physics_shape_edges: unknown shape %d", shape_id);
+    return PGP_EINVAL;
+  }
+  PhysEdgeSlice s;
+  PGP_HIP(hipMemcpy(&s, ctx->d_phys_eslices.as<PhysEdgeSlice>() + shape_id, sizeof(s), hipMemcpyDeviceToHost));
+  if (n_edges) *n_edges = s.n_edge;
+  if (edges && s.n_edge > 0)
+    PGP_HIP(hipMemcpy(edges, ctx->d_phys_edges.as<int4>() + s.edge_off, (size_t)s.n_edge * sizeof(int4), hipMemcpyDeviceToHost));
+  return PGP_OK;
+}
+
+int pgp_physics_set_edge_contacts(pgp_ctx* ctx, int on, float reach) {
+  if (!ctx || !(reach > 0.f) || !std::isfinite(reach)) {
+    set_error("pgp_physics_set_edge_contacts: %s", !ctx ? "ctx is NULL" : "reach must be > 0 and finite");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  ctx->phys_edge_contacts = on != 0;
+  ctx->phys_edge_reach = reach;
   return PGP_OK;
 }
 

@@ -129,6 +129,12 @@ struct PhysShape {
   float inertia[3];       // unit-mass inertia diagonal
   float pad;
 };
+// the hull edges of shape i: rows (v0, v1, f0, f1), an int4 slice of the edge arena (indices into the shape's own
+// vertices and planes).  Kept beside PhysShape, one per shape, not in it: the vertex-face settle kernel stages
+// PhysShape whole and must stay the code it was (see settle_kernel)
+struct PhysEdgeSlice {
+  int edge_off, n_edge;
+};
 
 }  // namespace pgp
 
@@ -370,7 +376,11 @@ struct pgp_ctx {
   // physics shape arena (physics.hip): host mirrors and their device copies (shape 0 = the table box)
   std::vector<pgp::PhysShape> phys_shapes;
   std::vector<float4> phys_verts, phys_planes;   // body frame: {x, y, z, 0} and {n, d}
-  pgp::DevBuf d_phys_shapes, d_phys_verts, d_phys_planes, d_phys_io;
+  std::vector<pgp::PhysEdgeSlice> phys_eslices;  // one per shape
+  std::vector<int4> phys_edges;                  // hull edges: {v0, v1, f0, f1}, v0 < v1, f0 < f1, ascending (v0, v1)
+  pgp::DevBuf d_phys_shapes, d_phys_verts, d_phys_planes, d_phys_eslices, d_phys_edges, d_phys_io;
+  bool phys_edge_contacts = false;   // pgp_physics_set_edge_contacts: launch_settle runs the edge-edge instantiation
+  float phys_edge_reach = PGP_PHYSICS_EDGE_REACH_DEFAULT;
 
   // MCTS search (mcts.hip): step workspace (pose tables, settle inputs, descriptors, scores); two images per slot
   pgp::DevBuf d_mcts_ws, d_mcts_img;
@@ -660,9 +670,11 @@ struct PhysParams {
   float table[12];
 };
 int physics_arena_init(pgp_ctx* ctx);   // the built-in table box as shape 0, uploaded (idempotent)
+// edges (nullable): the hull's edge rows (v0, v1, f0, f1) over hv and pl, see PhysShape
 int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>& hv, std::vector<std::array<double, 4>>& pl,
-                     const char* who);
-void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, float margin);
+                     const char* who, std::vector<int4>* edges = nullptr);
+void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, const std::vector<int4>& e,
+                  float margin);
 int arena_upload(pgp_ctx* ctx);
 int check_options(const pgp_physics_options* o, const char* who, int max_steps);
 int make_params(pgp_ctx* ctx, const pgp_physics_options* o, int n_states, const float* table_params, const float* cam_pose,

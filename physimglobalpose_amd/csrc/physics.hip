@@ -3,13 +3,16 @@
 // The reference (PPE/hypothesis_verification/mcts/UCTState.cpp:208-270, physics_reasoning/PhySim.cpp) drops the newest
 // object into a Bullet 2.86 world among the earlier objects (mass 0) and the table box, runs 60 x stepSimulation(1/60)
 // and reads the pose back.  Bullet is not matched bit for bit; this file runs the rules below EXACTLY, and
-// tests/_physics_restate.py restates them in numpy float32, term by term.  Every operation is float32, rounded
+// tests/_physics_restate.py (steps 1 .. 6) and tests/_physics_edges_restate.py (with step 3e) restate them in numpy
+// float32, term by term.  Every operation is float32, rounded
 // separately (-ffp-contract=off), sums left to right as written; sqrt(x) = (float)sqrt((double)x) and a / b = __fdiv_rn,
 // both correctly rounded.  One dynamic body D per state; the others (the table first, then the statics in the caller's
 // order) are static S.  Mass cancels: impulses are per unit mass, 1/m = 1.
 //
 // Shapes (pgp_physics_add_shape): hull vertices v and planes (n, d) (n . x <= d inside) in the body frame, margin m,
-// radius r (bounding sphere about the body origin), unit-mass inertia diagonal I (see include/pgp.h).
+// radius r (bounding sphere about the body origin), unit-mass inertia diagonal I (see include/pgp.h), and the hull's
+// edges as rows (v0, v1, f0, f1): two vertices shared by two triangles of the hull whose merged planes f0 < f1 differ
+// (a side between coplanar triangles that merged into one plane is no edge), v0 < v1, rows ascending by (v0, v1).
 // Poses: W_D = cam . T (4 x 4 column-major products, element (i, j) = ((C_i0 T_0j + C_i1 T_1j) + C_i2 T_2j) + C_i3 T_3j),
 // W_S = cam . T_S likewise (cam NULL: W = T); the table's R, t are the rows of tableParams.  R_D -> q by Shepperd's
 // method, then q /= |q| (quat_from_R); R(q) is Bullet's setRotation matrix (R_from_q).  x = W_D's translation.
@@ -27,6 +30,25 @@
 //       maximal s_f (the least penetrated); normal R_S n_f; point p; depth = max s_f - m.
 //       S vertex s: p = R_S s + t_S (world), p_D = R^T (p - x), s_f over D's planes; normal -(R n_f); point p.
 //     The plane loop stops at the first s_f >= m (exact: such a vertex is no candidate).
+//  3e. Edge-edge candidates of the pair, only with pgp_physics_set_edge_contacts on (reach: its second argument):
+//     Active edges: an edge of D is active unless one plane of S has BOTH its end points at s_f >= m, the end points
+//     taken in S's frame with the s_f expression above; an edge of S likewise against D's planes (its end points
+//     p = R_S s + t_S, p_D = R^T (p - x)).  Active edges keep their ascending edge index.
+//     Pairs (active D edge a0 a1, active S edge b0 b1, world points), ascending by (D edge, S edge):
+//       d1 = a1 - a0, d2 = b1 - b0, r = a0 - b0; a = d1 . d1, e = d2 . d2, b = d1 . d2, c = d1 . r, f = d2 . r (each
+//       (x x + y y) + z z); den = a e - b b; rejected unless den > 1e-6f (a e) (parallel edges);
+//       s = (b f - c e) / den, t = (a f - b c) / den; rejected unless 0 < s < 1 and 0 < t < 1 (end points stay with
+//       the vertex test); c_D = a0 + s d1, c_S = b0 + t d2 (per component a0_i + s d1_i); g = c_D - c_S; rejected
+//       when |g|^2 > reach reach (a far-side pair of two overlapping flat bodies would be the deepest candidate);
+//       rejected unless every s_f of c_D over S's planes is < m (u = c_D - t_S, as for a D vertex) and every s_f of
+//       c_S over D's planes is < m (u = c_S - x, as for an S vertex);
+//       n = (d1 x d2) / |d1 x d2| (each component divided by L = sqrt(|d1 x d2|^2));
+//       o_S = R_S (n_f0 + n_f1) of the S edge's planes, o_D = R (n_f0 + n_f1) of the D edge's (sums per component,
+//       then (R_i0 q_x + R_i1 q_y) + R_i2 q_z); n = -n when n . o_S < 0; rejected unless then n . o_S > 0 and
+//       n . o_D < 0 (n leaves S and enters D);
+//       candidate: point c_D, normal n, depth = (n . g) - m.
+//     Edge candidates are numbered after D's and S's vertex candidates, in pair order; a pair has room for 512
+//     candidates in all, and edge candidates past it are dropped, in pair order.
 //  4. Manifold reduction, when a pair has more than 4 candidates (else all of them, in candidate order): c1 = the
 //     least depth; c2 = max |p - p1|^2; c3 = max |(p - p1) x (p - p2)|^2; c4 = max of the sum
 //     (|(p - p1) x (p - p2)|^2 + |(p - p2) x (p - p3)|^2) + |(p - p3) x (p - p1)|^2; each among the candidates not
@@ -44,19 +66,25 @@
 //     q = q / |q|.  (Bullet integrates with the exponential map; this first-order update needs only + - x / sqrt.)
 // Out: W = [R(q) | x], T_out = cam^-1 . W (cam^-1 the rigid inverse formed on the host in float: R^T,
 // -(((R_0i t_0 + R_1i t_1) + R_2i t_2))), or W without cam.  steps == 0: T_out = T, bit for bit.
-// Contacts are vertex-face only (no edge-edge), with no persistent manifold, no split impulse, no restitution.
+// Contacts are vertex-face, plus edge-edge behind the switch; no persistent manifold, no split impulse, no
+// restitution.  Limits of 3e: a body thinner than reach can pick up an edge pair of its far side; an overlap deeper
+// than reach falls back to vertex-face contacts; it is still not GJK/EPA.
 //
 // Kernel: one workgroup of 256 threads per state, all steps in one launch.  D's hull (body and world frame) and
 // planes sit in LDS; candidates are tested one vertex per thread and compacted in vertex order with a ballot and
 // a prefix; the reduction is a block arg-max with lowest-index ties; the impulse loop is a chain of dependent row
 // updates and runs on one lane.  The planes of each static body are staged into LDS per pair and step (the plane
 // loop of a vertex is a chain of dependent loads: from L2 it cost ~8x more with 256-vertex hulls); its vertices
-// are read from the arena (it stays in L2) and transformed on the fly.  Workgroups never talk to each other, so a state's result is independent of its batch.
+// are read from the arena (it stays in L2) and transformed on the fly.  Step 3e (settle_kernel<true> only): one
+// edge per thread and pass of 256 for the activity test, compacted like the candidates into 16-bit indices in LDS;
+// then one edge pair per thread and pass, compacted behind the vertex candidates; every loop is bounded by the edge
+// counts.  Workgroups never talk to each other, so a state's result is independent of its batch.
 #include <algorithm>
 #include <array>
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <map>
 #include <set>
 #include <utility>
 
@@ -69,6 +97,7 @@ namespace {
 constexpr int PT = 256;                                     // threads per state
 constexpr int MAXV = PGP_PHYSICS_MAX_VERTICES;
 constexpr int MAXP = 2 * MAXV;                              // plane capacity of a shape (a hull has <= 2V - 4)
+constexpr int MAXE = PGP_PHYSICS_MAX_EDGES;                 // edge capacity of a shape (a hull has <= 3V - 6)
 constexpr int MAXB = 1 + PGP_PHYSICS_MAX_STATICS;           // bodies besides D
 constexpr int MAXC = PGP_PHYSICS_MAX_CONTACTS;
 constexpr float HALF_PI_F = 1.57079637f;
@@ -174,13 +203,20 @@ __device__ void plane_space(const float* n, float* p, float* q) {
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
+// EDGES = false is the vertex-face kernel: step 3e is compiled out, not branched over, and PhysShape, which this kernel
+// stages whole, keeps its 40 bytes (the edge slices live beside it in PhysEdgeSlice): that instantiation is the kernel
+// of before, instruction for instruction and at the same offsets.  It matters: the same loops moved by 8 .. 40 bytes
+// ran 4-9 % slower or faster, row by row (DESIGN.md section 4 has the figures of both instantiations and of the moves)
+template <bool EDGES>
 __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShape* __restrict__ shapes,
                                                     const float4* __restrict__ verts, const float4* __restrict__ planes,
                                                     const int* __restrict__ dyn_shape, const float* T,
                                                     const int* __restrict__ static_off, const int* __restrict__ static_shape,
                                                     const float* __restrict__ static_T, float* T_out,
                                                     pgp_physics_info* __restrict__ info, float* __restrict__ tr_state,
-                                                    float* __restrict__ tr_contacts, int* __restrict__ tr_n) {
+                                                    float* __restrict__ tr_contacts, int* __restrict__ tr_n,
+                                                    const PhysEdgeSlice* __restrict__ eslice, const int4* __restrict__ edges,
+                                                    float reach) {
   __shared__ float4 s_dv[MAXV];        // D's hull, body frame
   __shared__ float4 s_dw[MAXV];        // D's hull, world frame of the step
   __shared__ float4 s_dp[MAXP];        // D's planes, body frame
@@ -189,6 +225,7 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
   __shared__ float4 s_cn[2 * PT];      // candidates: normal
   __shared__ float s_body[MAXB][12];   // R (row-major) | t of the table and the statics, world frame
   __shared__ PhysShape s_sh[MAXB + 1]; // [0] = D, [1 + j] = body j
+  __shared__ PhysEdgeSlice s_er[EDGES ? MAXB + 1 : 1];   // their edge slices, settle_kernel<true> only
   __shared__ float4 s_ctp[MAXC], s_ctn[MAXC];
   __shared__ Row s_rows[3 * MAXC];
   __shared__ float s_x[3], s_q[4], s_v[3], s_w[3], s_R[9], s_Iw[9], s_Tin[16];
@@ -214,6 +251,10 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
     if (ok) {
       s_sh[0] = shapes[dyn];
       s_sh[1] = shapes[0];
+      if constexpr (EDGES) {
+        s_er[0] = eslice[dyn];
+        s_er[1] = eslice[0];
+      }
       for (int i = 0; i < 3; ++i) {
         for (int c = 0; c < 3; ++c) s_body[0][3 * i + c] = P.table[4 * i + c];
         s_body[0][9 + i] = P.table[4 * i + 3];
@@ -221,6 +262,7 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
       for (int k = o0; k < o1; ++k) {
         const int b = 1 + (k - o0);
         s_sh[1 + b] = shapes[static_shape[k]];
+        if constexpr (EDGES) s_er[1 + b] = eslice[static_shape[k]];
         float Ts[16], W[16];
         for (int e = 0; e < 16; ++e) Ts[e] = static_T[(size_t)k * 16 + e];
         if (P.has_cam) mat4_mul(P.cam, Ts, W);
@@ -360,6 +402,152 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
       if (fl[0]) { const int at = base0 + __popcll(b0 & lt); s_cp[at] = cp[0]; s_cn[at] = cn[0]; }
       if (fl[1]) { const int at = base1 + __popcll(b1 & lt); s_cp[at] = cp[1]; s_cn[at] = cn[1]; }
       __syncthreads();
+      if constexpr (EDGES) {
+        // 3e: edge-edge candidates, appended after the vertex candidates
+        __shared__ unsigned short s_ae[2][MAXE];   // active edges of D ([0]) and of S ([1]), ascending edge index
+        const PhysEdgeSlice Der = s_er[0], Ser = s_er[1 + b];
+        int n_act[2];
+        for (int side = 0; side < 2; ++side) {
+          // an edge is active unless one plane of the other body holds both its end points at s_f >= m
+          const int ne = side == 0 ? Der.n_edge : Ser.n_edge;
+          const int eoff = side == 0 ? Der.edge_off : Ser.edge_off;
+          const float4* pl = side == 0 ? s_sp : s_dp;
+          const int npl = side == 0 ? S.n_plane : D.n_plane;
+          int na = 0;
+          for (int e0 = 0; e0 < ne; e0 += PT) {
+            const int e = e0 + tid;
+            bool act = false;
+            if (e < ne) {
+              const int4 row = edges[eoff + e];
+              float la[3], lb[3];
+              if (side == 0) {
+                const float4 a = s_dw[row.x], c = s_dw[row.y];
+                const float ua[3] = {a.x - B[9], a.y - B[10], a.z - B[11]}, ub[3] = {c.x - B[9], c.y - B[10], c.z - B[11]};
+                for (int i = 0; i < 3; ++i) {
+                  la[i] = (B[i] * ua[0] + B[3 + i] * ua[1]) + B[6 + i] * ua[2];
+                  lb[i] = (B[i] * ub[0] + B[3 + i] * ub[1]) + B[6 + i] * ub[2];
+                }
+              } else {
+                const float4 a = verts[S.vert_off + row.x], c = verts[S.vert_off + row.y];
+                float ua[3], ub[3];
+                for (int i = 0; i < 3; ++i) {
+                  ua[i] = (((B[3 * i] * a.x + B[3 * i + 1] * a.y) + B[3 * i + 2] * a.z) + B[9 + i]) - x[i];
+                  ub[i] = (((B[3 * i] * c.x + B[3 * i + 1] * c.y) + B[3 * i + 2] * c.z) + B[9 + i]) - x[i];
+                }
+                for (int i = 0; i < 3; ++i) {
+                  la[i] = (R[i] * ua[0] + R[3 + i] * ua[1]) + R[6 + i] * ua[2];
+                  lb[i] = (R[i] * ub[0] + R[3 + i] * ub[1]) + R[6 + i] * ub[2];
+                }
+              }
+              act = true;
+              for (int f = 0; f < npl; ++f) {
+                const float4 q = pl[f];
+                const float sa = ((q.x * la[0] + q.y * la[1]) + q.z * la[2]) - q.w;
+                const float sb = ((q.x * lb[0] + q.y * lb[1]) + q.z * lb[2]) - q.w;
+                if (sa >= m && sb >= m) { act = false; break; }
+              }
+            }
+            const unsigned long long ba = __ballot(act);
+            if (lane == 0) s_wc[wv] = __popcll(ba);
+            __syncthreads();
+            int at = na;
+            for (int k = 0; k < 4; ++k) {
+              if (k < wv) at += s_wc[k];
+              na += s_wc[k];
+            }
+            if (act) s_ae[side][at + __popcll(ba & lt)] = (unsigned short)e;
+            __syncthreads();
+          }
+          n_act[side] = na;
+        }
+        // pairs in ascending (active D edge, active S edge) order, one per thread, a workgroup's worth at a time
+        const int npair = n_act[0] * n_act[1];
+        const float reach2 = reach * reach;
+        for (int p0 = 0; p0 < npair && cnt < 2 * PT; p0 += PT) {
+          const int pi = p0 + tid;
+          bool ok = false;
+          float4 ecp = make_float4(0.f, 0.f, 0.f, 0.f), ecn = ecp;
+          if (pi < npair) {
+            const int ia = pi / n_act[1];
+            const int4 ed = edges[Der.edge_off + s_ae[0][ia]], es = edges[Ser.edge_off + s_ae[1][pi - ia * n_act[1]]];
+            const float4 a0 = s_dw[ed.x], a1 = s_dw[ed.y];
+            const float4 v0 = verts[S.vert_off + es.x], v1 = verts[S.vert_off + es.y];
+            float b0[3], b1v[3];
+            for (int i = 0; i < 3; ++i) {
+              b0[i] = ((B[3 * i] * v0.x + B[3 * i + 1] * v0.y) + B[3 * i + 2] * v0.z) + B[9 + i];
+              b1v[i] = ((B[3 * i] * v1.x + B[3 * i + 1] * v1.y) + B[3 * i + 2] * v1.z) + B[9 + i];
+            }
+            const float d1[3] = {a1.x - a0.x, a1.y - a0.y, a1.z - a0.z};
+            const float d2[3] = {b1v[0] - b0[0], b1v[1] - b0[1], b1v[2] - b0[2]};
+            const float r[3] = {a0.x - b0[0], a0.y - b0[1], a0.z - b0[2]};
+            const float a = dot3(d1, d1), e = dot3(d2, d2), bq = dot3(d1, d2), c = dot3(d1, r), f = dot3(d2, r);
+            const float ae = a * e;
+            const float den = ae - bq * bq;
+            if (den > 1e-6f * ae) {
+              const float s = fdv(bq * f - c * e, den), t = fdv(a * f - bq * c, den);
+              if (s > 0.f && s < 1.f && t > 0.f && t < 1.f) {
+                const float cD[3] = {a0.x + s * d1[0], a0.y + s * d1[1], a0.z + s * d1[2]};
+                const float cS[3] = {b0[0] + t * d2[0], b0[1] + t * d2[1], b0[2] + t * d2[2]};
+                const float g[3] = {cD[0] - cS[0], cD[1] - cS[1], cD[2] - cS[2]};
+                if (!(norm2_3(g[0], g[1], g[2]) > reach2)) {
+                  // c_D inside S grown by m, c_S inside D grown by m
+                  const float uS[3] = {cD[0] - B[9], cD[1] - B[10], cD[2] - B[11]};
+                  const float uD[3] = {cS[0] - x[0], cS[1] - x[1], cS[2] - x[2]};
+                  float lS[3], lD[3];
+                  for (int i = 0; i < 3; ++i) {
+                    lS[i] = (B[i] * uS[0] + B[3 + i] * uS[1]) + B[6 + i] * uS[2];
+                    lD[i] = (R[i] * uD[0] + R[3 + i] * uD[1]) + R[6 + i] * uD[2];
+                  }
+                  bool in = true;
+                  for (int k = 0; k < S.n_plane && in; ++k) {
+                    const float4 q = s_sp[k];
+                    in = ((q.x * lS[0] + q.y * lS[1]) + q.z * lS[2]) - q.w < m;
+                  }
+                  for (int k = 0; k < D.n_plane && in; ++k) {
+                    const float4 q = s_dp[k];
+                    in = ((q.x * lD[0] + q.y * lD[1]) + q.z * lD[2]) - q.w < m;
+                  }
+                  if (in) {
+                    float cr[3], n[3];
+                    cross3(d1, d2, cr);
+                    const float L = fsq(norm2_3(cr[0], cr[1], cr[2]));
+                    for (int i = 0; i < 3; ++i) n[i] = fdv(cr[i], L);
+                    const float4 s0 = s_sp[es.z], s1 = s_sp[es.w], q0 = s_dp[ed.z], q1 = s_dp[ed.w];
+                    const float qS[3] = {s0.x + s1.x, s0.y + s1.y, s0.z + s1.z}, qD[3] = {q0.x + q1.x, q0.y + q1.y, q0.z + q1.z};
+                    float oS[3], oD[3];
+                    for (int i = 0; i < 3; ++i) {
+                      oS[i] = (B[3 * i] * qS[0] + B[3 * i + 1] * qS[1]) + B[3 * i + 2] * qS[2];
+                      oD[i] = (R[3 * i] * qD[0] + R[3 * i + 1] * qD[1]) + R[3 * i + 2] * qD[2];
+                    }
+                    float dS = dot3(n, oS), dD = dot3(n, oD);
+                    if (dS < 0.f) {
+                      for (int i = 0; i < 3; ++i) n[i] = -n[i];
+                      dS = -dS; dD = -dD;
+                    }
+                    if (dS > 0.f && dD < 0.f) {
+                      ok = true;
+                      ecp = make_float4(cD[0], cD[1], cD[2], dot3(n, g) - m);
+                      ecn = make_float4(n[0], n[1], n[2], 0.f);
+                    }
+                  }
+                }
+              }
+            }
+          }
+          const unsigned long long bo = __ballot(ok);
+          if (lane == 0) s_wc[wv] = __popcll(bo);
+          __syncthreads();
+          int at = cnt;
+          for (int k = 0; k < 4; ++k) {
+            if (k < wv) at += s_wc[k];
+            cnt += s_wc[k];
+          }
+          at += __popcll(bo & lt);
+          if (ok && at < 2 * PT) { s_cp[at] = ecp; s_cn[at] = ecn; }   // past the capacity: dropped, in pair order
+          if (cnt > 2 * PT) cnt = 2 * PT;
+          __syncthreads();
+        }
+      }
       if (cnt > 4) {
         for (int round = 0; round < 4; ++round) {
           float bv = -INFINITY;
@@ -598,7 +786,7 @@ bool hull_faces(const std::vector<V3>& P, const std::vector<int>& ids, double ep
 }  // namespace
 
 int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>& hv, std::vector<std::array<double, 4>>& pl,
-                     const char* who) {
+                     const char* who, std::vector<int4>* edges) {
   if (!xyz || n < 4 || max_vertices < 4 || max_vertices > MAXV) {
     set_error("%s: bad argument (n = %d, max_vertices = %d of 4 .. %d)", who, n, max_vertices, MAXV);
     return PGP_EINVAL;
@@ -673,6 +861,27 @@ int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>
     for (int v : hv) d = std::max(d, dt3(nn, P[v]));
     pl.push_back({nn.x, nn.y, nn.z, d});
   }
+  if (edges) {
+    // hull edges from the topology: a triangle side shared by two triangles of different planes; the map orders
+    // them by (v0, v1), v the position in hv
+    edges->clear();
+    std::map<std::pair<int, int>, std::pair<int, int>> em;   // (v0, v1) -> the planes of the two triangles
+    for (size_t i = 0; i < faces.size(); ++i) {
+      const int t[3] = {faces[i].a, faces[i].b, faces[i].c};
+      for (int k = 0; k < 3; ++k) {
+        const int va = (int)(std::lower_bound(hv.begin(), hv.end(), t[k]) - hv.begin());
+        const int vb = (int)(std::lower_bound(hv.begin(), hv.end(), t[(k + 1) % 3]) - hv.begin());
+        auto it = em.find({std::min(va, vb), std::max(va, vb)});
+        if (it == em.end()) em[{std::min(va, vb), std::max(va, vb)}] = {grp[i], -1};
+        else it->second.second = grp[i];
+      }
+    }
+    for (const auto& e : em) {
+      const int f0 = e.second.first, f1 = e.second.second;
+      if (f1 < 0 || f0 == f1) continue;
+      edges->push_back(make_int4(e.first.first, e.first.second, std::min(f0, f1), std::max(f0, f1)));
+    }
+  }
   return PGP_OK;
 }
 
@@ -681,16 +890,22 @@ int arena_upload(pgp_ctx* ctx) {
   if ((rc = ctx->d_phys_shapes.ensure(ctx->phys_shapes.size() * sizeof(PhysShape))) != PGP_OK) return rc;
   if ((rc = ctx->d_phys_verts.ensure(ctx->phys_verts.size() * sizeof(float4))) != PGP_OK) return rc;
   if ((rc = ctx->d_phys_planes.ensure(ctx->phys_planes.size() * sizeof(float4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_phys_eslices.ensure(ctx->phys_eslices.size() * sizeof(PhysEdgeSlice))) != PGP_OK) return rc;
+  if ((rc = ctx->d_phys_edges.ensure(ctx->phys_edges.size() * sizeof(int4))) != PGP_OK) return rc;
   PGP_HIP(hipMemcpy(ctx->d_phys_shapes.p, ctx->phys_shapes.data(), ctx->phys_shapes.size() * sizeof(PhysShape),
                     hipMemcpyHostToDevice));
   PGP_HIP(hipMemcpy(ctx->d_phys_verts.p, ctx->phys_verts.data(), ctx->phys_verts.size() * sizeof(float4), hipMemcpyHostToDevice));
   PGP_HIP(hipMemcpy(ctx->d_phys_planes.p, ctx->phys_planes.data(), ctx->phys_planes.size() * sizeof(float4),
                     hipMemcpyHostToDevice));
+  PGP_HIP(hipMemcpy(ctx->d_phys_eslices.p, ctx->phys_eslices.data(), ctx->phys_eslices.size() * sizeof(PhysEdgeSlice),
+                    hipMemcpyHostToDevice));
+  PGP_HIP(hipMemcpy(ctx->d_phys_edges.p, ctx->phys_edges.data(), ctx->phys_edges.size() * sizeof(int4), hipMemcpyHostToDevice));
   return PGP_OK;
 }
 
 // appends a shape to the host mirror; the radius and inertia follow the rules of include/pgp.h
-void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, float margin) {
+void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, const std::vector<int4>& e,
+                  float margin) {
   PhysShape s{};
   s.vert_off = (int)ctx->phys_verts.size();
   s.n_vert = (int)v.size();
@@ -715,8 +930,10 @@ void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<
   s.inertia[1] = (float)((l2[0] + l2[2]) / 12.0);
   s.inertia[2] = (float)((l2[0] + l2[1]) / 12.0);
   ctx->phys_shapes.push_back(s);
+  ctx->phys_eslices.push_back(PhysEdgeSlice{(int)ctx->phys_edges.size(), (int)e.size()});
   ctx->phys_verts.insert(ctx->phys_verts.end(), v.begin(), v.end());
   ctx->phys_planes.insert(ctx->phys_planes.end(), p.begin(), p.end());
+  ctx->phys_edges.insert(ctx->phys_edges.end(), e.begin(), e.end());
 }
 
 int check_options(const pgp_physics_options* o, const char* who, int max_steps) {
@@ -778,9 +995,11 @@ int launch_settle(pgp_ctx* ctx, const PhysParams& P, const int* d_dyn, const flo
                   const int* d_ss, const float* d_sT, float* d_out, pgp_physics_info* d_info, float* tr_s, float* tr_c,
                   int* tr_n, hipStream_t st) {
   if (P.n_states == 0) return PGP_OK;
-  hipLaunchKernelGGL(settle_kernel, dim3(P.n_states), dim3(PT), 0, st, P, ctx->d_phys_shapes.as<PhysShape>(),
+  // the context's switch picks the instantiation (pgp_physics_set_edge_contacts); off: the vertex-face kernel
+  auto* kernel = ctx->phys_edge_contacts ? settle_kernel<true> : settle_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(P.n_states), dim3(PT), 0, st, P, ctx->d_phys_shapes.as<PhysShape>(),
                      ctx->d_phys_verts.as<float4>(), ctx->d_phys_planes.as<float4>(), d_dyn, d_T, d_off, d_ss, d_sT, d_out,
-                     d_info, tr_s, tr_c, tr_n);
+                     d_info, tr_s, tr_c, tr_n, ctx->d_phys_eslices.as<PhysEdgeSlice>(), ctx->d_phys_edges.as<int4>(), ctx->phys_edge_reach);
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }
@@ -832,9 +1051,19 @@ int physics_arena_init(pgp_ctx* ctx) {
   for (int i = 0; i < 8; ++i) v.push_back(make_float4(i & 1 ? 0.4f : -0.4f, i & 2 ? 0.4f : -0.4f, i & 4 ? 0.2f : -0.2f, 0.f));
   p = {make_float4(1, 0, 0, 0.4f), make_float4(-1, 0, 0, 0.4f), make_float4(0, 1, 0, 0.4f),
        make_float4(0, -1, 0, 0.4f), make_float4(0, 0, 1, 0.2f), make_float4(0, 0, -1, 0.2f)};
-  arena_append(ctx, v, p, 0.f);
+  // its 12 edges: vertices that differ in one bit; bit k set means the + side of axis k, planes 2k (+) and 2k + 1 (-)
+  std::vector<int4> e;
+  for (int i = 0; i < 8; ++i)
+    for (int ax = 0; ax < 3; ++ax) {
+      if (i & (1 << ax)) continue;
+      const int o0 = ax == 0 ? 1 : 0, o1 = ax == 2 ? 1 : 2;
+      e.push_back(make_int4(i, i | (1 << ax), 2 * o0 + (i & (1 << o0) ? 0 : 1), 2 * o1 + (i & (1 << o1) ? 0 : 1)));
+    }
+  std::sort(e.begin(), e.end(), [](const int4& a, const int4& b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
+  arena_append(ctx, v, p, e, 0.f);
   const int rc = arena_upload(ctx);
-  if (rc != PGP_OK) ctx->phys_shapes.clear(), ctx->phys_verts.clear(), ctx->phys_planes.clear();
+  if (rc != PGP_OK) ctx->phys_shapes.clear(), ctx->phys_verts.clear(), ctx->phys_planes.clear(), ctx->phys_edges.clear(),
+                      ctx->phys_eslices.clear();
   return rc;
 }
 

@@ -20,6 +20,8 @@ from ._lib import PGP_MODE_PLAIN, PGP_MODE_WEIGHTED
 
 _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int)
+PHYSICS_MAX_EDGES = 3 * 256 - 6          # PGP_PHYSICS_MAX_EDGES
+PHYSICS_EDGE_REACH_DEFAULT = 0.01        # PGP_PHYSICS_EDGE_REACH_DEFAULT
 
 
 def _fp(a):
@@ -1519,6 +1521,19 @@ class LcpScorer:
         _lib.check(self._lib.pgp_physics_shape_info(self._h, int(shape_id), _fp(hv), C.byref(nv), _fp(pl), C.byref(npl),
                                                     _fp(inertia), C.byref(margin)))
         return dict(verts=hv[:nv.value].copy(), planes=pl[:npl.value].copy(), inertia=inertia, margin=np.float32(margin.value))
+
+    def physics_shape_edges(self, shape_id):
+        """pgp_physics_shape_edges: the hull edges the device holds for a shape -> (k, 4) int32 rows (v0, v1, f0, f1),
+        indices into physics_shape_info's verts and planes, ascending by (v0, v1)."""
+        rows = np.zeros((PHYSICS_MAX_EDGES, 4), np.int32)
+        n = C.c_int(0)
+        _lib.check(self._lib.pgp_physics_shape_edges(self._h, int(shape_id), rows.ctypes.data_as(_i), C.byref(n)))
+        return rows[:n.value].copy()
+
+    def physics_set_edge_contacts(self, on=True, reach=PHYSICS_EDGE_REACH_DEFAULT):
+        """pgp_physics_set_edge_contacts: edge-edge contacts in every later settle, trace and MCTS search of this
+        context (off by default); reach in metres, > 0."""
+        _lib.check(self._lib.pgp_physics_set_edge_contacts(self._h, int(bool(on)), C.c_float(reach)))
 
     @staticmethod
     def _statics(statics, n):
