@@ -14,6 +14,7 @@
 // HBM-bound streaming: 2 or 4 B of depth (+1 B of mask) per pixel in, 12 B per kept pixel out.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "depth_pixel.h"
 
 namespace pgp {
@@ -41,16 +42,13 @@ __global__ __launch_bounds__(kBpThreads) void backproject(const void* __restrict
     keep = depth_ok(d, z_min, z_max);
   }
   const unsigned long long b = __ballot(keep);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
+  wave::block4_publish(s_wave, wave::lane() == 0, (uint32_t)__popcll(b));
   if (!WRITE) {
-    if (threadIdx.x == 0) block_ctr[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    if (threadIdx.x == 0) block_ctr[blockIdx.x] = wave::block4_total(s_wave);
     return;
   }
   if (!keep) return;
-  uint32_t rank = block_ctr[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) rank += s_wave[w];
+  const uint32_t rank = wave::block4_rank(s_wave, b, block_ctr[blockIdx.x]);
   if (rank >= cap) return;
   const int u = (int)(i / (size_t)cols), v = (int)(i - (size_t)u * cols);
   const float3 p = depth_point(u, v, d, fx, fy, cx, cy);   // depth_pixel.h

@@ -2,7 +2,7 @@
 //   ppfk::fit_plane / seg_seg / try_quadrilateral   the plane through three base points (base.cc:527-547, :731-745), distSegmentToSegment
 //                                                   (:81-148) and TryQuadrilateral (:415-464): base_select.hip (StoCS, pgp_base_invariants)
 //                                                   and super4pcs.hip (SelectQuadrilateral)
-//   v4dev::widest_triangle, wave_max / wave_min      SelectRandomTriangle (:377-410) with the counter-based draw: v4pcs.hip and super4pcs.hip
+//   v4dev::widest_triangle                           SelectRandomTriangle (:377-410) with the counter-based draw: v4pcs.hip and super4pcs.hip
 #pragma once
 
 #include "pgp_internal.h"
@@ -138,23 +138,6 @@ __device__ inline bool try_quadrilateral(const float4* __restrict__ P, int ids[4
 namespace v4dev {
 
 using namespace exact;
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o, 64);
-    k = other > k ? other : k;
-  }
-  return k;
-}
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long k) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const unsigned long long other = __shfl_xor(k, o, 64);
-    k = other < k ? other : k;
-  }
-  return k;
-}
 
 // The widest triangle among trials first, first + stride, ... < T of the attempt whose stream is `st`, first point p0:
 // key = how_wide bits << 32 | ~trial (how_wide > 0: its bits order as the floats do), 0 when no trial qualifies.  The greatest

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) void cluster_keys(const float* __restrict__ sc
   int base = 0;
   if (lane == 0) base = atomicAdd(m_out, __popcll(b));
   base = __builtin_amdgcn_readfirstlane(base);
-  if (pass) keys[base + __popcll(b & ((1ull << lane) - 1ull))] = key;
+  if (pass) keys[base + wave::rank_in(b, lane)] = key;
 }
 
 __device__ __forceinline__ float cof3(const float* a, int i, int j) {
@@ -482,7 +483,7 @@ __global__ __launch_bounds__(kGreedyThreads) void cluster_greedy_small(const uns
       const int a = my_pre >= 0 ? my_pre : dk ? c0 + (__ffsll((long long)dk) - 1) : c;
       if (c < m) assign[s_idx[c]] = s_idx[a];
       const int n0 = n_rep_s;
-      if ((kw >> lane) & 1ull) rep_out[n0 + __popcll(kw & ((1ull << lane) - 1ull))] = s_idx[c];
+      if ((kw >> lane) & 1ull) rep_out[n0 + wave::rank_in(kw, lane)] = s_idx[c];
       if (lane == 0) {
         keep[t] = kw;
         n_rep_s = n0 + __popcll(kw);
@@ -566,8 +567,7 @@ __global__ __launch_bounds__(kRoundThreads) void cluster_rounds(const float* __r
     }
     // the first candidate nobody has taken yet
     int* slot = &s_next[n_rep % 3];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) first_left = min(first_left, __shfl_xor(first_left, off, 64));
+    first_left = wave::min(first_left);
     if ((tid & 63) == 0 && first_left != 0x7FFFFFFF) atomicMin(slot, first_left);
     __syncthreads();
     r = *slot;
@@ -575,9 +575,7 @@ __global__ __launch_bounds__(kRoundThreads) void cluster_rounds(const float* __r
     if (n_rep == 8 && r != 0x7FFFFFFF) {
       if (tid == 0) s_left = 0;
       __syncthreads();
-      int left = __popc(~assigned & 0xFFFFu);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) left += __shfl_xor(left, off, 64);
+      const int left = wave::sum(__popc(~assigned & 0xFFFFu));
       if ((tid & 63) == 0) atomicAdd(&s_left, left);
       __syncthreads();
       if (s_left > m / 2) n_rep = max_rounds;   // reported as "not done" below

@@ -30,6 +30,7 @@
 // argmax (the lower id on ties).
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "depth_pixel.h"
 
 #include <algorithm>
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void cc_flatten(const int* __restrict__ p
   }
   __syncthreads();
   if (threadIdx.x == 0) {   // one pair of atomics per workgroup
-    const int nv = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3], nh = s_heads[0] + s_heads[1] + s_heads[2] + s_heads[3];
+    const int nv = wave::block4_total(s_valid), nh = wave::block4_total(s_heads);
     if (nv) atomicAdd(&counts[2], nv);
     if (nh) atomicAdd(&counts[1], nh);
   }
@@ -279,13 +280,6 @@ __global__ __launch_bounds__(kThreads) void cc_rank(const unsigned long long* __
   r.pixels = (int)(key >> 32);
   row_clear(&r);
   info[k] = r;
-}
-
-template <class T, class Op>
-__device__ __forceinline__ T wave_fold(T v, Op op) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // integer atomics on one row, in LDS or in global memory
@@ -348,15 +342,12 @@ __global__ __launch_bounds__(kThreads) void cc_table(const void* __restrict__ im
       const int id0 = __shfl(id, leader, 64);
       const bool in = id == id0;
       todo &= ~__ballot(in);
-      const int u_lo = wave_fold(in ? u : INT_MAX, [](int a, int b) { return min(a, b); });
-      const int u_hi = wave_fold(in ? u : INT_MIN, [](int a, int b) { return max(a, b); });
-      const int v_lo = wave_fold(in ? v : INT_MAX, [](int a, int b) { return min(a, b); });
-      const int v_hi = wave_fold(in ? v : INT_MIN, [](int a, int b) { return max(a, b); });
-      const unsigned z_lo = wave_fold(in ? zk : 0xFFFFFFFFu, [](unsigned a, unsigned b) { return min(a, b); });
-      const unsigned z_hi = wave_fold(in ? zk : 0u, [](unsigned a, unsigned b) { return max(a, b); });
+      const int u_lo = wave::min(in ? u : INT_MAX), u_hi = wave::max(in ? u : INT_MIN);
+      const int v_lo = wave::min(in ? v : INT_MAX), v_hi = wave::max(in ? v : INT_MIN);
+      const unsigned z_lo = wave::min(in ? zk : 0xFFFFFFFFu), z_hi = wave::max(in ? zk : 0u);
       long long t[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) t[k] = wave_fold(in ? s[k] : 0ll, [](long long a, long long b) { return a + b; });
+      for (int k = 0; k < 3; ++k) t[k] = wave::sum(in ? s[k] : 0ll);
       if (lane == leader) {
         if (id0 <= kLdsIds) row_fold(&s_row[id0 - 1], u_lo, u_hi, v_lo, v_hi, z_lo, z_hi, t);
         else row_fold(info + (id0 - 1), u_lo, u_hi, v_lo, v_hi, z_lo, z_hi, t);
@@ -386,13 +377,13 @@ __global__ __launch_bounds__(64) void cc_finish(const int* __restrict__ counts, 
       r.z_max = __uint_as_float(max(__float_as_uint(r.z_max), __float_as_uint(q.z_max)));
       for (int c = 0; c < 3; ++c) r.sum_um[c] += q.sum_um[c];
     }
-    r.u_min = wave_fold(r.u_min, [](int a, int b) { return min(a, b); });
-    r.u_max = wave_fold(r.u_max, [](int a, int b) { return max(a, b); });
-    r.v_min = wave_fold(r.v_min, [](int a, int b) { return min(a, b); });
-    r.v_max = wave_fold(r.v_max, [](int a, int b) { return max(a, b); });
-    r.z_min = __uint_as_float(wave_fold(__float_as_uint(r.z_min), [](unsigned a, unsigned b) { return min(a, b); }));
-    r.z_max = __uint_as_float(wave_fold(__float_as_uint(r.z_max), [](unsigned a, unsigned b) { return max(a, b); }));
-    for (int c = 0; c < 3; ++c) r.sum_um[c] = wave_fold(r.sum_um[c], [](long long a, long long b) { return a + b; });
+    r.u_min = wave::min(r.u_min);
+    r.u_max = wave::max(r.u_max);
+    r.v_min = wave::min(r.v_min);
+    r.v_max = wave::max(r.v_max);
+    r.z_min = __uint_as_float(wave::min(__float_as_uint(r.z_min)));
+    r.z_max = __uint_as_float(wave::max(__float_as_uint(r.z_max)));
+    for (int c = 0; c < 3; ++c) r.sum_um[c] = wave::sum(r.sum_um[c]);
   }
   if (lane != 0) return;
   info[k].u_min = r.u_min;

@@ -36,6 +36,7 @@
 #include <cstring>  // rocprim's texture_cache_iterator.hpp uses memset without including it
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void pair_rows(const float4* __restrict__ Qw, 
     }
     unsigned long long m = __ballot(hit);
     if (FILL && hit) {
-      uint32_t slot = base + running + __popcll(m & ((1ull << lane) - 1ull));
+      uint32_t slot = base + running + wave::rank_in(m, lane);
       if (2ull * slot < cap) out[2 * slot] = make_int2(j, i);          // pairs->emplace_back(j, i)
       if (2ull * slot + 1 < cap) out[2 * slot + 1] = make_int2(i, j);  // pairs->emplace_back(i, j)
     }
@@ -317,13 +318,11 @@ __global__ __launch_bounds__(256) void bq_match(CsBatchArgs a) {
   int first = -1;
   const bool any = t < a.total_q && bq_has_cell(a, t, b, &first);
   const unsigned long long m = __ballot(any);
-  if (lane == 0) s_wcnt[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t off = 0;
-  for (int w = 0; w < wave; ++w) off += s_wcnt[w];
-  const uint32_t n_any = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+  wave::block4_publish(s_wcnt, lane == 0, (uint32_t)__popcll(m));
+  const uint32_t off = wave::block4_offset(s_wcnt, wave, 0u);
+  const uint32_t n_any = wave::block4_total(s_wcnt);
   if (any) {
-    const uint32_t slot = off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    const uint32_t slot = off + wave::rank_in(m, lane);
     s_items[slot] = t;
     s_first[slot] = first;
     s_base[slot] = (unsigned short)b;   // at most 65535 bases per call
@@ -356,17 +355,11 @@ __global__ __launch_bounds__(256) void bq_match(CsBatchArgs a) {
   const uint32_t my_t = mine ? s_items[threadIdx.x] : 0u;
   const int my_b = mine ? (int)s_base[threadIdx.x] : 0;
   if (mine) found = bq_walk<false>(a, my_t, my_b, s_first[threadIdx.x], s_col[threadIdx.x], kept, 0u);
-  uint32_t incl = found;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
+  const uint32_t incl = wave::scan_incl(found, lane);
   __syncthreads();   // (s_wcnt is read above by every wave)
-  if (lane == 63) s_wcnt[wave] = incl;
-  __syncthreads();
+  wave::block4_publish(s_wcnt, lane == 63, incl);
   __shared__ uint32_t s_out0;
-  const uint32_t total = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+  const uint32_t total = wave::block4_total(s_wcnt);
   if (total == 0u) return;
   const bool one_base = s_b0 == s_b1;
   if (threadIdx.x == 0) {
@@ -375,8 +368,7 @@ __global__ __launch_bounds__(256) void bq_match(CsBatchArgs a) {
   }
   if (!one_base && found) atomicAdd(&a.base_cnt[my_b], found);
   __syncthreads();
-  uint32_t out0 = s_out0 + incl - found;
-  for (int w = 0; w < wave; ++w) out0 += s_wcnt[w];
+  const uint32_t out0 = wave::block4_offset(s_wcnt, wave, s_out0 + incl - found);
   if (found == 0u) return;
   if (found <= (uint32_t)kBqKeep) {
     const uint32_t i = my_t - a.bases[my_b].q_flat;

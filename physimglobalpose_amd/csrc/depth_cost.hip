@@ -14,6 +14,7 @@
 // at 640x480 it stays in L2).
 
 #include "pgp_internal.h"
+#include "wave.h"
 
 namespace pgp {
 
@@ -50,15 +51,11 @@ __global__ __launch_bounds__(256) void depth_cost(const float* __restrict__ obs,
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += gridDim.x * blockDim.x)
       tally(obs[i], r[i], thr, &ob, &re, &in);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    ob += __shfl_xor(ob, off, 64);
-    re += __shfl_xor(re, off, 64);
-    in += __shfl_xor(in, off, 64);
-  }
+  int c[3] = {ob, re, in};
+  wave::reduce(c, wave::Add{});   // the three butterflies in one loop
   __shared__ int s[4][3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { s[wave][0] = ob; s[wave][1] = re; s[wave][2] = in; }
+  if (lane == 0) { s[wave][0] = c[0]; s[wave][1] = c[1]; s[wave][2] = c[2]; }
   __syncthreads();
   if (threadIdx.x < 3) {
     int v = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];

@@ -47,6 +47,7 @@
 #include <mutex>
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "host_worker.h"
 #include "nn_prune.h"
 
@@ -251,15 +252,8 @@ __global__ __launch_bounds__(kScanThreads) void scan_tile_totals(const uint32_t*
   uint32_t sum = 0;
 #pragma unroll
   for (int k = 0; k < kScanItems; ++k) sum += v[k];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < kScanThreads / 64; ++w) t += s_wave[w];
-    tile_sums[blockIdx.x] = t;
-  }
+  wave::block4_publish(s_wave, wave::lane() == 0, wave::sum(sum));
+  if (threadIdx.x == 0) tile_sums[blockIdx.x] = wave::block4_total(s_wave);
 }
 
 // pass 3 (after scan_tile_sums has turned the totals into the tiles' offsets): the exclusive prefix of every word.
@@ -276,16 +270,9 @@ __global__ __launch_bounds__(kScanThreads) void scan_tiles(const uint32_t* in, u
   for (int k = 0; k < kScanItems; ++k) sum += v[k];
   // inclusive scan of `sum` across the wave, then across the 4 waves
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = sum;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    uint32_t t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  uint32_t wave_off = tile_offsets[blockIdx.x];
-  for (int w = 0; w < wave; ++w) wave_off += s_wave[w];
+  const uint32_t incl = wave::scan_incl(sum, lane);
+  wave::block4_publish(s_wave, lane == 63, incl);
+  const uint32_t wave_off = wave::block4_offset(s_wave, wave, tile_offsets[blockIdx.x]);
   uint32_t excl = wave_off + incl - sum;
   uint32_t o[kScanItems];
 #pragma unroll
@@ -314,12 +301,7 @@ __global__ __launch_bounds__(1024) void scan_tile_sums(uint32_t* __restrict__ ti
   for (int base = 0; base < n_tiles; base += 1024) {
     int i = base + threadIdx.x;
     uint32_t v = (i < n_tiles) ? tile_sums[i] : 0u;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      uint32_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
+    const uint32_t incl = wave::scan_incl(v, lane);   // (16 waves: the tail below is this kernel's own)
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     uint32_t wave_off = 0;
@@ -676,7 +658,7 @@ __global__ __launch_bounds__(64 * kNnWaves) void nn_compact(GridDesc g, const ui
       for (uint32_t a0 = 0; a0 < run.y; a0 += 64) {
         const bool k = a0 + lane < run.y && keep[run.x + a0 + lane] != 0;
         const unsigned long long m = __ballot(k);
-        if (k) cand_nn[s + done + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = cand[run.x + a0 + lane];
+        if (k) cand_nn[s + done + (uint32_t)wave::rank_in(m, lane)] = cand[run.x + a0 + lane];
         done += (uint32_t)__popcll(m);
       }
       if (lane == 0) {

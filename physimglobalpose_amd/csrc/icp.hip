@@ -56,6 +56,7 @@
 //     cells of edge max_corr, 27 cells per query, identical (d2, lowest j) results to the scan.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "icp_plan.h"
 
 #include <cfloat>
@@ -453,46 +454,6 @@ __device__ __attribute__((noinline)) bool converged_extra(const StopRules a, int
   return stop;
 }
 
-// Sum of one double per lane over the wave, the same value in every lane, on the DPP path: four steps inside
-// each row of 16 lanes (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror: two register
-// moves + one v_add_f64 each, no LDS), then the four row sums are read with v_readlane and added in row order.
-// A FIXED tree: ((r0 + r1) + r2) + r3 of balanced 16-lane trees -- every kernel of this file reduces with it,
-// so they agree bit for bit.  (__shfl_xor on doubles = 12 ds_bpermute round trips per value; the 17 sums of an
-// iteration spent ~5 us in them.)
-template <int CTRL>
-__device__ __forceinline__ double dpp_add_f64(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const int plo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-  const int phi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-  return v + __hiloint2double(phi, plo);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v = dpp_add_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v = dpp_add_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  v = dpp_add_f64<0x141>(v);   // row_half_mirror
-  v = dpp_add_f64<0x140>(v);   // row_mirror: every lane of a row holds the row's sum
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const double r0 = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
-  const double r1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
-  const double r2 = __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
-  const double r3 = __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
-  return ((r0 + r1) + r2) + r3;
-}
-
-// Inclusive prefix sum over the 64 lanes on the DPP path: four row_shr steps inside the rows of 16, then the row
-// totals are carried by row_bcast15 (rows 1, 3) and row_bcast31 (rows 2, 3) -- six additions, no LDS.  (__shfl_up
-// is a ds_bpermute round trip per step; the scans of the query sort and of the selection sit between barriers
-// where nothing hides it.)
-__device__ __forceinline__ unsigned wave_scan_incl_u32(unsigned v) {
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast15 into rows 1 and 3
-  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast31 into rows 2 and 3
-  return v;
-}
-
 constexpr int kPartStride = 32;   // doubles per (pose, block) in the partial sums of icp_sums_partial (kRedPlane + 1 = 29 used)
 
 // SPLIT = false: persistent kernel, all iterations of one pose in one workgroup (many poses).
@@ -695,7 +656,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_refine(IcpArgs a, const doubl
         unsigned mine = 0;
 #pragma unroll
         for (int r = 0; r < kSumR; ++r) mine += (b0 + kSumR * tid + r < a.n_src && key[r] == thr_key) ? 1u : 0u;
-        const unsigned incl = wave_scan_incl_u32(mine);
+        const unsigned incl = wave::scan_incl_dpp(mine);
         if (lane == 63) s_scan[wave] = incl;
         __syncthreads();
         unsigned rank = s_carry + incl - mine;
@@ -758,8 +719,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_refine(IcpArgs a, const doubl
 #pragma unroll
     for (int k = 0; k < kRedPlane; ++k)
       if (k < 16 || a.metric == 1)
-        acc[k] = wave_sum_f64(acc[k]);
-    e_acc = wave_sum_f64(e_acc);
+        acc[k] = wave::sum_dpp(acc[k]);
+    e_acc = wave::sum_dpp(e_acc);
     __syncthreads();
     if (lane == 0) {
       for (int k = 0; k < kRedPlane; ++k) s_red[wave * (kRedPlane + 1) + k] = acc[k];
@@ -896,8 +857,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_sums_partial(IcpArgs a, doubl
 #pragma unroll
   for (int k = 0; k < kRedPlane; ++k)
     if (k < 16 || a.metric == 1)
-      acc[k] = wave_sum_f64(acc[k]);
-  e_acc = wave_sum_f64(e_acc);
+      acc[k] = wave::sum_dpp(acc[k]);
+  e_acc = wave::sum_dpp(e_acc);
   if (lane == 0) {
     for (int k = 0; k < kRedPlane; ++k) s_red[wave * (kRedPlane + 1) + k] = acc[k];
     s_red[wave * (kRedPlane + 1) + kRedPlane] = e_acc;
@@ -1473,11 +1434,11 @@ __global__ __launch_bounds__(kSceneThreads) PGP_SCENE_ATTR void icp_scene_persis
         }
       }
 #pragma unroll
-      for (int k = 0; k < kNs; ++k) acc[k] = wave_sum_f64(acc[k]);
-      e_acc = wave_sum_f64(e_acc);
+      for (int k = 0; k < kNs; ++k) acc[k] = wave::sum_dpp(acc[k]);
+      e_acc = wave::sum_dpp(e_acc);
       double* Wu = z.W + ((size_t)pose * z.n_units16 + u) * kPartStride;
       {
-        // every lane holds every sum (wave_sum_f64): lane k stores sum k -- ONE store instruction over three lines instead
+        // every lane holds every sum (wave::sum_dpp): lane k stores sum k -- ONE store instruction over three lines instead
         // of 29 single-lane write-through stores, each a fabric write of its own
         double mine = lane == kRedPlane ? e_acc : 0.0;
 #pragma unroll
@@ -2049,7 +2010,7 @@ __device__ __forceinline__ void nn_all_queries(const IcpArgs& a, const NnLds& t,
     const unsigned c0 = w.x & 0xFFFFu, c1 = w.x >> 16, c2 = w.y & 0xFFFFu, c3 = w.y >> 16, c4 = w.z & 0xFFFFu, c5 = w.z >> 16,
                    c6 = w.w & 0xFFFFu, c7 = w.w >> 16;
     const unsigned mine = c0 + c1 + c2 + c3 + c4 + c5 + c6 + c7;
-    const unsigned incl = wave_scan_incl_u32(mine);
+    const unsigned incl = wave::scan_incl_dpp(mine);
     if ((tid & 63) == 63) sch->wave_sum[tid >> 6] = incl;
     __syncthreads();
     unsigned base = 0;
@@ -2384,7 +2345,7 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
       __syncthreads();
       const uint4 hv = reinterpret_cast<const uint4*>(hist)[tid];
       const unsigned mine = hv.x + hv.y + hv.z + hv.w;
-      const unsigned incl = wave_scan_incl_u32(mine);
+      const unsigned incl = wave::scan_incl_dpp(mine);
       if (lane == 63) s_scan[wave] = incl;
       __syncthreads();
       {
@@ -2506,7 +2467,7 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
         const int i = kSumR * tid + r;
         mine += (i < a.n_src && __float_as_uint(t.d2[i]) == thr_key) ? 1u : 0u;
       }
-      const unsigned incl = wave_scan_incl_u32(mine);
+      const unsigned incl = wave::scan_incl_dpp(mine);
       if (lane == 63) s_tie[wave] = incl;
       __syncthreads();
       rank = incl - mine;
@@ -2570,8 +2531,8 @@ __device__ __forceinline__ void icp_persist_body(const IcpArgs a) {   // BY VALU
     // (a wave without points holds zeros: its trees would return the same zeros)
 #pragma unroll
     for (int k = 0; k < kNs; ++k)
-      acc[k] = wave_sum_f64(acc[k]);
-    e_acc = wave_sum_f64(e_acc);
+      acc[k] = wave::sum_dpp(acc[k]);
+    e_acc = wave::sum_dpp(e_acc);
     }
     // (no barrier here: s_red was last read before the previous iteration's closing barriers)
     if (lane == 0) {

@@ -37,6 +37,7 @@
 // transcendental can disagree with the host at the gate boundary.
 
 #include "pgp_internal.h"
+#include "wave.h"
 
 #include <hip/hip_ext.h>
 
@@ -79,26 +80,6 @@ __device__ __forceinline__ float rot_row(float a, float b, float c, float n0, fl
 __device__ __forceinline__ float sqdist(float x, float y, float z, float4 p) {
   float dx = __fsub_rn(x, p.x), dy = __fsub_rn(y, p.y), dz = __fsub_rn(z, p.z);
   return __fadd_rn(__fmul_rn(dx, dx), __fadd_rn(__fmul_rn(dy, dy), __fmul_rn(dz, dz)));
-}
-
-// Sum over the 64 lanes in a FIXED association, on the DPP cross-lane path (no LDS traffic, unlike
-// __shfl_xor = ds_bpermute): four row-local steps (quad swaps, half-row and row mirrors -- after
-// them every lane of a 16-lane row holds the row total), then the four row totals (r0+r1)+(r2+r3).
-template <int CTRL>
-__device__ __forceinline__ float dpp_step(float v) {
-  const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true);
-  return __fadd_rn(v, __int_as_float(moved));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v = dpp_step<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = dpp_step<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = dpp_step<0x141>(v);  // row_half_mirror
-  v = dpp_step<0x140>(v);  // row_mirror
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return __fadd_rn(__fadd_rn(r0, r1), __fadd_rn(r2, r3));
 }
 
 // Cell lookup: candidate run [s, e) for position (x,y,z); empty outside the grid / in empty cells.
@@ -446,7 +427,7 @@ __global__ __launch_bounds__(64) void score_hypotheses(ScoreArgs a) {
         }
       }
       unsigned long long mask = __ballot(hit);
-      if (MODE == PGP_MODE_WEIGHTED && mask) wsum = wave_sum(wsum);  // fixed association, same every run
+      if (MODE == PGP_MODE_WEIGHTED && mask) wsum = wave::sum_dpp(wsum);  // fixed association, same every run
       if (lane == 0 && hb + u < h1)
         prow[2 * (size_t)(hb + u)] = make_uint2((uint32_t)__popcll(mask), __float_as_uint(MODE == PGP_MODE_WEIGHTED ? wsum : 0.f));
     }
@@ -469,23 +450,6 @@ __global__ __launch_bounds__(64) void score_hypotheses(ScoreArgs a) {
 // through LDS (store / 64-bit min) and read back by the owner.
 // Arithmetic per (query, candidate) pair is unchanged; results are identical.
 constexpr int kFlatCap = 1024;  // candidate slots per wave-iteration served by the flat path
-
-// Inclusive prefix sum over the 64 lanes on the DPP path: a shift-and-add scan inside each 16-lane
-// row (zeros are shifted in at the row start), then the row totals are carried across rows
-// (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_scan_step(uint32_t v) {
-  return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-}
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
-  v = dpp_scan_step<0x111, 0xF>(v);  // row_shr:1
-  v = dpp_scan_step<0x112, 0xF>(v);  // row_shr:2
-  v = dpp_scan_step<0x114, 0xF>(v);  // row_shr:4
-  v = dpp_scan_step<0x118, 0xF>(v);  // row_shr:8
-  v = dpp_scan_step<0x142, 0xA>(v);  // row_bcast:15 -> rows 1, 3
-  v = dpp_scan_step<0x143, 0xC>(v);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
 
 // NC chunks of 64 candidate slots of the wave's concatenated runs (see score_hypotheses_flat).
 // Slot w belongs to the owner with the greatest run start <= w.  Run starts are marked as bits
@@ -700,7 +664,7 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
     } else {
     // slot allocation in the concatenated run of the wave, in LANE order: an inclusive DPP scan of
     // the run lengths (no LDS); the total lands in an SGPR, so everything below branches scalar.
-    const uint32_t incl = wave_inclusive_scan(len);
+    const uint32_t incl = wave::scan_incl_dpp(len);
     const uint32_t W = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);   // >= 1
     const uint32_t pre = incl - len;
     // result of the candidate phase per owner lane (rlo): plain 0 / 1, weighted the scene id of the nearest
@@ -797,10 +761,10 @@ __device__ __forceinline__ void score_flat_body(const ScoreArgs& a, const float*
         __builtin_amdgcn_wave_barrier();
         const float4 v0 = *reinterpret_cast<const float4*>(&s_w[k][(pl & 15) * 4]);
         t = __fadd_rn(__fadd_rn(__fadd_rn(v0.x, v0.y), v0.z), v0.w);
-        t = dpp_step<0xB1>(t);   // quad_perm [1,0,3,2]
-        t = dpp_step<0x4E>(t);   // quad_perm [2,3,0,1]
-        t = dpp_step<0x141>(t);  // row_half_mirror
-        t = dpp_step<0x140>(t);  // row_mirror
+        t = wave::dpp_step<0xB1>(t);   // quad_perm [1,0,3,2]
+        t = wave::dpp_step<0x4E>(t);   // quad_perm [2,3,0,1]
+        t = wave::dpp_step<0x141>(t);  // row_half_mirror
+        t = wave::dpp_step<0x140>(t);  // row_mirror
         // a row nobody wrote holds an older group's values: its sum is 0
         t = ((wrote >> k) & 1u) != 0u ? t : 0.0f;
         __builtin_amdgcn_wave_barrier();
@@ -1449,19 +1413,12 @@ __global__ __launch_bounds__(256) void records_find(int n_h, int nQ, const float
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) m = fmaxf(m, v[k]);
-    float inc = m;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float o = __shfl_up(inc, off, 64);
-      if (lane >= off) inc = fmaxf(inc, o);
-    }
-    if (lane == 63) s_wmax[wave] = inc;
-    float run = __shfl_up(inc, 1, 64);   // running maximum of the tree scores before this thread's run
-    if (lane == 0) run = 0.f;
-    __syncthreads();
-    run = fmaxf(run, carry);
-    for (int w = 0; w < wave; ++w) run = fmaxf(run, s_wmax[w]);
-    carry = fmaxf(carry, fmaxf(fmaxf(s_wmax[0], s_wmax[1]), fmaxf(s_wmax[2], s_wmax[3])));
+    // the running maximum in front of this thread's run: prefix-max over the wave, the waves in front, the passes in front
+    const float inc = wave::scan_incl(m, lane, wave::Max{});
+    float excl = __shfl_up(inc, 1, 64);
+    if (lane == 0) excl = 0.f;
+    wave::block4_publish(s_wmax, lane == 63, inc);
+    const float run = wave::block4_offset(s_wmax, wave, fmaxf(carry, excl), wave::Max{});
     unsigned mask = 0;
     {
       float r = run;
@@ -1473,23 +1430,18 @@ __global__ __launch_bounds__(256) void records_find(int n_h, int nQ, const float
       }
     }
     const int cnt = __popc(mask);
-    int pre = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(pre, off, 64);
-      if (lane >= off) pre += o;
-    }
-    if (lane == 63) s_wcnt[wave] = pre;
-    __syncthreads();
-    int off = base + pre - cnt;
-    for (int w = 0; w < wave; ++w) off += s_wcnt[w];
-    base += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+    // where this thread's near-records go: exclusive count over the wave, the waves in front, the passes in front
+    const int ic = wave::scan_incl(cnt, lane);
+    wave::block4_publish(s_wcnt, lane == 63, ic);
+    int at = wave::block4_offset(s_wcnt, wave, base + ic - cnt);
     while (mask) {
       const int k = __ffs(mask) - 1;
       mask &= mask - 1;
-      if (off < kRecordCap) list[off] = lo + k;
-      ++off;
+      if (at < kRecordCap) list[at] = lo + k;
+      ++at;
     }
+    base += wave::block4_total(s_wcnt);
+    carry = fmaxf(carry, wave::block4_total(s_wmax, wave::Max{}));   // (a maximum: the same whatever the order)
     __syncthreads();   // s_wmax / s_wcnt are rewritten by the next pass
   }
   if (tid == 0) *count = min(base, kRecordCap);

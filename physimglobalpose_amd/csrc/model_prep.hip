@@ -29,6 +29,7 @@
 
 #include "exact_f32.h"
 #include "pgp_internal.h"
+#include "wave.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -161,15 +162,6 @@ __device__ __forceinline__ unsigned long long x_key(float x, int index) {
 // (key 0: nothing left to pick -- only a cloud of non-finite points gets there -- reads as index 0, never out of bounds)
 __device__ __forceinline__ int key_index(unsigned long long key) { return key ? (int)(~(unsigned int)key) : 0; }
 
-__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long key) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = __shfl_xor(key, m, 64);
-    key = o > key ? o : key;
-  }
-  return key;
-}
-
 struct WaveRec {   // what a wave leaves per pick: its best key and that point
   unsigned long long key;
   float x, y, z, pad;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(kResThreads) void fps_resident(const float4* __rest
   int bank = 0;
   // the pick of one round: every lane's candidate {key, point} -> the workgroup's best, in every lane
   const auto block_best = [&](unsigned long long key, float bx, float by, float bz, float& cx, float& cy, float& cz) {
-    const unsigned long long wk = wave_max_key(key);
+    const unsigned long long wk = wave::max(key);
     if (key == wk && (key != 0ull || lane == 0)) s_rec[bank][wave] = WaveRec{wk, bx, by, bz, 0.f, {0.f, 0.f}};
     __syncthreads();
     unsigned long long best = 0ull;
@@ -272,7 +264,7 @@ __global__ __launch_bounds__(kResThreads) void fps_resident(const float4* __rest
 
 // the workgroup's max of one key per thread, in every thread (kMultiThreads threads; s: kMultiWaves words of LDS)
 __device__ __forceinline__ unsigned long long multi_block_max(unsigned long long key, unsigned long long* s) {
-  const unsigned long long wk = wave_max_key(key);
+  const unsigned long long wk = wave::max(key);
   if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = wk;
   __syncthreads();
   unsigned long long best = s[0];

@@ -2,6 +2,7 @@
 // No CPU fallback anywhere: every scoring entry point ends in a HIP kernel launch or an error.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "match_plan.h"
 
 #include <chrono>
@@ -1423,26 +1424,14 @@ __global__ __launch_bounds__(256) void records_walk(int n, const float* __restri
     float m = 0.f;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) m = fmaxf(m, v[k]);
-    float inc = m;
-    int ik = my_kept;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float o = __shfl_up(inc, off, 64);
-      const int ok = __shfl_up(ik, off, 64);
-      if (lane >= off) {
-        inc = fmaxf(inc, o);
-        ik += ok;
-      }
-    }
+    // the running maximum in front of this thread's run: prefix-max over the wave, the waves in front, the passes in front
+    const float inc = wave::scan_incl(m, lane, wave::Max{});
     float excl = __shfl_up(inc, 1, 64);
     if (lane == 0) excl = 0.f;
-    if (lane == 63) {
-      s_wmax[wave] = inc;
-      s_wkept[wave] = ik;
-    }
-    __syncthreads();
-    float run = fmaxf(carry, excl);
-    for (int w = 0; w < wave; ++w) run = fmaxf(run, s_wmax[w]);
+    const int ik = wave::scan_incl(my_kept, lane);
+    if (lane == 63) s_wkept[wave] = ik;
+    wave::block4_publish(s_wmax, lane == 63, inc);
+    float run = wave::block4_offset(s_wmax, wave, fmaxf(carry, excl), wave::Max{});
     unsigned mask = 0u;
     int c = 0;
 #pragma unroll
@@ -1452,16 +1441,10 @@ __global__ __launch_bounds__(256) void records_walk(int n, const float* __restri
         mask |= 1u << k;
         ++c;
       }
-    int ic = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(ic, off, 64);
-      if (lane >= off) ic += o;
-    }
-    if (lane == 63) s_wcnt[wave] = ic;
-    __syncthreads();
-    int at = base + ic - c;
-    for (int w = 0; w < wave; ++w) at += s_wcnt[w];
+    // where this thread's records go: exclusive count over the wave, the waves in front, the passes in front
+    const int ic = wave::scan_incl(c, lane);
+    wave::block4_publish(s_wcnt, lane == 63, ic);
+    int at = wave::block4_offset(s_wcnt, wave, base + ic - c);
 #pragma unroll
     for (int k = 0; k < kPer; ++k)
       if (mask & (1u << k)) {
@@ -1471,10 +1454,10 @@ __global__ __launch_bounds__(256) void records_walk(int n, const float* __restri
         }
         ++at;
       }
-    base += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-    kept += s_wkept[0] + s_wkept[1] + s_wkept[2] + s_wkept[3];
-    carry = fmaxf(fmaxf(fmaxf(carry, s_wmax[0]), fmaxf(s_wmax[1], s_wmax[2])), s_wmax[3]);
-    __syncthreads();
+    base += wave::block4_total(s_wcnt);
+    kept += wave::block4_total(s_wkept);
+    carry = fmaxf(carry, wave::block4_total(s_wmax, wave::Max{}));   // (a maximum: the same whatever the order)
+    __syncthreads();   // s_wmax / s_wcnt / s_wkept are rewritten by the next pass
   }
   if (tid == 0) {
     list[0] = base;
@@ -1610,8 +1593,7 @@ __global__ __launch_bounds__(64) void sample_quads_kernel(const uint32_t* __rest
   const int b = blockIdx.x, lane = threadIdx.x;
   uint32_t off = 0;
   for (int i = lane; i < b; i += 64) off += min(base_start[i + 1] - base_start[i], (uint32_t)cap);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) off += __shfl_xor(off, o, 64);
+  off = wave::sum(off);
   const uint32_t nq = base_start[b + 1] - base_start[b];
   const int4 ids = base_ids[b];
   if (nq < (uint32_t)cap) {

@@ -89,6 +89,7 @@
 #include <utility>
 
 #include "pgp_internal.h"
+#include "wave.h"
 
 using namespace pgp;
 
@@ -398,9 +399,8 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
         if (k == 4 + wv) base1 = cnt;
         cnt += s_wc[k];
       }
-      const unsigned long long lt = (1ull << lane) - 1ull;
-      if (fl[0]) { const int at = base0 + __popcll(b0 & lt); s_cp[at] = cp[0]; s_cn[at] = cn[0]; }
-      if (fl[1]) { const int at = base1 + __popcll(b1 & lt); s_cp[at] = cp[1]; s_cn[at] = cn[1]; }
+      if (fl[0]) { const int at = base0 + wave::rank_in(b0, lane); s_cp[at] = cp[0]; s_cn[at] = cn[0]; }
+      if (fl[1]) { const int at = base1 + wave::rank_in(b1, lane); s_cp[at] = cp[1]; s_cn[at] = cn[1]; }
       __syncthreads();
       if constexpr (EDGES) {
         // 3e: edge-edge candidates, appended after the vertex candidates
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
               if (k < wv) at += s_wc[k];
               na += s_wc[k];
             }
-            if (act) s_ae[side][at + __popcll(ba & lt)] = (unsigned short)e;
+            if (act) s_ae[side][at + wave::rank_in(ba, lane)] = (unsigned short)e;
             __syncthreads();
           }
           n_act[side] = na;
@@ -542,7 +542,7 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
             if (k < wv) at += s_wc[k];
             cnt += s_wc[k];
           }
-          at += __popcll(bo & lt);
+          at += wave::rank_in(bo, lane);
           if (ok && at < 2 * PT) { s_cp[at] = ecp; s_cn[at] = ecn; }   // past the capacity: dropped, in pair order
           if (cnt > 2 * PT) cnt = 2 * PT;
           __syncthreads();

@@ -26,6 +26,7 @@
 // distance from the float coefficients, dist < threshold zeroes the pixel.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "exact_f32.h"
 #include "eigen33.h"
 
@@ -107,12 +108,6 @@ __global__ __launch_bounds__(kThreads) void plane_candidates(const float* __rest
   valid[i] = ok ? 1 : 0;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // grid (chunk blocks, candidate blocks): partial penalty and inlier count per (candidate, chunk block)
 __global__ __launch_bounds__(kThreads) void plane_score(const float* __restrict__ xyz, int n, int n_chunks,
                                                         const float4* __restrict__ coeff, int m, float thr,
@@ -155,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void plane_score(const float* __restrict_
         s += in[k] ? (double)fminf(d, thr) : 0.0;
         cnt += __popcll(__ballot(in[k] && d <= thr));
       }
-      s = wave_sum_d(s);
+      s = wave::sum(s);
       if (lane == 0) {   // chunk order within the wave's own accumulator
         s_pen[wave][c] += s;
         s_cnt[wave][c] += cnt;
@@ -308,11 +303,10 @@ __global__ __launch_bounds__(kSelThreads) void plane_select(SelArgs a) {
 
 // the workgroup's sum in a fixed order: lanes by the xor butterfly, then waves 0..3
 __device__ __forceinline__ double block_sum_d(double v, double* s_w) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  v = wave::sum(v);
+  __syncthreads();   // s_w may still be read from the call before
+  wave::block4_publish(s_w, wave::lane() == 0, v);
+  return wave::block4_total(s_w);   // ((s0 + s1) + s2) + s3
 }
 
 // refit pass 1: per chunk, {count, sum x, sum y, sum z} of the chosen sample's strict inliers
@@ -351,7 +345,7 @@ __device__ __forceinline__ void wave_sum_parts(const double* __restrict__ part, 
 #pragma unroll
     for (int k = 0; k < K; ++k) out[k] += part[K * (size_t)b + k];
 #pragma unroll
-  for (int k = 0; k < K; ++k) out[k] = wave_sum_d(out[k]);
+  for (int k = 0; k < K; ++k) out[k] = wave::sum(out[k]);
 }
 
 // {count, centroid}: run by a whole wave
@@ -428,10 +422,9 @@ __global__ __launch_bounds__(kThreads) void plane_inliers(const float* __restric
     if (mask) mask[i] = in ? 1 : 0;
   }
   const unsigned long long b = __ballot(in);
-  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
+  wave::block4_publish(s_n, wave::lane() == 0, __popcll(b));
   if (threadIdx.x == 0) {
-    const int s = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const int s = wave::block4_total(s_n);
     if (s) atomicAdd(n_inl, s);
     if (blockIdx.x == 0) {
       out_coeff[0] = q.x;
@@ -475,10 +468,9 @@ __global__ __launch_bounds__(kThreads) void plane_mask_depth(void* __restrict__ 
   }
   if (!n_masked) return;
   const unsigned long long b = __ballot(hit);
-  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
+  wave::block4_publish(s_n, wave::lane() == 0, __popcll(b));
   if (threadIdx.x == 0) {
-    const int s = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const int s = wave::block4_total(s_n);
     if (s) atomicAdd(n_masked, s);
   }
 }

@@ -40,6 +40,7 @@
 //                          every kept slot, the full count.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "ppf_key.h"
 
 #include <algorithm>
@@ -161,11 +162,6 @@ __device__ __forceinline__ int load_acc(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past the CU's vector cache
 }
 
-__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 template <bool kLds>
 __global__ __launch_bounds__(kThreads) void ppf_vote_kernel(VoteArgs a) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -199,12 +195,7 @@ __global__ __launch_bounds__(kThreads) void ppf_vote_kernel(VoteArgs a) {
         }
       }
       // the wave's rows are walked as ONE list, 64 consecutive pairs per step (row lengths vary by orders of magnitude)
-      int inc = cnt;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-      }
+      const int inc = wave::scan_incl(cnt, lane);
       const int total = __shfl(inc, 63);
       if (total == 0) continue;
       w_pref[lane] = inc;
@@ -241,11 +232,7 @@ __global__ __launch_bounds__(kThreads) void ppf_vote_kernel(VoteArgs a) {
               ((unsigned long long)(unsigned)load_acc<kLds>(acc + c) << 32) | (0xFFFFFFFFu - (unsigned)c);
           if (key < prev && key > best) best = key;
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-          const unsigned long long o = shfl_xor64(best, m);
-          best = o > best ? o : best;
-        }
+        best = wave::max(best);
         if (lane == 0) red[wave] = best;
         __syncthreads();
         best = 0;
@@ -315,7 +302,7 @@ __global__ __launch_bounds__(kEmitThreads) void ppf_emit_kernel(EmitArgs a) {
     const int2 s = i < a.n_slots ? a.slots[i] : make_int2(0, -1);
     const bool v = s.x > 0;
     const unsigned long long m = __ballot(v);
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    const int rank = wave::rank_in(m, lane);
     if (lane == 0) wsum[wave] = __popcll(m);
     __syncthreads();
     int before = 0, total = 0;

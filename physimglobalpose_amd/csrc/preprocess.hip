@@ -23,6 +23,7 @@
 #include <cstring>  // rocprim's texture_cache_iterator.hpp uses memset without including it
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "exact_f32.h"
 
 #include <rocprim/rocprim.hpp>
@@ -48,11 +49,8 @@ __global__ __launch_bounds__(256) void bbox_partial(const float* __restrict__ xy
     mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
     mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
   }
-  for (int k = 0; k < 3; ++k)
-    for (int off = 32; off >= 1; off >>= 1) {
-      mn[k] = fminf(mn[k], __shfl_xor(mn[k], off, 64));
-      mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off, 64));
-    }
+  wave::reduce(mn, wave::Min{});
+  wave::reduce(mx, wave::Max{});
   if ((threadIdx.x & 63) == 0)
     for (int k = 0; k < 3; ++k) {
       s_mn[k][threadIdx.x >> 6] = mn[k];
@@ -178,8 +176,7 @@ __global__ __launch_bounds__(64) void pose_hausdorff(const float4* __restrict__ 
       mind = dist < FLT_MAX ? dist : FLT_MAX;
     }
     const float for_max = ii < n_hull ? mind : 0.f;
-    float wmax = for_max;
-    for (int off = 32; off >= 1; off >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, off, 64));
+    const float wmax = wave::max(for_max);
     mx = wmax > mx ? wmax : mx;
     // mean_distance += min_distance, in hull order
     const int cnt = min(64, n_hull - base);

@@ -19,6 +19,7 @@
 // the square root is exact_f32.h's (the double root rounded once).
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "exact_f32.h"
 
 namespace pgp {
@@ -49,16 +50,13 @@ __global__ __launch_bounds__(kSegThreads) void filter_compact(FilterArgs a) {
   const int i = blockIdx.x * kSegThreads + threadIdx.x;
   const bool keep = i < a.n && a.counts[i] > a.min_neighbors;   // PCL 1.7: `k <= min_pts_radius_` -> outlier
   const unsigned long long b = __ballot(keep);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
+  wave::block4_publish(s_wave, wave::lane() == 0, (uint32_t)__popcll(b));
   if (!WRITE) {
-    if (threadIdx.x == 0) a.block_ctr[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    if (threadIdx.x == 0) a.block_ctr[blockIdx.x] = wave::block4_total(s_wave);
     return;
   }
   if (!keep) return;
-  uint32_t rank = a.block_ctr[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) rank += s_wave[w];
+  const uint32_t rank = wave::block4_rank(s_wave, b, a.block_ctr[blockIdx.x]);
   if (rank >= a.cap) return;
   const float px = a.xyz[3 * (size_t)i], py = a.xyz[3 * (size_t)i + 1], pz = a.xyz[3 * (size_t)i + 2];
   a.out_xyz[3 * (size_t)rank] = px;

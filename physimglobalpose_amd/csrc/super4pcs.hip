@@ -26,6 +26,7 @@
 // a record of the list's base edge that base_records gathers from the scene.  The rules are in include/pgp.h.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "base_device.h"
 
 #include <algorithm>
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
   const V3 p0 = ld3(P, i0);
   const float DD = mul(D, D);
   // the widest triangle (base_device.h): trials strided over the workgroup
-  unsigned long long best = v4dev::wave_max(v4dev::widest_triangle(P, un, st, T, DD, p0, tid, kBaseThreads));
+  unsigned long long best = wave::max(v4dev::widest_triangle(P, un, st, T, DD, p0, tid, kBaseThreads));
   if (lane == 0) s_max[wave] = best;
   __syncthreads();
   best = s_max[0];
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(kBaseThreads) void wide_bases(const float4* __restr
       }
     }
   }
-  mine = v4dev::wave_min(mine);
+  mine = wave::min(mine);
   if (lane == 0) s_min[wave] = mine;
   __syncthreads();
   if (wave != 0) return;
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256) void pair_lists(const float4* __restrict__ Q, 
       if (m == 0ull) continue;
       const uint32_t cnt = (uint32_t)__popcll(m);
       if (FILL) {
-        const uint32_t at = __shfl(mine, k, 64) + 2u * (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t at = __shfl(mine, k, 64) + 2u * (uint32_t)wave::rank_in(m, lane);
         if (hit) {
           out[at] = make_int2(j, i);        // pairs->emplace_back(j, i)
           out[at + 1] = make_int2(i, j);    // pairs->emplace_back(i, j)
@@ -253,7 +254,6 @@ __global__ __launch_bounds__(256) void pair_lists_gated(const float4* __restrict
   const bool has = lane < kn;   // this lane keeps list k0 + lane
   const size_t my_row = (size_t)(k0 + lane) * (size_t)n + (size_t)i;
   uint32_t mine = (FILL && has) ? list_off[k0 + lane] + row_start[my_row] : 0u;
-  const unsigned long long below = (1ull << lane) - 1ull;
   const V3 zero = {0.f, 0.f, 0.f}, no_rgb = {-1.f, -1.f, -1.f};
   const V3 qi = ld3(Q, i);
   const V3 ni = Qn ? ld3(Qn, i) : zero;
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void pair_lists_gated(const float4* __restrict
       const unsigned long long mf = __ballot(fwd), mb = __ballot(bwd);
       if ((mf | mb) == 0ull) continue;
       if (FILL) {
-        uint32_t at = __shfl(mine, k, 64) + (uint32_t)__popcll(mf & below) + (uint32_t)__popcll(mb & below);
+        uint32_t at = __shfl(mine, k, 64) + (uint32_t)wave::rank_in(mf, lane) + (uint32_t)wave::rank_in(mb, lane);
         if (fwd) out[at++] = make_int2(j, i);   // pairs->emplace_back(j, i)
         if (bwd) out[at] = make_int2(i, j);     // pairs->emplace_back(i, j)
       }

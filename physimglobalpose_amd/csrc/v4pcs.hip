@@ -25,6 +25,7 @@
 // Plain launches, no waiting between workgroups.  Every result is an integer.
 
 #include "pgp_internal.h"
+#include "wave.h"
 #include "base_device.h"
 
 #include <algorithm>
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, 
   const float DD = mul(D, D);
   // the widest triangle (base_device.h): trials strided over the lanes
   unsigned long long best = widest_triangle(P, un, st, T, DD, p0, lane, 64);
-  best = wave_max(best);
+  best = wave::max(best);
   int4 out = make_int4(-1, -1, -1, -1);
   int ok = 0;
   float d[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(64) void tetra_bases(const float4* __restrict__ P, 
         bestv = key > bestv ? key : bestv;
       }
     }
-    bestv = wave_max(bestv);
+    bestv = wave::max(bestv);
     if (bestv != 0ull) {
       const int k = (int)(0xFFFFFFFFu - (unsigned)(bestv & 0xFFFFFFFFull));
       const int i3 = (int)(sample_variate(st, 1 + 2 * T + k) % un);
@@ -152,12 +153,9 @@ __global__ __launch_bounds__(64) void join_rows(const unsigned long long* __rest
           } else {
             // this lane's quads follow those of the lower lanes (= the lower words)
             const unsigned pc = (unsigned)__popcll(x);
-            unsigned incl = pc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-              const unsigned other = __shfl_up(incl, o, 64);
-              if (lane >= o) incl += other;
-            }
+            // the whole wave is here: the block is one wave, and the trip counts, the `continue` above and the return below
+            // depend on shuffled words, ballots and `off` alone, which are the same in every lane
+            const unsigned incl = wave::scan_incl(pc, lane);
             const unsigned total = __shfl(incl, 63, 64);
             unsigned long long at = off + (incl - pc);
             for (; x && at < cap; x &= x - 1ull, ++at) out[at] = make_int4(v1, v2, v3, lane * 64 + __builtin_ctzll(x));
@@ -169,8 +167,7 @@ __global__ __launch_bounds__(64) void join_rows(const unsigned long long* __rest
     }
   }
   if (!FILL) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) count += __shfl_xor(count, o, 64);
+    count = wave::sum(count);
     if (lane == 0) row_cnt[(size_t)b * N + v1] = count;
   }
 }

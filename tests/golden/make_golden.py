@@ -209,7 +209,7 @@ def morton_order(Q):
 
 
 def tree_sum_score(wq, order):
-    """Emulates the association of the HIP kernel's weighted sum (csrc/lcp_score.hip: wave_sum DPP
+    """Emulates the association of the HIP kernel's weighted sum (csrc/wave.h: sum_dpp, the DPP
     tree per 64 lanes, 4 waves per 256-point tile added in order, tiles added in order) for per-
     model-point registered weights wq (0 where nothing registered).  Used only to PICK a fixture on
     which a tree-summed arg-max differs from the reference's sequential one."""
