@@ -1019,7 +1019,8 @@ int pgp_remove_table(pgp_ctx* ctx, void* image, int raw16, int rows, int cols, c
  *              0, 1, ... in that order (further rows of info are not written).  ids[u cols + v] = the id of the
  *              pixel's component, 0 for invalid pixels, unkept components and kept ones beyond cap.
  *   counts     [0] kept components (the full number, it may exceed cap), [1] components of any size, [2] valid pixels.
- * Touching objects are one component: that is the method's limit, not an error.
+ * Touching objects are one component: that is the method's limit, not an error (pgp_depth_objects below cuts them
+ * along the concave crease between them).
  * tolerance <= 0 or not finite, a connectivity other than 4 or 8, min_pixels < 1, cap < 0, cap > 0 without info,
  * rows * cols > 2^30 and outputs that overlap the inputs or each other are PGP_EINVAL; rows == 0 or cols == 0 is PGP_OK
  * with zero counts. */
@@ -1081,6 +1082,80 @@ int pgp_assign_masks_to_components(pgp_ctx* ctx, const int* ids, const void* cla
 int pgp_assign_masks_to_components_device(pgp_ctx* ctx, const int* d_ids, const void* d_classes, int class_bytes, int rows,
                                           int cols, const int* class_values, int n_objects, int* component,
                                           int* pixels_in, int* pixels_total, int* group, void* stream);
+
+/* ---- Touching objects: the concave-crease cut (csrc/depth_crease.hip) ----
+ * Where two objects touch, the depth image has no jump, but the surface has a concave crease; one rigid, roughly convex
+ * object shows convex edges.  This is the local-convexity criterion of LCCP (Stein et al. 2014) on the pixel grid, as the
+ * edge maps of Tateno et al. 2015: surface normals of the organised image, a concavity test between pixels a few steps
+ * apart, pgp_depth_components on what is left (the cores), and a few passes that hand the crease pixels back.  The
+ * reference has no such step, so nothing of its bits is pinned; the rules, all of them:
+ *   points     pixels, validity (the caller's mask included), z_min / z_max and tolerance are pgp_depth_components',
+ *              taken from a pgp_components_options.
+ *   floats     every float operation is rounded on its own; a three-term sum is (a + b) + c; divide and square root
+ *              are IEEE.  dist2(p, q) = ((dx dx + dy dy) + dz dz).
+ *   reach      the pixel q at offset (du, dv) is reachable from p iff both are valid, k = max(|du|, |dv|) >= 1 and
+ *              dist2(p, q) <= t * t with t = tolerance * (float)k (float products).
+ *   raw normal (s = normal_step) the horizontal tangent h is p(u, v + s) - p(u, v - s) when both are reachable,
+ *              p(u, v + s) - p when only the first is, p - p(u, v - s) when only the second is; with neither the pixel
+ *              has no normal.  The vertical tangent g likewise from p(u +- s, v).  m = g x h (it points towards the
+ *              camera), z = (mx mx + my my) + mz mz; the normal is m / sqrt(z) when z > 0, else there is none.
+ *   smoothed   (w = smooth_radius) only for a pixel with a raw normal: acc = (+0, +0, +0); for du = -w .. w (outer) and
+ *              dv = -w .. w (inner) the raw normal of (u + du, v + dv) is added component-wise when (du, dv) == (0, 0)
+ *              or that pixel is reachable and has a raw normal; normalised as above, a zero sum is no normal.
+ *   crease     (c = crease_step) for a pixel i with a smoothed normal n_i and each of the eight pixels j at (+-c, 0),
+ *              (0, +-c), (+-c, +-c) that is reachable and has a smoothed normal: the pair is concave iff
+ *              (n_j - n_i) . (p_j - p_i) < 0, and a concave pair's penalty is 1 - n_i . n_j (dots as three-term sums),
+ *              any other pair's 0.  i is a crease pixel iff its largest penalty > concavity (strict).
+ *   cores      pgp_depth_components with mask = (caller's mask) AND (not crease): roots is that labelling (-1 on crease
+ *              and invalid pixels); selection, ranking and the ids 1 .. min(kept, cap) are decided on the cores.
+ *   growing    grow_passes Jacobi passes, each reading the ids of the one before: a valid pixel with id 0 (a crease
+ *              pixel, or one of an unkept core or of one beyond cap) takes the smallest non-zero id among its four
+ *              neighbours that are reachable (k = 1), or stays 0.
+ *   table      the info rows keep the cores' order and root; pixels, bounding box, depth range and sum_um describe the
+ *              grown ids, folded in integers as in pgp_depth_components.
+ *   counts     [0] kept cores, [1] cores of any size, [2] valid pixels, [3] crease pixels, [4] pixels labelled by growing.
+ * Limits: a convex contact -- two boxes flush side by side with coplanar tops -- has no concave crease and is not cut;
+ * a strongly concave single object (the inside of a mug, a bowl) is cut.
+ * Refused (PGP_EINVAL): whatever pgp_depth_components refuses, normal_step or crease_step outside 1..8, smooth_radius
+ * outside 0..4, grow_passes outside 0..64, concavity negative or not finite.  rows == 0 or cols == 0 is PGP_OK with zero
+ * counts. */
+typedef struct pgp_crease_options {
+  int   normal_step;     /* 3: pixels between a pixel and the two its tangent is taken from */
+  int   smooth_radius;   /* 2: the normals are summed over (2 w + 1)^2 pixels */
+  int   crease_step;     /* 4: pixels between the two ends of a tested pair */
+  float concavity;       /* 0.06: a concave pair with 1 - n_i . n_j above this is a crease (about 20 degrees) */
+  int   grow_passes;     /* 12 */
+} pgp_crease_options;
+int pgp_crease_default_options(pgp_crease_options* opt);
+
+/* The smoothed normals: normals[(u cols + v) 4 ..] = (nx, ny, nz, 1) for a pixel that has one, (0, 0, 0, 0) for any
+ * other.  image, mask, K as in pgp_depth_components.  Host pointers, synchronous; the _device forms of all three calls
+ * take DEVICE arrays, are enqueued on `stream` with no host synchronisation and are sized by rows * cols, so they chain
+ * behind pgp_mask_plane_depth_device; the workspace lives in the context and grows on demand. */
+int pgp_depth_normals(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease, const void* image,
+                      int raw16, const unsigned char* mask, int rows, int cols, const float K[9], float* normals);
+int pgp_depth_normals_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                             const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols,
+                             const float K[9], float* d_normals, void* stream);
+
+/* keep[u cols + v] = 1 for a pixel that is valid (the caller's mask included) and not a crease pixel, else 0: the byte
+ * mask pgp_depth_components and pgp_segment_from_depth_device read.  *n_crease = the crease pixels. */
+int pgp_depth_crease_mask(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                          const void* image, int raw16, const unsigned char* mask, int rows, int cols, const float K[9],
+                          unsigned char* keep, int* n_crease);
+int pgp_depth_crease_mask_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                                 const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols,
+                                 const float K[9], unsigned char* d_keep, int* d_n_crease, void* stream);
+
+/* The whole chain.  roots, ids (nullable), info (nullable when cap == 0) as in pgp_depth_components; counts[5].  The
+ * device form always runs all grow_passes passes: nothing is read home in between. */
+int pgp_depth_objects(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease, const void* image,
+                      int raw16, const unsigned char* mask, int rows, int cols, const float K[9], int* roots, int* ids,
+                      pgp_component_info* info, int cap, int counts[5]);
+int pgp_depth_objects_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                             const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols,
+                             const float K[9], int* d_roots, int* d_ids, pgp_component_info* d_info, int cap,
+                             int* d_counts, void* stream);
 
 /* Replaces UCTState::computeCost (PPE/hypothesis_verification/mcts/UCTState.cpp:93-116) for n
  * rendered depth images against one observed image (all rows x cols float, row-major, metres):

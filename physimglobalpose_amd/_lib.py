@@ -86,6 +86,11 @@ class ComponentsOptions(C.Structure):
                 ("min_pixels", C.c_int), ("max_pixels", C.c_int)]
 
 
+class CreaseOptions(C.Structure):
+    _fields_ = [("normal_step", C.c_int), ("smooth_radius", C.c_int), ("crease_step", C.c_int), ("concavity", C.c_float),
+                ("grow_passes", C.c_int)]
+
+
 class ComponentInfo(C.Structure):
     _fields_ = [("root", C.c_int), ("pixels", C.c_int), ("u_min", C.c_int), ("u_max", C.c_int), ("v_min", C.c_int),
                 ("v_max", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float), ("sum_um", C.c_longlong * 3)]
@@ -328,6 +333,21 @@ SIGNATURES = {
                                                  _i, _i, _i, _i]),
     "pgp_assign_masks_to_components_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _i,
                                                         C.c_int, _i, _i, _i, _i, C.c_void_p]),
+    "pgp_crease_default_options": (C.c_int, [C.POINTER(CreaseOptions)]),
+    # ctx, options, crease options, image, raw16, mask, rows, cols, K, outputs ...
+    "pgp_depth_normals": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p]),
+    "pgp_depth_normals_device": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p, C.c_void_p]),
+    "pgp_depth_crease_mask": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p, _i]),
+    "pgp_depth_crease_mask_device": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgp_depth_objects": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _i]),
+    "pgp_depth_objects_device": (C.c_int, [C.c_void_p, C.POINTER(ComponentsOptions), C.POINTER(CreaseOptions), C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_int, C.c_int, _f, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p, C.c_void_p]),
     "pgp_ppf_default_options": (C.c_int, [C.POINTER(PpfOptions)]),
     "pgp_set_ppf_model": (C.c_int, [C.c_void_p, _f, _f, C.c_int]),
     "pgp_ppf_vote_device": (C.c_int, [C.c_void_p, C.POINTER(PpfOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

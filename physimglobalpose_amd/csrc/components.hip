@@ -23,6 +23,8 @@
 //               ids and folds bounding box, depth range and the integer coordinate sums into the rows: a wave folds its
 //               lanes per distinct id first, then one set of integer atomics -- in LDS for the 16 largest components
 //               (per-workgroup parts that cc_finish folds), in global memory for the rest.
+//   cc_retable_clear / cc_retable / cc_finish   the table once more, of ids that depth_crease.hip has grown past the
+//               labelling's own (launch_component_table): cc_table's fold over given ids, the pixel counts with it.
 // No kernel waits for another workgroup, there is no cooperative launch and no float atomic: every loop ends because
 // parents only decrease.
 //
@@ -545,6 +547,102 @@ int launch_depth_components(pgp_ctx* ctx, const pgp_components_options* opt, con
   if (n_rank > 0)
     hipLaunchKernelGGL(cc_finish, dim3(n_rank), dim3(64), 0, st, (const int*)d_counts, n_rank, d_info,
                        (const pgp_component_info*)cv.at(c_part), table_blocks);
+  PGP_HIP(hipGetLastError());
+  return PGP_OK;
+}
+
+// ---- the table of an id image that is no longer the labelling's own (depth_crease.hip: the grown ids) ---------------
+namespace {
+
+// rows 0 .. min(kept, cap) - 1 keep their root; pixels and the folds start again
+__global__ __launch_bounds__(kThreads) void cc_retable_clear(const int* __restrict__ counts, int cap,
+                                                             pgp_component_info* __restrict__ info) {
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= cap || k >= counts[0]) return;
+  info[k].pixels = 0;
+  row_clear(&info[k]);
+}
+
+// cc_table's fold over given ids (values 0 .. min(kept, cap)); the pixel counts, which cc_table takes from the sort keys,
+// are one integer atomic per wave and distinct id on the row itself
+template <bool RAW16>
+__global__ __launch_bounds__(kThreads) void cc_retable(const void* __restrict__ img, int cols, Cam cam, const int* __restrict__ ids,
+                                                       size_t n, pgp_component_info* __restrict__ info,
+                                                       pgp_component_info* __restrict__ part) {
+  __shared__ pgp_component_info s_row[kLdsIds];
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x < kLdsIds) row_clear(&s_row[threadIdx.x]);
+  __syncthreads();
+  const size_t n_chunks = (n + kThreads - 1) / kThreads;
+  for (size_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {   // (workgroup-uniform)
+    const size_t i = ch * kThreads + threadIdx.x;
+    const int id = i < n ? ids[i] : 0;
+    int u = 0, v = 0;
+    unsigned zk = 0;
+    long long s[3] = {0, 0, 0};
+    if (id > 0) {
+      u = (int)(i / (size_t)cols);
+      v = (int)(i - (size_t)u * cols);
+      const float3 p = depth_point(u, v, depth_at<RAW16>(img, i), cam.fx, cam.fy, cam.cx, cam.cy);
+      zk = ordered_bits(p.z);
+      s[0] = llrint((double)p.x * 1e6);
+      s[1] = llrint((double)p.y * 1e6);
+      s[2] = llrint((double)p.z * 1e6);
+    }
+    unsigned long long todo = __ballot(id > 0);
+    while (todo) {   // (wave-uniform)
+      const int leader = __ffsll((long long)todo) - 1;
+      const int id0 = __shfl(id, leader, 64);
+      const bool in = id == id0;
+      const unsigned long long same = __ballot(in);
+      todo &= ~same;
+      const int u_lo = wave::min(in ? u : INT_MAX), u_hi = wave::max(in ? u : INT_MIN);
+      const int v_lo = wave::min(in ? v : INT_MAX), v_hi = wave::max(in ? v : INT_MIN);
+      const unsigned z_lo = wave::min(in ? zk : 0xFFFFFFFFu), z_hi = wave::max(in ? zk : 0u);
+      long long t[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) t[k] = wave::sum(in ? s[k] : 0ll);
+      if (lane == leader) {
+        atomicAdd(&info[id0 - 1].pixels, __popcll(same));
+        if (id0 <= kLdsIds) row_fold(&s_row[id0 - 1], u_lo, u_hi, v_lo, v_hi, z_lo, z_hi, t);
+        else row_fold(info + (id0 - 1), u_lo, u_hi, v_lo, v_hi, z_lo, z_hi, t);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kLdsIds) part[(size_t)blockIdx.x * kLdsIds + threadIdx.x] = s_row[threadIdx.x];
+}
+
+}  // namespace
+
+// d_ids: the ids of the launch_depth_components call just queued on `st` with the same options, shape and cap, regrown by
+// the caller (a pixel with id 0 may have taken an id; no id has lost a pixel).  Rewrites pixels, box, depth range and sums
+// of its info rows; their order and roots stay.
+int launch_component_table(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_img, bool raw16, int rows, int cols,
+                           const float K[9], const int* d_ids, pgp_component_info* d_info, int cap, const int* d_counts,
+                           hipStream_t st) {
+  const size_t n = (size_t)rows * cols;
+  const size_t key_cap = n / (size_t)opt->min_pixels;
+  const int n_rank = (int)(key_cap < (size_t)cap ? key_cap : (size_t)cap);
+  if (n_rank <= 0) return PGP_OK;
+  const int table_blocks = (int)std::min<size_t>((n + kThreads - 1) / kThreads, (size_t)kTableBlocks);
+  Carve cv;
+  const auto c_part = cv.add<pgp_component_info>((size_t)table_blocks * kLdsIds, 256);
+  cv.pad(256);
+  // (the labelling's workspace: free once its results are out, calls on one context are ordered, and that call sized it
+  //  for these parts among the rest, so nothing is allocated here)
+  int rc = cv.ensure(ctx->d_cc_ws);
+  if (rc != PGP_OK) return rc;
+  const Cam cam{K[0], K[4], K[2], K[5], opt->z_min, opt->z_max};
+  hipLaunchKernelGGL(cc_retable_clear, grid_for((size_t)n_rank), dim3(kThreads), 0, st, d_counts, n_rank, d_info);
+  if (raw16)
+    hipLaunchKernelGGL(cc_retable<true>, dim3(table_blocks), dim3(kThreads), 0, st, d_img, cols, cam, d_ids, n, d_info,
+                       cv.at(c_part));
+  else
+    hipLaunchKernelGGL(cc_retable<false>, dim3(table_blocks), dim3(kThreads), 0, st, d_img, cols, cam, d_ids, n, d_info,
+                       cv.at(c_part));
+  hipLaunchKernelGGL(cc_finish, dim3(n_rank), dim3(64), 0, st, d_counts, n_rank, d_info,
+                     (const pgp_component_info*)cv.at(c_part), table_blocks);
   PGP_HIP(hipGetLastError());
   return PGP_OK;
 }

@@ -262,7 +262,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_bitmap, &ctx->d_blocktab, &ctx->d_kd_nodes, &ctx->d_kd_pts, &ctx->d_occ_start, &ctx->d_cand, &ctx->d_Q, &ctx->d_Qn, &ctx->d_Qpos, &ctx->d_eo_ws, &ctx->d_T, &ctx->d_partial,
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
-                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_cc_ws, &ctx->d_cc_io, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
+                    &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_cc_ws, &ctx->d_cc_io, &ctx->d_crease_ws, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
                     &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io, &ctx->d_Prgb, &ctx->d_Qs_nrm, &ctx->d_Qs_rgb,
                     &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io,
@@ -3285,6 +3285,219 @@ int pgp_assign_masks_to_components(pgp_ctx* ctx, const int* ids, const void* cla
   PGP_HIP(hipMemcpyAsync(h_result, cv.at(c_res), (3 * (size_t)n_objects + 1) * 4, hipMemcpyDeviceToHost, st));
   PGP_HIP(hipStreamSynchronize(st));
   return assign_finish(h_result, n_objects, component, pixels_in, pixels_total, group, who);
+}
+
+}  // extern "C"
+
+// ---- touching objects: normals, concave-crease mask, cores + growing (depth_crease.hip) ------------------------------
+namespace {
+bool crease_options_ok(const pgp_crease_options* co, const char* who) {
+  if (!co || co->normal_step < 1 || co->normal_step > 8 || co->smooth_radius < 0 || co->smooth_radius > 4 ||
+      co->crease_step < 1 || co->crease_step > 8 || !(co->concavity >= 0.f) || !std::isfinite(co->concavity) ||
+      co->grow_passes < 0 || co->grow_passes > 64) {
+    set_error("%s: bad crease options (normal_step, crease_step 1..8, smooth_radius 0..4, concavity >= 0 and finite, "
+              "grow_passes 0..64)", who);
+    return false;
+  }
+  return true;
+}
+
+// image, mask, shape and options as pgp_depth_components checks them, and one output of out_bytes (+ an optional count)
+bool crease_args_ok(const pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* co, const void* image,
+                    const unsigned char* mask, int raw16, int rows, int cols, const float* K, const void* out,
+                    size_t bytes_per_pixel, const int* count, bool want_count, const char* who) {
+  int none[3];
+  if (!components_args_ok(ctx, opt, image, mask, raw16, rows, cols, K, nullptr, nullptr, nullptr, 0, none, who) ||
+      !crease_options_ok(co, who))
+    return false;
+  const size_t n = (size_t)rows * cols;
+  if ((n > 0 && !out) || (want_count && !count)) {
+    set_error("%s: null output", who);
+    return false;
+  }
+  const size_t out_bytes = n * bytes_per_pixel, img_bytes = n * (raw16 ? 2 : 4);
+  if (ranges_overlap(image, img_bytes, out, out_bytes) || ranges_overlap(mask, n, out, out_bytes) ||
+      (want_count && (ranges_overlap(image, img_bytes, count, 4) || ranges_overlap(mask, n, count, 4) ||
+                      ranges_overlap(out, out_bytes, count, 4)))) {
+    set_error("%s: the outputs overlap the inputs or each other", who);
+    return false;
+  }
+  return true;
+}
+
+bool objects_args_ok(const pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* co, const void* image,
+                     const unsigned char* mask, int raw16, int rows, int cols, const float* K, const int* roots, const int* ids,
+                     const pgp_component_info* info, int cap, const int* counts, const char* who) {
+  if (!components_args_ok(ctx, opt, image, mask, raw16, rows, cols, K, roots, ids, info, cap, counts, who) ||
+      !crease_options_ok(co, who))
+    return false;
+  // counts[3], counts[4]: the two words pgp_depth_components does not have
+  const size_t n = (size_t)rows * cols;
+  const void* other[5] = {image, mask, roots, ids, info};
+  const size_t other_bytes[5] = {n * (raw16 ? 2 : 4), n, n * 4, n * 4, (size_t)cap * sizeof(pgp_component_info)};
+  for (int k = 0; k < 5; ++k)
+    if (ranges_overlap(other[k], other_bytes[k], counts + 3, 8)) {
+      set_error("%s: the outputs overlap the inputs or each other", who);
+      return false;
+    }
+  return true;
+}
+
+// image (and mask) of a host-pointer call into the staging buffer, in front of whatever the call adds to `cv`
+struct StagedImage {
+  Carve::Piece<unsigned char> img, mask;
+  StagedImage(Carve& cv, size_t n, int raw16, bool has_mask) {
+    img = cv.add<unsigned char>(n * (raw16 ? 2 : 4), 256);
+    mask = cv.add<unsigned char>(has_mask ? n : 0, 256);
+  }
+  int upload(const Carve& cv, const void* image, const unsigned char* m, size_t n, hipStream_t st) const {
+    PGP_HIP(hipMemcpyAsync(cv.at(img), image, img.bytes(), hipMemcpyHostToDevice, st));
+    if (m) PGP_HIP(hipMemcpyAsync(cv.at(mask), m, n, hipMemcpyHostToDevice, st));
+    return PGP_OK;
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int pgp_crease_default_options(pgp_crease_options* opt) {
+  if (!opt) {
+    set_error("pgp_crease_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->normal_step = 3;
+  opt->smooth_radius = 2;
+  opt->crease_step = 4;
+  opt->concavity = 0.06f;
+  opt->grow_passes = 12;
+  return PGP_OK;
+}
+
+int pgp_depth_normals_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                             const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols, const float K[9],
+                             float* d_normals, void* stream) {
+  if (!crease_args_ok(ctx, opt, crease, d_image, d_mask, raw16, rows, cols, K, d_normals, 16, nullptr, false,
+                      "pgp_depth_normals_device"))
+    return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_depth_normals(opt, crease, d_image, raw16 != 0, d_mask, rows, cols, K, d_normals, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_depth_normals(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease, const void* image,
+                      int raw16, const unsigned char* mask, int rows, int cols, const float K[9], float* normals) {
+  if (!crease_args_ok(ctx, opt, crease, image, mask, raw16, rows, cols, K, normals, 16, nullptr, false, "pgp_depth_normals"))
+    return PGP_EINVAL;
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  Carve cv;
+  const StagedImage in(cv, n, raw16, mask != nullptr);
+  const auto c_out = cv.add<float>(4 * n, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK || (rc = in.upload(cv, image, mask, n, st)) != PGP_OK) return rc;
+  if ((rc = launch_depth_normals(opt, crease, cv.at(in.img), raw16 != 0, mask ? cv.at(in.mask) : nullptr, rows, cols, K,
+                                 cv.at(c_out), st)) != PGP_OK)
+    return rc;
+  PGP_HIP(hipMemcpyAsync(normals, cv.at(c_out), c_out.bytes(), hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+int pgp_depth_crease_mask_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                                 const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols,
+                                 const float K[9], unsigned char* d_keep, int* d_n_crease, void* stream) {
+  if (!crease_args_ok(ctx, opt, crease, d_image, d_mask, raw16, rows, cols, K, d_keep, 1, d_n_crease, true,
+                      "pgp_depth_crease_mask_device"))
+    return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_depth_crease_mask(ctx, opt, crease, d_image, raw16 != 0, d_mask, rows, cols, K, d_keep, d_n_crease, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_depth_crease_mask(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease, const void* image,
+                          int raw16, const unsigned char* mask, int rows, int cols, const float K[9], unsigned char* keep,
+                          int* n_crease) {
+  if (!crease_args_ok(ctx, opt, crease, image, mask, raw16, rows, cols, K, keep, 1, n_crease, true, "pgp_depth_crease_mask"))
+    return PGP_EINVAL;
+  *n_crease = 0;
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  Carve cv;
+  const StagedImage in(cv, n, raw16, mask != nullptr);
+  const auto c_keep = cv.add<unsigned char>(n, 256);
+  const auto c_count = cv.add<int>(1, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK || (rc = in.upload(cv, image, mask, n, st)) != PGP_OK) return rc;
+  if ((rc = launch_depth_crease_mask(ctx, opt, crease, cv.at(in.img), raw16 != 0, mask ? cv.at(in.mask) : nullptr, rows, cols, K,
+                                     cv.at(c_keep), cv.at(c_count), st)) != PGP_OK)
+    return rc;
+  int h_count = 0;
+  PGP_HIP(hipMemcpyAsync(keep, cv.at(c_keep), n, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(&h_count, cv.at(c_count), 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  *n_crease = h_count;
+  return PGP_OK;
+}
+
+int pgp_depth_objects_device(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease,
+                             const void* d_image, int raw16, const unsigned char* d_mask, int rows, int cols, const float K[9],
+                             int* d_roots, int* d_ids, pgp_component_info* d_info, int cap, int* d_counts, void* stream) {
+  if (!objects_args_ok(ctx, opt, crease, d_image, d_mask, raw16, rows, cols, K, d_roots, d_ids, d_info, cap, d_counts,
+                       "pgp_depth_objects_device"))
+    return PGP_EINVAL;
+  CtxGuard guard(ctx, false);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = launch_depth_objects(ctx, opt, crease, d_image, raw16 != 0, d_mask, rows, cols, K, d_roots, d_ids, d_info, cap,
+                                      d_counts, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_depth_objects(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* crease, const void* image,
+                      int raw16, const unsigned char* mask, int rows, int cols, const float K[9], int* roots, int* ids,
+                      pgp_component_info* info, int cap, int counts[5]) {
+  if (!objects_args_ok(ctx, opt, crease, image, mask, raw16, rows, cols, K, roots, ids, info, cap, counts, "pgp_depth_objects"))
+    return PGP_EINVAL;
+  std::memset(counts, 0, 20);
+  const size_t n = (size_t)rows * cols;
+  if (n == 0) return PGP_OK;
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t rows_cap = std::min((size_t)cap, n / (size_t)opt->min_pixels);   // info rows the device can write
+  Carve cv;
+  const StagedImage in(cv, n, raw16, mask != nullptr);
+  const auto c_roots = cv.add<int>(roots ? n : 0, 256), c_ids = cv.add<int>(ids ? n : 0, 256);
+  const auto c_info = cv.add<pgp_component_info>(rows_cap, 256);
+  const auto c_counts = cv.add<int>(5, 256);
+  cv.pad(256);
+  int rc = cv.ensure(ctx->d_cc_io);
+  if (rc != PGP_OK || (rc = in.upload(cv, image, mask, n, st)) != PGP_OK) return rc;
+  if ((rc = launch_depth_objects(ctx, opt, crease, cv.at(in.img), raw16 != 0, mask ? cv.at(in.mask) : nullptr, rows, cols, K,
+                                 roots ? cv.at(c_roots) : nullptr, ids ? cv.at(c_ids) : nullptr,
+                                 rows_cap ? cv.at(c_info) : nullptr, (int)rows_cap, cv.at(c_counts), st)) != PGP_OK)
+    return rc;
+  int h_counts[5] = {0, 0, 0, 0, 0};
+  if (roots) PGP_HIP(hipMemcpyAsync(roots, cv.at(c_roots), n * 4, hipMemcpyDeviceToHost, st));
+  if (ids) PGP_HIP(hipMemcpyAsync(ids, cv.at(c_ids), n * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipMemcpyAsync(h_counts, cv.at(c_counts), 20, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  const size_t written = std::min((size_t)h_counts[0], rows_cap);   // rows beyond the kept count stay as the caller left them
+  if (written) {
+    PGP_HIP(hipMemcpyAsync(info, cv.at(c_info), written * sizeof(pgp_component_info), hipMemcpyDeviceToHost, st));
+    PGP_HIP(hipStreamSynchronize(st));
+  }
+  std::memcpy(counts, h_counts, 20);
+  return PGP_OK;
 }
 
 }  // extern "C"

@@ -270,6 +270,7 @@ struct pgp_ctx {
   pgp::DevBuf d_mls_ws;                      // mls.hip: sort keys, sorted cloud, per-point results
   pgp::DevBuf d_plane_ws, d_plane_io;        // plane.hip: candidate / partial workspace; host-API staging
   pgp::DevBuf d_cc_ws, d_cc_io;              // components.hip: parents | roots | counts | sort keys; host-API staging
+  pgp::DevBuf d_crease_ws;                   // depth_crease.hip: normals | keep bytes | two id images
   bool hd_attr_set = false;
   // segment.hip: the filter's counts | workgroup counters | scan scratch, and the centroid of pgp_center_device (d_seg_c);
   // the intermediates of pgp_segment_from_depth_device: dense cloud, voxel leaves, the MLS and filter rows + weights
@@ -766,11 +767,25 @@ int launch_mask_plane_depth(pgp_ctx* ctx, void* d_img, bool raw16, int rows, int
 int launch_depth_components(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_img, bool raw16,
                             const unsigned char* d_mask, int rows, int cols, const float K[9], int* d_roots, int* d_ids,
                             pgp_component_info* d_info, int cap, int* d_counts, hipStream_t st);
+// the info rows of that call again, from ids the caller has regrown (depth_crease.hip): order and roots stay
+int launch_component_table(pgp_ctx* ctx, const pgp_components_options* opt, const void* d_img, bool raw16, int rows, int cols,
+                           const float K[9], const int* d_ids, pgp_component_info* d_info, int cap, const int* d_counts,
+                           hipStream_t st);
 int launch_component_mask(const int* d_ids, size_t n, int id, unsigned char* d_mask, hipStream_t st);
 constexpr int kAssignMaxId = 65535, kAssignMaxObjects = 64;
 // d_result: n_objects x {component, pixels_in, pixels_total} followed by one flag word (non-zero: an id outside the bound)
 int launch_assign_masks(pgp_ctx* ctx, const int* d_ids, const void* d_classes, int class_bytes, size_t n,
                         const int* class_values, int n_objects, int* d_result, hipStream_t st);
+
+// depth_crease.hip (d_normals: rows x cols x 4 floats; d_counts: 5 ints)
+int launch_depth_normals(const pgp_components_options* opt, const pgp_crease_options* co, const void* d_img, bool raw16,
+                         const unsigned char* d_mask, int rows, int cols, const float K[9], float* d_normals, hipStream_t st);
+int launch_depth_crease_mask(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* co, const void* d_img,
+                             bool raw16, const unsigned char* d_mask, int rows, int cols, const float K[9],
+                             unsigned char* d_keep, int* d_n_crease, hipStream_t st);
+int launch_depth_objects(pgp_ctx* ctx, const pgp_components_options* opt, const pgp_crease_options* co, const void* d_img,
+                         bool raw16, const unsigned char* d_mask, int rows, int cols, const float K[9], int* d_roots, int* d_ids,
+                         pgp_component_info* d_info, int cap, int* d_counts, hipStream_t st);
 
 // rigid_fit.hip
 int launch_rigid(pgp_ctx* ctx, const int* d_base_ids, const int* d_quad_ids, int n, const float cP[3],

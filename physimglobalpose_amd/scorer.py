@@ -961,6 +961,138 @@ class LcpScorer:
                 cols, vals.ctypes.data_as(_i), n, *ip))
         return tuple(a[:n] for a in out)
 
+    # ---- touching objects: normals, concave-crease mask, cores + growing ------------------------------
+    @staticmethod
+    def crease_options(**kw):
+        """pgp_crease_options with the defaults (normal_step 3, smooth_radius 2, crease_step 4, concavity 0.06,
+        grow_passes 12), fields overridden by keyword."""
+        o = _lib.CreaseOptions()
+        _lib.check(_lib.load().pgp_crease_default_options(C.byref(o)))
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError(f"pgp_crease_options has no field {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def _crease_call_options(self, options, crease, kw):
+        """(pgp_components_options, pgp_crease_options) of a call: keywords go to the struct that has the field."""
+        names = {f[0] for f in _lib.CreaseOptions._fields_}
+        co = crease if crease is not None else self.crease_options(**{k: v for k, v in kw.items() if k in names})
+        rest = {k: v for k, v in kw.items() if k not in names}
+        if crease is not None and len(rest) != len(kw):
+            raise TypeError("crease fields given both as a struct and by keyword")
+        return (options if options is not None else self.components_options(**rest)), co
+
+    @staticmethod
+    def _host_image(image, K, mask):
+        image = np.ascontiguousarray(image)
+        assert image.dtype in (np.uint16, np.float32) and image.ndim == 2
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        return image, np.ascontiguousarray(K, np.float32).reshape(9), m
+
+    @staticmethod
+    def _device_image(d_image):
+        import torch
+        assert d_image.is_cuda and d_image.is_contiguous() and d_image.dtype in (torch.uint16, torch.int16, torch.float32)
+        return d_image.shape[0], d_image.shape[1], int(d_image.dtype != torch.float32)
+
+    def depth_normals(self, image, K, mask=None, options=None, crease=None, **kw):
+        """Smoothed surface normals of a depth image (uint16 raw or float32 metres) -> (rows, cols, 4) float32:
+        (nx, ny, nz, 1) where the pixel has a normal, zeros elsewhere.  Keywords are fields of pgp_components_options
+        or pgp_crease_options."""
+        image, K9, m = self._host_image(image, K, mask)
+        rows, cols = image.shape
+        o, co = self._crease_call_options(options, crease, kw)
+        out = np.zeros((rows, cols, 4), np.float32)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.pgp_depth_normals(self._h, C.byref(o), C.byref(co), vp(image), int(image.dtype == np.uint16),
+                                               vp(m), rows, cols, _fp(K9), vp(out)))
+        return out
+
+    def depth_normals_device(self, d_image, K, d_mask=None, d_normals=None, options=None, crease=None, stream=None, **kw):
+        """pgp_depth_normals_device on torch tensors, queued on `stream` (default: the current stream), no host
+        synchronisation -> d_normals (rows, cols, 4) float32."""
+        import torch
+        rows, cols, raw16 = self._device_image(d_image)
+        o, co = self._crease_call_options(options, crease, kw)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        if d_normals is None:
+            d_normals = torch.empty((rows, cols, 4), dtype=torch.float32, device=d_image.device)
+        st = (stream or torch.cuda.current_stream(d_image.device)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_depth_normals_device(self._h, C.byref(o), C.byref(co), p(d_image), raw16, p(d_mask), rows,
+                                                      cols, _fp(K9), p(d_normals), C.c_void_p(st)))
+        return d_normals
+
+    def depth_crease_mask(self, image, K, mask=None, options=None, crease=None, **kw):
+        """-> (keep (rows, cols) uint8: 1 for a valid pixel that is no crease pixel, number of crease pixels)."""
+        image, K9, m = self._host_image(image, K, mask)
+        rows, cols = image.shape
+        o, co = self._crease_call_options(options, crease, kw)
+        keep = np.zeros((rows, cols), np.uint8)
+        n = C.c_int(0)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.pgp_depth_crease_mask(self._h, C.byref(o), C.byref(co), vp(image), int(image.dtype == np.uint16),
+                                                   vp(m), rows, cols, _fp(K9), vp(keep), C.byref(n)))
+        return keep, n.value
+
+    def depth_crease_mask_device(self, d_image, K, d_mask=None, d_keep=None, d_n_crease=None, options=None, crease=None,
+                                 stream=None, **kw):
+        """pgp_depth_crease_mask_device on torch tensors, queued, not synchronised -> (d_keep (rows, cols) uint8,
+        d_n_crease (1,) int32)."""
+        import torch
+        rows, cols, raw16 = self._device_image(d_image)
+        o, co = self._crease_call_options(options, crease, kw)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        dev = d_image.device
+        d_keep = torch.empty((rows, cols), dtype=torch.uint8, device=dev) if d_keep is None else d_keep
+        d_n_crease = torch.empty(1, dtype=torch.int32, device=dev) if d_n_crease is None else d_n_crease
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_depth_crease_mask_device(self._h, C.byref(o), C.byref(co), p(d_image), raw16, p(d_mask), rows,
+                                                          cols, _fp(K9), p(d_keep), p(d_n_crease), C.c_void_p(st)))
+        return d_keep, d_n_crease
+
+    def depth_objects(self, image, K, mask=None, cap=64, want_roots=True, want_ids=True, options=None, crease=None, **kw):
+        """Object proposals with touching objects cut along concave creases: normals, crease mask, the cores'
+        components, growing -> (roots, ids, info, counts (5,) int32: kept cores, cores, valid pixels, crease pixels,
+        pixels labelled by growing), as depth_components returns them."""
+        image, K9, m = self._host_image(image, K, mask)
+        rows, cols = image.shape
+        o, co = self._crease_call_options(options, crease, kw)
+        roots = np.full((rows, cols), -2, np.int32) if want_roots else None
+        ids = np.full((rows, cols), -2, np.int32) if want_ids else None
+        info = np.zeros(max(cap, 1), self.COMPONENT_INFO_DTYPE)
+        counts = np.zeros(5, np.int32)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _lib.check(self._lib.pgp_depth_objects(self._h, C.byref(o), C.byref(co), vp(image), int(image.dtype == np.uint16), vp(m),
+                                               rows, cols, _fp(K9), vp(roots), vp(ids), vp(info) if cap > 0 else None, int(cap),
+                                               counts.ctypes.data_as(_i)))
+        return roots, ids, info[: min(int(counts[0]), cap)].copy(), counts
+
+    def depth_objects_device(self, d_image, K, d_mask=None, cap=64, d_roots=None, d_ids=None, d_info=None, d_counts=None,
+                             want_roots=True, want_ids=True, options=None, crease=None, stream=None, **kw):
+        """pgp_depth_objects_device on torch tensors, queued on `stream` (default: the current stream) with no host
+        synchronisation -> (d_roots, d_ids, d_info, d_counts (5,) int32), as depth_components_device returns them."""
+        import torch
+        rows, cols, raw16 = self._device_image(d_image)
+        dev = d_image.device
+        o, co = self._crease_call_options(options, crease, kw)
+        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        if d_roots is None and want_roots:
+            d_roots = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+        if d_ids is None and want_ids:
+            d_ids = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+        if d_info is None and cap > 0:
+            d_info = torch.zeros((cap, self.COMPONENT_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(5, dtype=torch.int32, device=dev) if d_counts is None else d_counts
+        st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_depth_objects_device(self._h, C.byref(o), C.byref(co), p(d_image), raw16, p(d_mask), rows, cols,
+                                                      _fp(K9), p(d_roots), p(d_ids), p(d_info), int(cap), p(d_counts),
+                                                      C.c_void_p(st)))
+        return d_roots, d_ids, d_info, d_counts
+
     def depth_cost(self, observed, rendered, threshold=0.01):
         """observed (rows,cols) f32, rendered (n,rows,cols) f32 -> (render_score (n,), counts (n,3))."""
         obs = np.ascontiguousarray(observed, np.float32)
