@@ -1311,6 +1311,10 @@ int pgp_ppf_model_angles(pgp_ctx* ctx, float* alpha, long long n);
  * default (the rule: csrc/physics.hip step 3e, restated by tests/_physics_edges_restate.py).  Its limits: a body
  * thinner than `reach` can pick up an edge pair of its far side; an overlap deeper than `reach` falls back to
  * vertex-face contacts; it is still not GJK/EPA (no face-face clipping, no closest features of separated hulls).
+ * pgp_physics_set_polyhedral_contacts replaces both rules by a separating-axis test with face clipping that has no
+ * `reach` (step 3p), also off by default.  Its limits: one contact point for an edge-edge contact; no persistent
+ * manifold and no warm start; no closest features of separated hulls (hulls farther apart than their margins make no
+ * contact); and a cost that grows with the product of the two hulls' edge counts.
  * Shapes live in a per-context arena until pgp_destroy.  Shape 0 is the built-in table box (8 vertices, 6 planes,
  * margin 0); pgp_physics_add_shape hands out 1, 2, ... */
 #define PGP_PHYSICS_TABLE_SHAPE 0
@@ -1366,6 +1370,22 @@ int pgp_physics_shape_edges(pgp_ctx* ctx, int shape_id, int* edges, int* n_edges
  * points of two edges that still makes a contact.  PGP_EINVAL: NULL context or a bad reach (nothing changes). */
 #define PGP_PHYSICS_EDGE_REACH_DEFAULT 0.01f
 int pgp_physics_set_edge_contacts(pgp_ctx* ctx, int on, float reach);
+/* The face loops the device holds for a shape: the loop of plane f is face_vertices[face_offsets[f]] ..
+ * face_vertices[face_offsets[f + 1] - 1], indices into pgp_physics_shape_info's vertices, counter-clockwise seen from
+ * outside, starting at the loop's lowest vertex index.  *n_faces = the plane count; face_offsets (n_faces + 1 ints, at
+ * most 2 x 256 + 1) and face_vertices (twice the edge count, at most 2 x PGP_PHYSICS_MAX_EDGES ints) are nullable. */
+int pgp_physics_shape_faces(pgp_ctx* ctx, int shape_id, int* face_offsets, int* face_vertices, int* n_faces);
+/* Polyhedral contacts in every later settle of this context (pgp_physics_settle, _settle_device, _trace,
+ * pgp_mcts_search): a separating-axis test over the face normals of both hulls and the edge pairs that form a face of
+ * their Minkowski difference, then the incident face clipped against the reference face (csrc/physics.hip step 3p,
+ * restated by tests/_physics_sat_restate.py).  A context setting, off by default.  While on it replaces the
+ * vertex-face and the edge-edge rule, whatever pgp_physics_set_edge_contacts says; turned off, the context is back at
+ * what that switch selects.  face_bias (metres, >= 0, finite): an edge axis is taken only when its separation exceeds
+ * the best face separation by more than this, so that nearly equal penetrations do not flicker between a one-point
+ * and a four-point manifold; the default is the reference's collision margin (PhySim.cpp:64).
+ * PGP_EINVAL: NULL context or a bad face_bias (nothing changes). */
+#define PGP_PHYSICS_FACE_BIAS_DEFAULT 0.001f
+int pgp_physics_set_polyhedral_contacts(pgp_ctx* ctx, int on, float face_bias);
 /* correctPhysics for n_states independent states, one dynamic body each: state i drops dyn_shape[i] at T[i] among the
  * table and its statics static_shape[j] at static_T[j], j in [static_offsets[i], static_offsets[i + 1]) (at most 16).
  * Poses are 16 floats column-major, object -> camera frame like every T of this header; world = cam_pose . T

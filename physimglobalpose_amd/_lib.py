@@ -383,6 +383,8 @@ SIGNATURES = {
     "pgp_physics_shape_info": (C.c_int, [C.c_void_p, C.c_int, _f, _i, _f, _i, _f, _f]),
     "pgp_physics_shape_edges": (C.c_int, [C.c_void_p, C.c_int, _i, _i]),
     "pgp_physics_set_edge_contacts": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "pgp_physics_shape_faces": (C.c_int, [C.c_void_p, C.c_int, _i, _i, _i]),
+    "pgp_physics_set_polyhedral_contacts": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "pgp_physics_settle": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, _i, _f, _i, _i, _f, _f, _f, _f,
                                      C.POINTER(PhysicsInfo)]),
     "pgp_physics_settle_device": (C.c_int, [C.c_void_p, C.POINTER(PhysicsOptions), C.c_int, C.c_void_p, C.c_void_p,

@@ -3758,10 +3758,23 @@ int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, i
   std::vector<int> hv;
   std::vector<std::array<double, 4>> pl;
   std::vector<int4> ed;
-  int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_physics_add_shape", &ed);
+  std::vector<int> loop_off, loop_idx;
+  int rc = convex_hull_impl(xyz, n, max_vertices, hv, pl, "pgp_physics_add_shape", &ed, &loop_off, &loop_idx);
   if (rc != PGP_OK) return rc;
   if ((int)ed.size() > PGP_PHYSICS_MAX_EDGES) {   // a closed hull of V vertices has at most 3 V - 6 edges
     set_error("pgp_physics_add_shape: %d hull edges (at most %d)", (int)ed.size(), PGP_PHYSICS_MAX_EDGES);
+    return PGP_EINVAL;
+  }
+  // every edge is a side of two loops, every loop closes, and no loop outgrows the vertex cap (the settle kernel
+  // sizes its polygon buffers by these)
+  bool loops_ok = loop_off.size() == pl.size() + 1 && loop_idx.size() == 2 * ed.size();
+  for (size_t f = 0; loops_ok && f < pl.size(); ++f) {
+    const int len = loop_off[f + 1] - loop_off[f];
+    loops_ok = len >= 3 && len <= PGP_PHYSICS_MAX_VERTICES;
+  }
+  if (!loops_ok) {
+    set_error("pgp_physics_add_shape: the hull's face loops do not close (%d loop entries, %d edges)", (int)loop_idx.size(),
+              (int)ed.size());
     return PGP_EINVAL;
   }
   CtxGuard guard(ctx);
@@ -3770,14 +3783,9 @@ int pgp_physics_add_shape(pgp_ctx* ctx, const float* xyz, int n, float margin, i
   for (int i : hv) v.push_back(make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.f));
   for (const auto& e : pl) p.push_back(make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]));
   PGP_HIP(hipDeviceSynchronize());   // a queued settle may still read the arena that is about to grow
-  arena_append(ctx, v, p, ed, margin);
+  arena_append(ctx, v, p, ed, loop_off, loop_idx, margin);
   if ((rc = arena_upload(ctx)) != PGP_OK) {
-    const PhysShape s = ctx->phys_shapes.back();
-    ctx->phys_shapes.pop_back();
-    ctx->phys_verts.resize(s.vert_off);
-    ctx->phys_planes.resize(s.plane_off);
-    ctx->phys_edges.resize(ctx->phys_eslices.back().edge_off);
-    ctx->phys_eslices.pop_back();
+    arena_pop(ctx);
     return rc;
   }
   *shape_id = (int)ctx->phys_shapes.size() - 1;
@@ -3846,6 +3854,43 @@ int pgp_physics_set_edge_contacts(pgp_ctx* ctx, int on, float reach) {
   CtxGuard guard(ctx);
   ctx->phys_edge_contacts = on != 0;
   ctx->phys_edge_reach = reach;
+  return PGP_OK;
+}
+
+int pgp_physics_shape_faces(pgp_ctx* ctx, int shape_id, int* face_offsets, int* face_vertices, int* n_faces) {
+  if (!ctx) {
+    set_error("pgp_physics_shape_faces: null context");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  int rc = physics_arena_init(ctx);
+  if (rc != PGP_OK) return rc;
+  if (shape_id < 0 || shape_id >= (int)ctx->phys_shapes.size()) {
+    set_error("pgp_physics_shape_faces: unknown shape %d", shape_id);
+    return PGP_EINVAL;
+  }
+  PhysShape sh;
+  PhysFaceSlice s;
+  PGP_HIP(hipMemcpy(&sh, ctx->d_phys_shapes.as<PhysShape>() + shape_id, sizeof(sh), hipMemcpyDeviceToHost));
+  PGP_HIP(hipMemcpy(&s, ctx->d_phys_fslices.as<PhysFaceSlice>() + shape_id, sizeof(s), hipMemcpyDeviceToHost));
+  std::vector<int> off((size_t)sh.n_plane + 1);
+  PGP_HIP(hipMemcpy(off.data(), ctx->d_phys_face_off.as<int>() + s.off_off, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (n_faces) *n_faces = sh.n_plane;
+  if (face_offsets) std::copy(off.begin(), off.end(), face_offsets);
+  if (face_vertices && off.back() > 0)
+    PGP_HIP(hipMemcpy(face_vertices, ctx->d_phys_face_idx.as<int>() + s.idx_off, (size_t)off.back() * sizeof(int),
+                      hipMemcpyDeviceToHost));
+  return PGP_OK;
+}
+
+int pgp_physics_set_polyhedral_contacts(pgp_ctx* ctx, int on, float face_bias) {
+  if (!ctx || !(face_bias >= 0.f) || !std::isfinite(face_bias)) {
+    set_error("pgp_physics_set_polyhedral_contacts: %s", !ctx ? "ctx is NULL" : "face_bias must be >= 0 and finite");
+    return PGP_EINVAL;
+  }
+  CtxGuard guard(ctx);
+  ctx->phys_poly_contacts = on != 0;
+  ctx->phys_face_bias = face_bias;
   return PGP_OK;
 }
 

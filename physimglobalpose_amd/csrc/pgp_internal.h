@@ -135,6 +135,12 @@ struct PhysShape {
 struct PhysEdgeSlice {
   int edge_off, n_edge;
 };
+// the face loops of shape i, beside PhysShape for the same reason: plane f's loop is idx[idx_off + off[off_off + f]] ..
+// idx[idx_off + off[off_off + f + 1]) (off: n_plane + 1 ints per shape, the first 0), entries index the shape's own
+// vertices, counter-clockwise seen from outside, from the loop's lowest vertex index; 2 n_edge entries per shape
+struct PhysFaceSlice {
+  int off_off, idx_off;
+};
 
 }  // namespace pgp
 
@@ -379,9 +385,14 @@ struct pgp_ctx {
   std::vector<float4> phys_verts, phys_planes;   // body frame: {x, y, z, 0} and {n, d}
   std::vector<pgp::PhysEdgeSlice> phys_eslices;  // one per shape
   std::vector<int4> phys_edges;                  // hull edges: {v0, v1, f0, f1}, v0 < v1, f0 < f1, ascending (v0, v1)
+  std::vector<pgp::PhysFaceSlice> phys_fslices;  // one per shape
+  std::vector<int> phys_face_off, phys_face_idx; // face loops, see PhysFaceSlice
   pgp::DevBuf d_phys_shapes, d_phys_verts, d_phys_planes, d_phys_eslices, d_phys_edges, d_phys_io;
+  pgp::DevBuf d_phys_fslices, d_phys_face_off, d_phys_face_idx;
   bool phys_edge_contacts = false;   // pgp_physics_set_edge_contacts: launch_settle runs the edge-edge instantiation
   float phys_edge_reach = PGP_PHYSICS_EDGE_REACH_DEFAULT;
+  bool phys_poly_contacts = false;   // pgp_physics_set_polyhedral_contacts: launch_settle runs settle_poly_kernel (step 3p)
+  float phys_face_bias = PGP_PHYSICS_FACE_BIAS_DEFAULT;
 
   // MCTS search (mcts.hip): step workspace (pose tables, settle inputs, descriptors, scores); two images per slot
   pgp::DevBuf d_mcts_ws, d_mcts_img;
@@ -671,11 +682,14 @@ struct PhysParams {
   float table[12];
 };
 int physics_arena_init(pgp_ctx* ctx);   // the built-in table box as shape 0, uploaded (idempotent)
-// edges (nullable): the hull's edge rows (v0, v1, f0, f1) over hv and pl, see PhysShape
+// edges (nullable): the hull's edge rows (v0, v1, f0, f1) over hv and pl, see PhysShape; loop_off / loop_idx (nullable,
+// both or neither): the face loops, see PhysFaceSlice
 int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>& hv, std::vector<std::array<double, 4>>& pl,
-                     const char* who, std::vector<int4>* edges = nullptr);
+                     const char* who, std::vector<int4>* edges = nullptr, std::vector<int>* loop_off = nullptr,
+                     std::vector<int>* loop_idx = nullptr);
 void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, const std::vector<int4>& e,
-                  float margin);
+                  const std::vector<int>& loop_off, const std::vector<int>& loop_idx, float margin);
+void arena_pop(pgp_ctx* ctx);   // drops the shape appended last from the host mirror
 int arena_upload(pgp_ctx* ctx);
 int check_options(const pgp_physics_options* o, const char* who, int max_steps);
 int make_params(pgp_ctx* ctx, const pgp_physics_options* o, int n_states, const float* table_params, const float* cam_pose,

@@ -3,8 +3,8 @@
 // The reference (PPE/hypothesis_verification/mcts/UCTState.cpp:208-270, physics_reasoning/PhySim.cpp) drops the newest
 // object into a Bullet 2.86 world among the earlier objects (mass 0) and the table box, runs 60 x stepSimulation(1/60)
 // and reads the pose back.  Bullet is not matched bit for bit; this file runs the rules below EXACTLY, and
-// tests/_physics_restate.py (steps 1 .. 6) and tests/_physics_edges_restate.py (with step 3e) restate them in numpy
-// float32, term by term.  Every operation is float32, rounded
+// tests/_physics_restate.py (steps 1 .. 6), tests/_physics_edges_restate.py (with step 3e) and
+// tests/_physics_sat_restate.py (with step 3p) restate them in numpy float32, term by term.  Every operation is float32, rounded
 // separately (-ffp-contract=off), sums left to right as written; sqrt(x) = (float)sqrt((double)x) and a / b = __fdiv_rn,
 // both correctly rounded.  One dynamic body D per state; the others (the table first, then the statics in the caller's
 // order) are static S.  Mass cancels: impulses are per unit mass, 1/m = 1.
@@ -49,6 +49,39 @@
 //       candidate: point c_D, normal n, depth = (n . g) - m.
 //     Edge candidates are numbered after D's and S's vertex candidates, in pair order; a pair has room for 512
 //     candidates in all, and edge candidates past it are dropped, in pair order.
+//  3p. Polyhedral contacts, only with pgp_physics_set_polyhedral_contacts on (face_bias: its second argument); they
+//     replace 3 and 3e, whatever the edge switch says; the sphere rule of 3 stays.  Shapes carry, per plane, the loop
+//     of its vertices, counter-clockwise seen from outside, from its lowest vertex index (tests/_physics_sat_restate.py
+//     restates the loops and this step).  Per pair (D, S), m = m_D + m_S, s_f the expression of 3:
+//     Face queries: sep_S(f) = min s_f over D's vertices (taken into S's frame as in 3) for each plane f of S,
+//       sep_D(f) = min s_f over S's vertices (p = R_S s + t_S, p_D = R^T (p - x)) for each plane f of D; best_S, best_D
+//       = the first maximal sep; the vertex of a plane = the first that attains its sep.  best_S >= m or best_D >= m:
+//       no contacts.
+//     Edge query, pairs (a of D: a0 a1, planes f0 f1; b of S: b0 b1) ascending by (D edge, S edge), world frame:
+//       A = R n_f0, B = R n_f1 of a; C = -(R_S n_f0), E = -(R_S n_f1) of b (each (R_i0 n_x + R_i1 n_y) + R_i2 n_z);
+//       the pair counts only when the arcs AB and CE cross on the Gauss map (then a and b span a face of the Minkowski
+//       difference): with U = B x A, V = E x C: (C . U) (E . U) < 0 and (A . V) (B . V) < 0 and (C . U) (B . V) > 0;
+//       d1, d2, a, e, b, den and the parallel rejection den > 1e-6f (a e) of 3e; n = (d1 x d2) / |d1 x d2|, o_S, o_D,
+//       the flip and the rejection unless n . o_S > 0 and n . o_D < 0 of 3e; sep_E = n . r, r = a0 - b0.
+//       best_E = the first maximal sep_E (a NaN is no maximum); best_E >= m: no contacts.
+//     Choice: an edge contact when a pair counted and best_E > max(best_S, best_D) + face_bias; else a face contact,
+//       the reference body S when best_S >= best_D, else D.  (A face gives a manifold, an edge one point: the bias
+//       keeps nearly equal penetrations from flickering between them.)
+//     Edge contact, of the pair of best_E: c = d1 . r, f = d2 . r, s = (b f - c e) / den clamped to [0, 1] (t does not
+//       enter: the point is D's); one candidate: point c_D = a0 + s d1, normal n, depth best_E - m.
+//     Face contact: f* the reference plane, N = R_ref n_f* (world).  Incident face g: the plane of the other body with
+//       the first least N . (R_inc n_g).  Polygon: g's loop in world coordinates (D: the step's world vertices; S:
+//       R_S s + t_S).  For each side k of f*'s loop in loop order, u = world vertex k, w = the next one (cyclic),
+//       K = (w - u) x N, side(p) = K . (p - u); p is kept when side(p) <= 0.  One pass visits the polygon's edges a -> b
+//       (b the next point, cyclic) in order and emits a when a is kept, then, when exactly one of a, b is kept, the
+//       crossing a + t (b - a), t = side(a) / (side(a) - side(b)), per component a_i + t (b_i - a_i)
+//       (Sutherland-Hodgman).  A polygon holds at most 512 points: later ones are dropped in output order (two loops
+//       of at most 256 vertices stay below it unless rounding breaks convexity).
+//       Candidates: the clipped polygon's points in output order whose s = s_f*(p) (p into the reference body's frame
+//       as in 3) is < m: point p, depth s - m, normal N when the reference is S, -N (per component) when it is D.
+//       An empty polygon: one candidate, the incident body's vertex of f* (above), depth best - m, the same normal.
+//     Limits: one point for an edge-edge contact; no persistent manifold, no warm start; no closest features of
+//     separated hulls (a pair farther apart than m has no contacts); the edge query visits E_D x E_S pairs.
 //  4. Manifold reduction, when a pair has more than 4 candidates (else all of them, in candidate order): c1 = the
 //     least depth; c2 = max |p - p1|^2; c3 = max |(p - p1) x (p - p2)|^2; c4 = max of the sum
 //     (|(p - p1) x (p - p2)|^2 + |(p - p2) x (p - p3)|^2) + |(p - p3) x (p - p1)|^2; each among the candidates not
@@ -68,7 +101,7 @@
 // -(((R_0i t_0 + R_1i t_1) + R_2i t_2))), or W without cam.  steps == 0: T_out = T, bit for bit.
 // Contacts are vertex-face, plus edge-edge behind the switch; no persistent manifold, no split impulse, no
 // restitution.  Limits of 3e: a body thinner than reach can pick up an edge pair of its far side; an overlap deeper
-// than reach falls back to vertex-face contacts; it is still not GJK/EPA.
+// than reach falls back to vertex-face contacts; it is still not GJK/EPA.  Step 3p has no reach; its limits stand with it.
 //
 // Kernel: one workgroup of 256 threads per state, all steps in one launch.  D's hull (body and world frame) and
 // planes sit in LDS; candidates are tested one vertex per thread and compacted in vertex order with a ballot and
@@ -79,6 +112,12 @@
 // edge per thread and pass of 256 for the activity test, compacted like the candidates into 16-bit indices in LDS;
 // then one edge pair per thread and pass, compacted behind the vertex candidates; every loop is bounded by the edge
 // counts.  Workgroups never talk to each other, so a state's result is independent of its batch.
+// Step 3p (settle_poly_kernel, a sibling with the same steps around it): face queries one plane per thread over the
+// other body's vertices, staged in LDS in the planes' frame, then a block arg-max; D's edges (world end points and
+// normals) are staged per step and S's per pair, 36 KB each at the cap, and the edge query runs one pair per thread and
+// pass; the clipping runs one side of the reference loop per pass and one polygon edge per thread, the 0 .. 2 points of
+// each compacted in order by a block scan from one LDS polygon into the other.  Every loop is bounded by vertex, plane,
+// edge or loop counts.  131 KB of LDS: one workgroup per CU.
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -692,12 +731,582 @@ __global__ void __launch_bounds__(PT) settle_kernel(PhysParams P, const PhysShap
   }
 }
 
+// ---- step 3p: polyhedral contacts (pgp_physics_set_polyhedral_contacts) -------------------------------------------------
+// A sibling of settle_kernel, not a third instantiation: the two instantiations above compile from the source they had.
+// Steps 1, 2, 4, 5 and 6 below are that kernel's text; step 3p stands where its steps 3 and 3e stand.
+constexpr int MAXPOLY = 2 * PT;   // polygon and candidate capacity of a pair
+constexpr int EROW = 12;          // floats of a staged edge: world end points (3 + 3), the two world normals (3 + 3)
+
+// block arg-max with lowest-index ties over the (v, i) of all 256 threads; every thread leaves with the winner.
+// sv / si: 4 LDS entries each, free to be overwritten once every thread has arrived
+__device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* si) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off);
+    const int oi = __shfl_xor(i, off);
+    if (better(ov, oi, v, i)) { v = ov; i = oi; }
+  }
+  __syncthreads();
+  if (wave::lane() == 0) si[wave::wave_id()] = i;
+  wave::block4_publish(sv, wave::lane() == 0, v);
+  v = sv[0]; i = si[0];
+  for (int k = 1; k < 4; ++k)
+    if (better(sv[k], si[k], v, i)) { v = sv[k]; i = si[k]; }
+}
+
+// the face query of one body: sep(f) = the least s_f over the other body's vertices loc[0 .. nv) (in this body's frame),
+// one plane per thread; leaves the first maximal sep in bv, its plane in bi and the vertex that attained it (the first
+// minimum) in vtx
+__device__ __forceinline__ void face_query(const float4* pl, int npl, const float4* loc, int nv, int* sepv, float* sv, int* si,
+                                           float& bv, int& bi, int& vtx) {
+  bv = -INFINITY;
+  bi = INT_MAX;
+  for (int f = threadIdx.x; f < npl; f += PT) {
+    const float4 e = pl[f];
+    float mn = INFINITY;
+    int mi = 0;
+    for (int i = 0; i < nv; ++i) {
+      const float4 p = loc[i];
+      const float s = ((e.x * p.x + e.y * p.y) + e.z * p.z) - e.w;
+      if (s < mn) { mn = s; mi = i; }
+    }
+    sepv[f] = mi;
+    if (mn > bv) { bv = mn; bi = f; }
+  }
+  block_argmax(bv, bi, sv, si);
+  vtx = bi < npl ? sepv[bi] : 0;
+}
+
+// the edge axis of one pair (a of D, b of S; ea / eb their staged rows): false when the arcs of their planes' normals do
+// not cross on the Gauss map, when the edges are parallel or when n does not leave S and enter D
+__device__ __forceinline__ bool edge_axis(const float* ea, const float* eb, const int4* rowD, const int4* rowS, const float4* dp,
+                                          const float4* sp, const float* R, const float* B, float* n, float& sep, float* d1,
+                                          float* d2, float* r, float& den) {
+  const float *A = ea + 6, *Bn = ea + 9, *C = eb + 6, *E = eb + 9;
+  float bxa[3], exc[3];
+  cross3(Bn, A, bxa);
+  cross3(E, C, exc);
+  const float cba = dot3(C, bxa), dba = dot3(E, bxa), adc = dot3(A, exc), bdc = dot3(Bn, exc);
+  if (!(cba * dba < 0.f && adc * bdc < 0.f && cba * bdc > 0.f)) return false;
+  for (int i = 0; i < 3; ++i) { d1[i] = ea[3 + i] - ea[i]; d2[i] = eb[3 + i] - eb[i]; r[i] = ea[i] - eb[i]; }
+  const float a = dot3(d1, d1), e = dot3(d2, d2), bq = dot3(d1, d2);
+  const float ae = a * e;
+  den = ae - bq * bq;
+  if (!(den > 1e-6f * ae)) return false;
+  float cr[3];
+  cross3(d1, d2, cr);
+  const float L = fsq(norm2_3(cr[0], cr[1], cr[2]));
+  for (int i = 0; i < 3; ++i) n[i] = fdv(cr[i], L);
+  const int4 ed = *rowD, es = *rowS;
+  const float4 s0 = sp[es.z], s1 = sp[es.w], q0 = dp[ed.z], q1 = dp[ed.w];
+  const float qS[3] = {s0.x + s1.x, s0.y + s1.y, s0.z + s1.z}, qD[3] = {q0.x + q1.x, q0.y + q1.y, q0.z + q1.z};
+  float oS[3], oD[3];
+  for (int i = 0; i < 3; ++i) {
+    oS[i] = (B[3 * i] * qS[0] + B[3 * i + 1] * qS[1]) + B[3 * i + 2] * qS[2];
+    oD[i] = (R[3 * i] * qD[0] + R[3 * i + 1] * qD[1]) + R[3 * i + 2] * qD[2];
+  }
+  float dS = dot3(n, oS), dD = dot3(n, oD);
+  if (dS < 0.f) {
+    for (int i = 0; i < 3; ++i) n[i] = -n[i];
+    dS = -dS; dD = -dD;
+  }
+  if (!(dS > 0.f && dD < 0.f)) return false;
+  sep = dot3(n, r);
+  return true;
+}
+
+__global__ void __launch_bounds__(PT) settle_poly_kernel(PhysParams P, const PhysShape* __restrict__ shapes,
+                                                         const float4* __restrict__ verts, const float4* __restrict__ planes,
+                                                         const int* __restrict__ dyn_shape, const float* T,
+                                                         const int* __restrict__ static_off, const int* __restrict__ static_shape,
+                                                         const float* __restrict__ static_T, float* T_out,
+                                                         pgp_physics_info* __restrict__ info, float* __restrict__ tr_state,
+                                                         float* __restrict__ tr_contacts, int* __restrict__ tr_n,
+                                                         const PhysEdgeSlice* __restrict__ eslice, const int4* __restrict__ edges,
+                                                         const PhysFaceSlice* __restrict__ fslice, const int* __restrict__ foff,
+                                                         const int* __restrict__ fidx, float face_bias) {
+  __shared__ float4 s_dv[MAXV];        // D's hull, body frame
+  __shared__ float4 s_dw[MAXV];        // D's hull, world frame of the step
+  __shared__ float4 s_dp[MAXP];        // D's planes, body frame
+  __shared__ float4 s_sp[MAXP];        // the planes of the pair's static body S, body frame
+  __shared__ float4 s_pa[MAXPOLY];     // the polygon under the clipping; the candidates: point (xyz), depth (w)
+  __shared__ float4 s_pb[MAXPOLY];     // its other half: each pass reads one and writes the other
+  __shared__ float4 s_loc[MAXV];       // the face queries: the other body's vertices in the frame of the planes
+  __shared__ int s_sepv[MAXP];         // the face queries: per plane, the vertex that attained sep
+  __shared__ float s_ed[MAXE * EROW];  // D's edges of the step: a0, a1, A, B (world)
+  __shared__ float s_es[MAXE * EROW];  // S's edges of the pair: b0, b1, C, E (world, the normals negated)
+  __shared__ float s_body[MAXB][12];   // R (row-major) | t of the table and the statics, world frame
+  __shared__ PhysShape s_sh[MAXB + 1]; // [0] = D, [1 + j] = body j
+  __shared__ PhysEdgeSlice s_er[MAXB + 1];
+  __shared__ PhysFaceSlice s_fs[MAXB + 1];
+  __shared__ float4 s_ctp[MAXC], s_ctn[MAXC];
+  __shared__ Row s_rows[3 * MAXC];
+  __shared__ float s_x[3], s_q[4], s_v[3], s_w[3], s_R[9], s_Iw[9], s_Tin[16], s_pn[3];
+  __shared__ int s_ok, s_nb, s_nct, s_pick[4], s_ri[4];
+  __shared__ uint32_t s_sc[4];
+  __shared__ float s_rv[4];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int st = blockIdx.x;
+  if (st >= P.n_states) return;
+
+  if (tid == 0) {
+    int ok = 1;
+    const int dyn = dyn_shape[st];
+    const int o0 = static_off[st], o1 = static_off[st + 1];
+    if (dyn < 0 || dyn >= P.n_shapes || o0 < 0 || o1 < o0 || o1 - o0 > PGP_PHYSICS_MAX_STATICS) ok = 0;
+    if (ok)
+      for (int k = o0; k < o1; ++k)
+        if (static_shape[k] < 0 || static_shape[k] >= P.n_shapes) ok = 0;
+    for (int k = 0; k < 16; ++k) {
+      s_Tin[k] = T[(size_t)st * 16 + k];
+      if (!isfinite(s_Tin[k])) ok = 0;
+    }
+    if (ok) {
+      s_sh[0] = shapes[dyn];
+      s_sh[1] = shapes[0];
+      s_er[0] = eslice[dyn];
+      s_er[1] = eslice[0];
+      s_fs[0] = fslice[dyn];
+      s_fs[1] = fslice[0];
+      for (int i = 0; i < 3; ++i) {
+        for (int c = 0; c < 3; ++c) s_body[0][3 * i + c] = P.table[4 * i + c];
+        s_body[0][9 + i] = P.table[4 * i + 3];
+      }
+      for (int k = o0; k < o1; ++k) {
+        const int b = 1 + (k - o0);
+        s_sh[1 + b] = shapes[static_shape[k]];
+        s_er[1 + b] = eslice[static_shape[k]];
+        s_fs[1 + b] = fslice[static_shape[k]];
+        float Ts[16], W[16];
+        for (int e = 0; e < 16; ++e) Ts[e] = static_T[(size_t)k * 16 + e];
+        if (P.has_cam) mat4_mul(P.cam, Ts, W);
+        else
+          for (int e = 0; e < 16; ++e) W[e] = Ts[e];
+        for (int i = 0; i < 3; ++i) {
+          for (int c = 0; c < 3; ++c) s_body[b][3 * i + c] = W[c * 4 + i];
+          s_body[b][9 + i] = W[12 + i];
+        }
+      }
+      s_nb = 1 + (o1 - o0);
+      float W[16];
+      if (P.has_cam) mat4_mul(P.cam, s_Tin, W);
+      else
+        for (int e = 0; e < 16; ++e) W[e] = s_Tin[e];
+      float R[9];
+      for (int i = 0; i < 3; ++i)
+        for (int c = 0; c < 3; ++c) R[3 * i + c] = W[c * 4 + i];
+      quat_from_R(R, s_q);
+      for (int i = 0; i < 3; ++i) { s_x[i] = W[12 + i]; s_v[i] = 0.f; s_w[i] = 0.f; }
+    }
+    s_ok = ok;
+  }
+  __syncthreads();
+  if (!s_ok || P.steps == 0) {
+    if (tid < 16) T_out[(size_t)st * 16 + tid] = s_ok ? s_Tin[tid] : __int_as_float(0x7fc00000);
+    if (tid == 0 && info) {
+      pgp_physics_info inf;
+      inf.n_contacts = s_ok ? 0 : -1;
+      inf.min_depth = 0.f; inf.lin_speed = 0.f; inf.ang_speed = 0.f;
+      info[st] = inf;
+    }
+    return;
+  }
+  const PhysShape D = s_sh[0];
+  const PhysEdgeSlice Der = s_er[0];
+  const PhysFaceSlice Dfs = s_fs[0];
+  const int nD = min(Der.n_edge, MAXE);
+  for (int i = tid; i < D.n_vert; i += PT) s_dv[i] = verts[D.vert_off + i];
+  for (int f = tid; f < D.n_plane; f += PT) s_dp[f] = planes[D.plane_off + f];
+  const float inv_i[3] = {fdv(1.f, D.inertia[0]), fdv(1.f, D.inertia[1]), fdv(1.f, D.inertia[2])};
+  const int nb = s_nb;
+
+  for (int step = 0; step < P.steps; ++step) {
+    // 1-2: velocities, damping, clamp; R, Iw
+    if (tid == 0) {
+      float* v = s_v; float* w = s_w;
+      for (int i = 0; i < 3; ++i) v[i] = (v[i] + P.dt * P.g[i]) * P.lin_c;
+      for (int i = 0; i < 3; ++i) w[i] = w[i] * P.ang_c;
+      const float L = fsq(norm2_3(w[0], w[1], w[2]));
+      if (L * P.dt > HALF_PI_F) {
+        const float sc = fdv(P.w_max, L);
+        for (int i = 0; i < 3; ++i) w[i] = w[i] * sc;
+      }
+      R_from_q(s_q, s_R);
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+          s_Iw[3 * i + j] = ((s_R[3 * i] * inv_i[0]) * s_R[3 * j] + (s_R[3 * i + 1] * inv_i[1]) * s_R[3 * j + 1]) +
+                            (s_R[3 * i + 2] * inv_i[2]) * s_R[3 * j + 2];
+      s_nct = 0;
+    }
+    __syncthreads();
+    float R[9], x[3];
+    for (int k = 0; k < 9; ++k) R[k] = s_R[k];
+    for (int k = 0; k < 3; ++k) x[k] = s_x[k];
+    for (int i = tid; i < D.n_vert; i += PT) {
+      const float4 a = s_dv[i];
+      s_dw[i] = make_float4(((R[0] * a.x + R[1] * a.y) + R[2] * a.z) + x[0], ((R[3] * a.x + R[4] * a.y) + R[5] * a.z) + x[1],
+                            ((R[6] * a.x + R[7] * a.y) + R[8] * a.z) + x[2], 0.f);
+    }
+    __syncthreads();
+    // D's edges of the step: world end points and the world normals A, B of their two planes
+    for (int e = tid; e < nD; e += PT) {
+      const int4 row = edges[Der.edge_off + e];
+      const float4 a0 = s_dw[row.x], a1 = s_dw[row.y], n0 = s_dp[row.z], n1 = s_dp[row.w];
+      float* o = s_ed + e * EROW;
+      o[0] = a0.x; o[1] = a0.y; o[2] = a0.z; o[3] = a1.x; o[4] = a1.y; o[5] = a1.z;
+      for (int i = 0; i < 3; ++i) {
+        o[6 + i] = (R[3 * i] * n0.x + R[3 * i + 1] * n0.y) + R[3 * i + 2] * n0.z;
+        o[9 + i] = (R[3 * i] * n1.x + R[3 * i + 1] * n1.y) + R[3 * i + 2] * n1.z;
+      }
+    }
+
+    // 3p-4: contacts pair by pair
+    for (int b = 0; b < nb; ++b) {
+      const PhysShape S = s_sh[1 + b];
+      const float* B = s_body[b];
+      const float m = D.margin + S.margin;
+      {
+        const float dx = B[9] - x[0], dy = B[10] - x[1], dz = B[11] - x[2];
+        const float rr = (D.radius + S.radius) + m;
+        if (norm2_3(dx, dy, dz) > rr * rr) continue;   // uniform over the block
+      }
+      const PhysEdgeSlice Ser = s_er[1 + b];
+      const PhysFaceSlice Sfs = s_fs[1 + b];
+      const int nS = min(Ser.n_edge, MAXE);
+      // S's world vertex i
+      const auto s_world = [&](int i, float* p) {
+        const float4 a = verts[S.vert_off + i];
+        for (int c = 0; c < 3; ++c) p[c] = ((B[3 * c] * a.x + B[3 * c + 1] * a.y) + B[3 * c + 2] * a.z) + B[9 + c];
+      };
+      __syncthreads();   // the pair before is done with s_sp, s_loc, s_es and the polygons; s_ed is written
+      for (int f = tid; f < S.n_plane; f += PT) s_sp[f] = planes[S.plane_off + f];
+      // face query of S's planes over D's vertices
+      for (int i = tid; i < D.n_vert; i += PT) {
+        const float4 a = s_dw[i];
+        const float u[3] = {a.x - B[9], a.y - B[10], a.z - B[11]};
+        s_loc[i] = make_float4((B[0] * u[0] + B[3] * u[1]) + B[6] * u[2], (B[1] * u[0] + B[4] * u[1]) + B[7] * u[2],
+                               (B[2] * u[0] + B[5] * u[1]) + B[8] * u[2], 0.f);
+      }
+      __syncthreads();
+      float bvS, bvD;
+      int biS, biD, vS, vD;
+      face_query(s_sp, S.n_plane, s_loc, D.n_vert, s_sepv, s_rv, s_ri, bvS, biS, vS);
+      __syncthreads();
+      // face query of D's planes over S's vertices
+      for (int i = tid; i < S.n_vert; i += PT) {
+        float p[3];
+        s_world(i, p);
+        const float u[3] = {p[0] - x[0], p[1] - x[1], p[2] - x[2]};
+        s_loc[i] = make_float4((R[0] * u[0] + R[3] * u[1]) + R[6] * u[2], (R[1] * u[0] + R[4] * u[1]) + R[7] * u[2],
+                               (R[2] * u[0] + R[5] * u[1]) + R[8] * u[2], 0.f);
+      }
+      __syncthreads();
+      face_query(s_dp, D.n_plane, s_loc, S.n_vert, s_sepv, s_rv, s_ri, bvD, biD, vD);
+      if (bvS >= m || bvD >= m || biS >= S.n_plane || biD >= D.n_plane) continue;   // a separating face; uniform
+
+      // edge query: S's edges of the pair, then one pair per thread and pass
+      for (int e = tid; e < nS; e += PT) {
+        const int4 row = edges[Ser.edge_off + e];
+        const float4 n0 = s_sp[row.z], n1 = s_sp[row.w];
+        float* o = s_es + e * EROW;
+        s_world(row.x, o);
+        s_world(row.y, o + 3);
+        for (int i = 0; i < 3; ++i) {
+          o[6 + i] = -((B[3 * i] * n0.x + B[3 * i + 1] * n0.y) + B[3 * i + 2] * n0.z);
+          o[9 + i] = -((B[3 * i] * n1.x + B[3 * i + 1] * n1.y) + B[3 * i + 2] * n1.z);
+        }
+      }
+      __syncthreads();
+      const int npair = nD * nS;
+      float bvE = -INFINITY;
+      int biE = INT_MAX;
+      for (int pi = tid; pi < npair; pi += PT) {
+        const int ia = pi / nS, ib = pi - ia * nS;
+        float n[3], d1[3], d2[3], r[3], sep, den;
+        if (edge_axis(s_ed + ia * EROW, s_es + ib * EROW, edges + Der.edge_off + ia, edges + Ser.edge_off + ib, s_dp, s_sp, R, B,
+                      n, sep, d1, d2, r, den) &&
+            sep > bvE) {
+          bvE = sep;
+          biE = pi;
+        }
+      }
+      block_argmax(bvE, biE, s_rv, s_ri);
+      const bool has_edge = biE != INT_MAX;
+      if (has_edge && bvE >= m) continue;   // a separating edge axis; uniform
+
+      int cnt = 0;
+      const float4* cand = s_pa;
+      if (has_edge && bvE > fmaxf(bvS, bvD) + face_bias) {
+        // edge contact: the closest point of D's edge, its parameter clamped to the segment
+        if (tid == 0) {
+          const int ia = biE / nS, ib = biE - ia * nS;
+          float n[3], d1[3], d2[3], r[3], sep, den;
+          edge_axis(s_ed + ia * EROW, s_es + ib * EROW, edges + Der.edge_off + ia, edges + Ser.edge_off + ib, s_dp, s_sp, R, B, n,
+                    sep, d1, d2, r, den);
+          const float e = dot3(d2, d2), bq = dot3(d1, d2), c = dot3(d1, r), f = dot3(d2, r);
+          float s = fdv(bq * f - c * e, den);
+          if (s < 0.f) s = 0.f;
+          if (s > 1.f) s = 1.f;
+          const float* a0 = s_ed + ia * EROW;
+          s_pa[0] = make_float4(a0[0] + s * d1[0], a0[1] + s * d1[1], a0[2] + s * d1[2], bvE - m);
+          for (int i = 0; i < 3; ++i) s_pn[i] = n[i];
+        }
+        cnt = 1;
+      } else {
+        // face contact: the reference plane f* of body S (best_S >= best_D) or D, the incident face of the other body
+        const bool refS = bvS >= bvD;
+        const int fr = refS ? biS : biD;
+        const float4 e = refS ? s_sp[fr] : s_dp[fr];
+        const float* Rr = refS ? B : s_R;
+        const float* Ri = refS ? s_R : B;
+        const float tr[3] = {refS ? B[9] : x[0], refS ? B[10] : x[1], refS ? B[11] : x[2]};
+        float N[3];
+        for (int i = 0; i < 3; ++i) N[i] = (Rr[3 * i] * e.x + Rr[3 * i + 1] * e.y) + Rr[3 * i + 2] * e.z;
+        const float4* pli = refS ? s_dp : s_sp;
+        const int npi = refS ? D.n_plane : S.n_plane;
+        float bvI = -INFINITY;
+        int g = INT_MAX;
+        for (int f = tid; f < npi; f += PT) {
+          const float4 q = pli[f];
+          float w[3];
+          for (int i = 0; i < 3; ++i) w[i] = (Ri[3 * i] * q.x + Ri[3 * i + 1] * q.y) + Ri[3 * i + 2] * q.z;
+          const float val = -dot3(N, w);
+          if (val > bvI) { bvI = val; g = f; }
+        }
+        block_argmax(bvI, g, s_rv, s_ri);
+        if (g >= npi) continue;   // every N . n_g is NaN: no contact; uniform
+        // a world vertex of the incident (inc) or the reference body
+        const auto world_of = [&](bool of_S, int i, float* p) {
+          if (of_S) {
+            s_world(i, p);
+          } else {
+            const float4 a = s_dw[i];
+            p[0] = a.x; p[1] = a.y; p[2] = a.z;
+          }
+        };
+        const PhysFaceSlice ifs = refS ? Dfs : Sfs, rfs = refS ? Sfs : Dfs;
+        const int i0 = foff[ifs.off_off + g], r0 = foff[rfs.off_off + fr];
+        int n = min(foff[ifs.off_off + g + 1] - i0, MAXV);
+        const int nr = min(foff[rfs.off_off + fr + 1] - r0, MAXV);
+        const int nvi = refS ? D.n_vert : S.n_vert, nvr = refS ? S.n_vert : D.n_vert;
+        for (int i = tid; i < n; i += PT) {
+          float p[3];
+          world_of(!refS, min(fidx[ifs.idx_off + i0 + i], nvi - 1), p);
+          s_pa[i] = make_float4(p[0], p[1], p[2], 0.f);
+        }
+        __syncthreads();
+        float4 *pa = s_pa, *pb = s_pb;
+        for (int k = 0; k < nr && n > 0; ++k) {
+          float u[3], w[3], kk[3];
+          world_of(refS, min(fidx[rfs.idx_off + r0 + k], nvr - 1), u);
+          world_of(refS, min(fidx[rfs.idx_off + r0 + (k + 1 == nr ? 0 : k + 1)], nvr - 1), w);
+          const float wu[3] = {w[0] - u[0], w[1] - u[1], w[2] - u[2]};
+          cross3(wu, N, kk);
+          uint32_t total = 0;
+          for (int j0 = 0; j0 < n; j0 += PT) {
+            const int j = j0 + tid;
+            uint32_t c = 0;
+            float4 first = make_float4(0.f, 0.f, 0.f, 0.f), second = first;   // a when kept, then the crossing
+            if (j < n) {
+              const float4 a = pa[j], q = pa[j + 1 == n ? 0 : j + 1];
+              const float da[3] = {a.x - u[0], a.y - u[1], a.z - u[2]}, dq[3] = {q.x - u[0], q.y - u[1], q.z - u[2]};
+              const float sa = dot3(kk, da), sb = dot3(kk, dq);
+              const bool ina = sa <= 0.f, inb = sb <= 0.f;
+              if (ina) { first = a; c = 1; }
+              if (ina != inb) {
+                const float t = fdv(sa, sa - sb);
+                second = make_float4(a.x + t * (q.x - a.x), a.y + t * (q.y - a.y), a.z + t * (q.z - a.z), 0.f);
+                if (!ina) first = second;
+                ++c;
+              }
+            }
+            const uint32_t incl = wave::scan_incl(c, lane);
+            wave::block4_publish(s_sc, lane == 63, incl);
+            const uint32_t at = total + wave::block4_offset(s_sc, wv, 0u) + incl - c;
+            // past the capacity: dropped, in output order
+            if (c > 0 && at < (uint32_t)MAXPOLY) pb[at] = first;
+            if (c > 1 && at + 1 < (uint32_t)MAXPOLY) pb[at + 1] = second;
+            total += wave::block4_total(s_sc);
+            __syncthreads();
+          }
+          n = (int)min(total, (uint32_t)MAXPOLY);
+          float4* sw = pa; pa = pb; pb = sw;
+        }
+        if (n == 0) {
+          // nothing left of the incident face: the incident body's vertex that attained sep
+          if (tid == 0) {
+            float p[3];
+            world_of(!refS, refS ? vS : vD, p);
+            pb[0] = make_float4(p[0], p[1], p[2], (refS ? bvS : bvD) - m);
+          }
+          cnt = 1;
+        } else {
+          // candidates: the clipped points below the margin over f*, in output order
+          uint32_t total = 0;
+          for (int j0 = 0; j0 < n; j0 += PT) {
+            const int j = j0 + tid;
+            bool fl = false;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j < n) {
+              a = pa[j];
+              const float u[3] = {a.x - tr[0], a.y - tr[1], a.z - tr[2]};
+              float loc[3];
+              for (int i = 0; i < 3; ++i) loc[i] = (Rr[i] * u[0] + Rr[3 + i] * u[1]) + Rr[6 + i] * u[2];
+              const float s = ((e.x * loc[0] + e.y * loc[1]) + e.z * loc[2]) - e.w;
+              fl = s < m;
+              a.w = s - m;
+            }
+            const unsigned long long bal = __ballot(fl);
+            wave::block4_publish(s_sc, lane == 0, (uint32_t)__popcll(bal));
+            if (fl) pb[wave::block4_rank(s_sc, bal, total)] = a;
+            total += wave::block4_total(s_sc);
+            __syncthreads();
+          }
+          cnt = (int)total;
+        }
+        cand = pb;
+        if (tid == 0)
+          for (int i = 0; i < 3; ++i) s_pn[i] = refS ? N[i] : -N[i];
+      }
+      __syncthreads();
+      if (cnt > 4) {
+        for (int round = 0; round < 4; ++round) {
+          float bv = -INFINITY;
+          int bi = INT_MAX;
+          for (int h = 0; h < 2; ++h) {
+            const int k = h * PT + tid;
+            if (k >= cnt) continue;
+            bool taken = false;
+            for (int r = 0; r < round; ++r) taken |= (s_pick[r] == k);
+            if (taken) continue;
+            const float4 c = cand[k];
+            float val;
+            if (round == 0) {
+              val = -c.w;
+            } else {
+              const float4 p1 = cand[s_pick[0]];
+              const float a[3] = {c.x - p1.x, c.y - p1.y, c.z - p1.z};
+              if (round == 1) {
+                val = norm2_3(a[0], a[1], a[2]);
+              } else {
+                const float4 p2 = cand[s_pick[1]];
+                const float bb[3] = {c.x - p2.x, c.y - p2.y, c.z - p2.z};
+                float o[3];
+                cross3(a, bb, o);
+                val = norm2_3(o[0], o[1], o[2]);
+                if (round == 3) {
+                  const float4 p3 = cand[s_pick[2]];
+                  const float cc[3] = {c.x - p3.x, c.y - p3.y, c.z - p3.z};
+                  float o2[3], o3[3];
+                  cross3(bb, cc, o2);
+                  cross3(cc, a, o3);
+                  val = (val + norm2_3(o2[0], o2[1], o2[2])) + norm2_3(o3[0], o3[1], o3[2]);
+                }
+              }
+            }
+            if (better(val, k, bv, bi)) { bv = val; bi = k; }
+          }
+          block_argmax(bv, bi, s_rv, s_ri);
+          if (tid == 0) s_pick[round] = bi;
+          __syncthreads();
+        }
+      }
+      if (tid == 0) {
+        const int take = cnt > 4 ? 4 : cnt;
+        for (int r = 0; r < take; ++r) {
+          const int k = cnt > 4 ? s_pick[r] : r;
+          s_ctp[s_nct] = cand[k];
+          s_ctn[s_nct] = make_float4(s_pn[0], s_pn[1], s_pn[2], 0.f);
+          ++s_nct;
+        }
+      }
+    }
+    __syncthreads();
+
+    // 5-6: sequential impulses and integration, one lane
+    if (tid == 0) {
+      const int nc = s_nct;
+      float v[3] = {s_v[0], s_v[1], s_v[2]}, w[3] = {s_w[0], s_w[1], s_w[2]};
+      float Iw[9];
+      for (int k = 0; k < 9; ++k) Iw[k] = s_Iw[k];
+      for (int c = 0; c < nc; ++c) {
+        const float4 p = s_ctp[c], n4 = s_ctn[c];
+        const float r[3] = {p.x - x[0], p.y - x[1], p.z - x[2]};
+        const float n[3] = {n4.x, n4.y, n4.z};
+        float tg = fdv((-p.w) * P.erp, P.dt);
+        if (tg < 0.f) tg = 0.f;
+        row_build(s_rows[c], r, n, Iw, tg);
+        float t1[3], t2[3];
+        plane_space(n, t1, t2);
+        row_build(s_rows[MAXC + 2 * c], r, t1, Iw, 0.f);
+        row_build(s_rows[MAXC + 2 * c + 1], r, t2, Iw, 0.f);
+      }
+      for (int it = 0; it < P.iterations; ++it) {
+        for (int c = 0; c < nc; ++c) row_solve(s_rows[c], 0.f, INFINITY, v, w);
+        for (int c = 0; c < nc; ++c) {
+          const float lim = P.mu * s_rows[c].lambda;
+          row_solve(s_rows[MAXC + 2 * c], -lim, lim, v, w);
+          row_solve(s_rows[MAXC + 2 * c + 1], -lim, lim, v, w);
+        }
+      }
+      float q[4] = {s_q[0], s_q[1], s_q[2], s_q[3]};
+      for (int i = 0; i < 3; ++i) x[i] = x[i] + P.dt * v[i];
+      const float o[4] = {(w[0] * q[3] + w[1] * q[2]) - w[2] * q[1], (w[1] * q[3] + w[2] * q[0]) - w[0] * q[2],
+                          (w[2] * q[3] + w[0] * q[1]) - w[1] * q[0], -((w[0] * q[0] + w[1] * q[1]) + w[2] * q[2])};
+      for (int i = 0; i < 4; ++i) q[i] = q[i] + P.half_dt * o[i];
+      const float qn = fsq(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+      for (int i = 0; i < 4; ++i) s_q[i] = fdv(q[i], qn);
+      for (int i = 0; i < 3; ++i) { s_x[i] = x[i]; s_v[i] = v[i]; s_w[i] = w[i]; }
+      if (tr_state) {
+        float* ts = tr_state + (size_t)step * TRACE_STATE;
+        for (int i = 0; i < 3; ++i) ts[i] = s_x[i];
+        for (int i = 0; i < 4; ++i) ts[3 + i] = s_q[i];
+        for (int i = 0; i < 3; ++i) { ts[7 + i] = v[i]; ts[10 + i] = w[i]; }
+        float* tc = tr_contacts + (size_t)step * MAXC * TRACE_CONTACT;
+        for (int c = 0; c < nc; ++c) {
+          const float4 p = s_ctp[c], n4 = s_ctn[c];
+          const float e[8] = {p.x, p.y, p.z, n4.x, n4.y, n4.z, p.w, s_rows[c].lambda};
+          for (int k = 0; k < 8; ++k) tc[c * TRACE_CONTACT + k] = e[k];
+        }
+        tr_n[step] = nc;
+      }
+    }
+    __syncthreads();
+  }
+
+  if (tid == 0) {
+    float R[9], W[16], O[16];
+    R_from_q(s_q, R);
+    for (int i = 0; i < 3; ++i) {
+      for (int c = 0; c < 3; ++c) W[c * 4 + i] = R[3 * i + c];
+      W[12 + i] = s_x[i];
+      W[i * 4 + 3] = 0.f;
+    }
+    W[15] = 1.f;
+    if (P.has_cam) mat4_mul(P.cam_inv, W, O);
+    else
+      for (int e = 0; e < 16; ++e) O[e] = W[e];
+    for (int e = 0; e < 16; ++e) T_out[(size_t)st * 16 + e] = O[e];
+    if (info) {
+      pgp_physics_info inf;
+      const int nc = s_nct;
+      float md = 0.f;
+      for (int c = 0; c < nc; ++c) md = fminf(md, s_ctp[c].w);
+      inf.n_contacts = nc;
+      inf.min_depth = md;
+      inf.lin_speed = fsq(norm2_3(s_v[0], s_v[1], s_v[2]));
+      inf.ang_speed = fsq(norm2_3(s_w[0], s_w[1], s_w[2]));
+      info[st] = inf;
+    }
+  }
+}
+
 }  // namespace
 
 namespace pgp {
 namespace {
 
-// ---- host: convex hull (double) ------------------------------------------------------------------------------------
+// ---- host: convex hull (double)------------------------------------------------------------------------------------
 struct V3 {
   double x, y, z;
 };
@@ -786,7 +1395,7 @@ bool hull_faces(const std::vector<V3>& P, const std::vector<int>& ids, double ep
 }  // namespace
 
 int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>& hv, std::vector<std::array<double, 4>>& pl,
-                     const char* who, std::vector<int4>* edges) {
+                     const char* who, std::vector<int4>* edges, std::vector<int>* loop_off, std::vector<int>* loop_idx) {
   if (!xyz || n < 4 || max_vertices < 4 || max_vertices > MAXV) {
     set_error("%s: bad argument (n = %d, max_vertices = %d of 4 .. %d)", who, n, max_vertices, MAXV);
     return PGP_EINVAL;
@@ -882,6 +1491,36 @@ int convex_hull_impl(const float* xyz, int n, int max_vertices, std::vector<int>
       edges->push_back(make_int4(e.first.first, e.first.second, std::min(f0, f1), std::max(f0, f1)));
     }
   }
+  if (loop_off && loop_idx) {
+    // face loops from the topology: the triangles run counter-clockwise seen from outside, so a directed side whose
+    // reverse belongs to a triangle of another plane is a side of its plane's loop, in loop direction
+    loop_off->assign(1, 0);
+    loop_idx->clear();
+    const auto pos = [&](int v) { return (int)(std::lower_bound(hv.begin(), hv.end(), v) - hv.begin()); };
+    std::map<std::pair<int, int>, int> side;   // directed (va, vb) -> the plane of its triangle
+    for (size_t i = 0; i < faces.size(); ++i) {
+      const int t[3] = {pos(faces[i].a), pos(faces[i].b), pos(faces[i].c)};
+      for (int k = 0; k < 3; ++k) side[{t[k], t[(k + 1) % 3]}] = grp[i];
+    }
+    std::vector<std::map<int, int>> next(pl.size());
+    for (const auto& s : side) {
+      const auto rev = side.find({s.first.second, s.first.first});
+      if (rev == side.end() || rev->second != s.second) next[s.second][s.first.first] = s.first.second;
+    }
+    for (const auto& nx : next) {
+      if (!nx.empty()) {
+        const int first = nx.begin()->first;   // the lowest vertex index of the loop
+        int v = first;
+        for (size_t k = 0; k < nx.size(); ++k) {
+          loop_idx->push_back(v);
+          const auto it = nx.find(v);
+          if (it == nx.end()) break;
+          v = it->second;
+        }
+      }
+      loop_off->push_back((int)loop_idx->size());
+    }
+  }
   return PGP_OK;
 }
 
@@ -892,6 +1531,9 @@ int arena_upload(pgp_ctx* ctx) {
   if ((rc = ctx->d_phys_planes.ensure(ctx->phys_planes.size() * sizeof(float4))) != PGP_OK) return rc;
   if ((rc = ctx->d_phys_eslices.ensure(ctx->phys_eslices.size() * sizeof(PhysEdgeSlice))) != PGP_OK) return rc;
   if ((rc = ctx->d_phys_edges.ensure(ctx->phys_edges.size() * sizeof(int4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_phys_fslices.ensure(ctx->phys_fslices.size() * sizeof(PhysFaceSlice))) != PGP_OK) return rc;
+  if ((rc = ctx->d_phys_face_off.ensure(ctx->phys_face_off.size() * sizeof(int))) != PGP_OK) return rc;
+  if ((rc = ctx->d_phys_face_idx.ensure(ctx->phys_face_idx.size() * sizeof(int))) != PGP_OK) return rc;
   PGP_HIP(hipMemcpy(ctx->d_phys_shapes.p, ctx->phys_shapes.data(), ctx->phys_shapes.size() * sizeof(PhysShape),
                     hipMemcpyHostToDevice));
   PGP_HIP(hipMemcpy(ctx->d_phys_verts.p, ctx->phys_verts.data(), ctx->phys_verts.size() * sizeof(float4), hipMemcpyHostToDevice));
@@ -900,12 +1542,16 @@ int arena_upload(pgp_ctx* ctx) {
   PGP_HIP(hipMemcpy(ctx->d_phys_eslices.p, ctx->phys_eslices.data(), ctx->phys_eslices.size() * sizeof(PhysEdgeSlice),
                     hipMemcpyHostToDevice));
   PGP_HIP(hipMemcpy(ctx->d_phys_edges.p, ctx->phys_edges.data(), ctx->phys_edges.size() * sizeof(int4), hipMemcpyHostToDevice));
+  PGP_HIP(hipMemcpy(ctx->d_phys_fslices.p, ctx->phys_fslices.data(), ctx->phys_fslices.size() * sizeof(PhysFaceSlice),
+                    hipMemcpyHostToDevice));
+  PGP_HIP(hipMemcpy(ctx->d_phys_face_off.p, ctx->phys_face_off.data(), ctx->phys_face_off.size() * sizeof(int), hipMemcpyHostToDevice));
+  PGP_HIP(hipMemcpy(ctx->d_phys_face_idx.p, ctx->phys_face_idx.data(), ctx->phys_face_idx.size() * sizeof(int), hipMemcpyHostToDevice));
   return PGP_OK;
 }
 
 // appends a shape to the host mirror; the radius and inertia follow the rules of include/pgp.h
 void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<float4>& p, const std::vector<int4>& e,
-                  float margin) {
+                  const std::vector<int>& loop_off, const std::vector<int>& loop_idx, float margin) {
   PhysShape s{};
   s.vert_off = (int)ctx->phys_verts.size();
   s.n_vert = (int)v.size();
@@ -934,6 +1580,21 @@ void arena_append(pgp_ctx* ctx, const std::vector<float4>& v, const std::vector<
   ctx->phys_verts.insert(ctx->phys_verts.end(), v.begin(), v.end());
   ctx->phys_planes.insert(ctx->phys_planes.end(), p.begin(), p.end());
   ctx->phys_edges.insert(ctx->phys_edges.end(), e.begin(), e.end());
+  ctx->phys_fslices.push_back(PhysFaceSlice{(int)ctx->phys_face_off.size(), (int)ctx->phys_face_idx.size()});
+  ctx->phys_face_off.insert(ctx->phys_face_off.end(), loop_off.begin(), loop_off.end());
+  ctx->phys_face_idx.insert(ctx->phys_face_idx.end(), loop_idx.begin(), loop_idx.end());
+}
+
+void arena_pop(pgp_ctx* ctx) {
+  if (ctx->phys_shapes.empty()) return;
+  ctx->phys_verts.resize(ctx->phys_shapes.back().vert_off);
+  ctx->phys_planes.resize(ctx->phys_shapes.back().plane_off);
+  ctx->phys_edges.resize(ctx->phys_eslices.back().edge_off);
+  ctx->phys_face_off.resize(ctx->phys_fslices.back().off_off);
+  ctx->phys_face_idx.resize(ctx->phys_fslices.back().idx_off);
+  ctx->phys_shapes.pop_back();
+  ctx->phys_eslices.pop_back();
+  ctx->phys_fslices.pop_back();
 }
 
 int check_options(const pgp_physics_options* o, const char* who, int max_steps) {
@@ -995,6 +1656,16 @@ int launch_settle(pgp_ctx* ctx, const PhysParams& P, const int* d_dyn, const flo
                   const int* d_ss, const float* d_sT, float* d_out, pgp_physics_info* d_info, float* tr_s, float* tr_c,
                   int* tr_n, hipStream_t st) {
   if (P.n_states == 0) return PGP_OK;
+  // pgp_physics_set_polyhedral_contacts on: step 3p, whatever the edge switch says
+  if (ctx->phys_poly_contacts) {
+    hipLaunchKernelGGL(settle_poly_kernel, dim3(P.n_states), dim3(PT), 0, st, P, ctx->d_phys_shapes.as<PhysShape>(),
+                       ctx->d_phys_verts.as<float4>(), ctx->d_phys_planes.as<float4>(), d_dyn, d_T, d_off, d_ss, d_sT, d_out,
+                       d_info, tr_s, tr_c, tr_n, ctx->d_phys_eslices.as<PhysEdgeSlice>(), ctx->d_phys_edges.as<int4>(),
+                       ctx->d_phys_fslices.as<PhysFaceSlice>(), ctx->d_phys_face_off.as<int>(), ctx->d_phys_face_idx.as<int>(),
+                       ctx->phys_face_bias);
+    PGP_HIP(hipGetLastError());
+    return PGP_OK;
+  }
   // the context's switch picks the instantiation (pgp_physics_set_edge_contacts); off: the vertex-face kernel
   auto* kernel = ctx->phys_edge_contacts ? settle_kernel<true> : settle_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3(P.n_states), dim3(PT), 0, st, P, ctx->d_phys_shapes.as<PhysShape>(),
@@ -1060,10 +1731,12 @@ int physics_arena_init(pgp_ctx* ctx) {
       e.push_back(make_int4(i, i | (1 << ax), 2 * o0 + (i & (1 << o0) ? 0 : 1), 2 * o1 + (i & (1 << o1) ? 0 : 1)));
     }
   std::sort(e.begin(), e.end(), [](const int4& a, const int4& b) { return a.x != b.x ? a.x < b.x : a.y < b.y; });
-  arena_append(ctx, v, p, e, 0.f);
+  // its six quads, counter-clockwise seen from outside, each from its lowest vertex
+  const std::vector<int> loop_off = {0, 4, 8, 12, 16, 20, 24};
+  const std::vector<int> loop_idx = {1, 3, 7, 5, 0, 4, 6, 2, 2, 6, 7, 3, 0, 1, 5, 4, 4, 5, 7, 6, 0, 2, 3, 1};
+  arena_append(ctx, v, p, e, loop_off, loop_idx, 0.f);
   const int rc = arena_upload(ctx);
-  if (rc != PGP_OK) ctx->phys_shapes.clear(), ctx->phys_verts.clear(), ctx->phys_planes.clear(), ctx->phys_edges.clear(),
-                      ctx->phys_eslices.clear();
+  if (rc != PGP_OK) arena_pop(ctx);
   return rc;
 }
 

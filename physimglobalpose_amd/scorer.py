@@ -22,6 +22,7 @@ _f = C.POINTER(C.c_float)
 _i = C.POINTER(C.c_int)
 PHYSICS_MAX_EDGES = 3 * 256 - 6          # PGP_PHYSICS_MAX_EDGES
 PHYSICS_EDGE_REACH_DEFAULT = 0.01        # PGP_PHYSICS_EDGE_REACH_DEFAULT
+PHYSICS_FACE_BIAS_DEFAULT = 0.001        # PGP_PHYSICS_FACE_BIAS_DEFAULT
 
 
 def _fp(a):
@@ -1666,6 +1667,22 @@ class LcpScorer:
         """pgp_physics_set_edge_contacts: edge-edge contacts in every later settle, trace and MCTS search of this
         context (off by default); reach in metres, > 0."""
         _lib.check(self._lib.pgp_physics_set_edge_contacts(self._h, int(bool(on)), C.c_float(reach)))
+
+    def physics_shape_faces(self, shape_id):
+        """pgp_physics_shape_faces: the face loops the device holds for a shape -> (offsets (f + 1,), vertices) int32;
+        plane i's loop is vertices[offsets[i]:offsets[i + 1]], counter-clockwise seen from outside, indices into
+        physics_shape_info's verts."""
+        off = np.zeros(2 * 256 + 1, np.int32)
+        idx = np.zeros(2 * PHYSICS_MAX_EDGES, np.int32)
+        n = C.c_int(0)
+        _lib.check(self._lib.pgp_physics_shape_faces(self._h, int(shape_id), off.ctypes.data_as(_i), idx.ctypes.data_as(_i), C.byref(n)))
+        return off[:n.value + 1].copy(), idx[:off[n.value]].copy()
+
+    def physics_set_polyhedral_contacts(self, on=True, face_bias=PHYSICS_FACE_BIAS_DEFAULT):
+        """pgp_physics_set_polyhedral_contacts: separating-axis contacts with face clipping in every later settle, trace
+        and MCTS search of this context, in place of the vertex-face and the edge-edge rule (off by default); face_bias
+        in metres, >= 0."""
+        _lib.check(self._lib.pgp_physics_set_polyhedral_contacts(self._h, int(bool(on)), C.c_float(face_bias)))
 
     @staticmethod
     def _statics(statics, n):

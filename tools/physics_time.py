@@ -5,8 +5,11 @@ is tested).  Prints median and p99 of `--reps` calls per cell, plus the per-stat
 The `edge` columns time the device form again with pgp_physics_set_edge_contacts on (default reach); two more groups
 of rows hold the scenes that need it: a bar dropped across a bar, and the 256-vertex ellipsoid of the tests resting on
 the 200-vertex one.  --no-edges leaves the switch alone and prints the vertex-face columns only.
+The `poly` columns time the device form once more with pgp_physics_set_polyhedral_contacts on (default face_bias), with
+its ratios to the vertex-face and the edge-edge medians of the same process; a last group of rows drops a 2 mm plate
+across an identical one.  --no-poly leaves that switch alone.
 
-    python tools/physics_time.py [--reps 20] [--no-edges]"""
+    python tools/physics_time.py [--reps 20] [--no-edges] [--no-poly]"""
 import argparse
 import os
 import sys
@@ -55,7 +58,14 @@ def ellipsoid_states(e256, e200, n, seed):
     return np.full(n, e256, np.int32), T, [[(e200, R.pose(Bm, (0.0, 0.0, 0.06)))] for _ in range(n)]
 
 
-def time_cell(s, torch, dev, table, reps, edges, label, n_static, dyn, T, statics):
+def plate_states(plate, n, seed):
+    """A 20 x 4 cm plate 2 mm thick dropped across an identical one from 1 cm, at a random yaw of 30 .. 150 degrees."""
+    rng = np.random.default_rng(seed)
+    T = np.stack([R.pose(R.rot("z", float(rng.uniform(30, 150))), (0.0, 0.0, 0.013)) for _ in range(n)])
+    return np.full(n, plate, np.int32), T, [[(plate, R.pose(t=(0.0, 0.0, 0.001)))] for _ in range(n)]
+
+
+def time_cell(s, torch, dev, table, reps, edges, poly, label, n_static, dyn, T, statics):
     n = len(dyn)
     out, info = s.physics_settle(dyn, T, table, statics=statics)   # warm-up
     host = []
@@ -94,6 +104,16 @@ def time_cell(s, torch, dev, table, reps, edges, label, n_static, dyn, T, static
             s.physics_set_edge_contacts(False)
         row += (f" | {np.median(edget):8.3f} {np.percentile(edget, 99):8.3f} {np.median(edget) / np.median(devt):6.2f} "
                 f"{einfo['n_contacts'].mean():9.2f}")
+    if poly:
+        s.physics_set_polyhedral_contacts(True)
+        try:
+            polyt = device_times()
+            _, pinfo = s.physics_settle(dyn, T, table, statics=statics)
+        finally:
+            s.physics_set_polyhedral_contacts(False)
+        row += f" | {np.median(polyt):8.3f} {np.percentile(polyt, 99):8.3f} {np.median(polyt) / np.median(devt):6.2f} "
+        row += f"{np.median(polyt) / np.median(edget):6.2f} " if edges else f"{'':>6} "
+        row += f"{pinfo['n_contacts'].mean():9.2f}"
     print(row, flush=True)
 
 
@@ -101,20 +121,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-edges", action="store_true", help="vertex-face columns only: the switch is never touched")
+    ap.add_argument("--no-poly", action="store_true", help="no polyhedral columns: that switch is never touched")
     args = ap.parse_args()
     import torch
     s = LcpScorer(0)
     table = R.table_params(0.0)
     dev = torch.device("cuda", 0)
     edges = not args.no_edges
+    poly = not args.no_poly
     print(f"# {torch.cuda.get_device_name(0)}; default options (60 steps, 10 iterations); ms per call, median / p99 of "
           f"{args.reps}")
     head = (f"{'hull':>5} {'statics':>7} {'states':>6} | {'host med':>9} {'host p99':>9} | {'dev med':>8} {'dev p99':>8} | "
             f"{'contacts/state':>14}")
     if edges:
         head += f" | {'edge med':>8} {'edge p99':>8} {'x off':>6} {'contacts':>9}"
+    if poly:
+        head += f" | {'poly med':>8} {'poly p99':>8} {'x off':>6} {'x edge':>6} {'contacts':>9}"
     print(head)
-    cell = lambda *a: time_cell(s, torch, dev, table, args.reps, edges, *a)
+    cell = lambda *a: time_cell(s, torch, dev, table, args.reps, edges, poly, *a)
     for nv in (64, 256):
         sid = s.physics_add_shape(hull_cloud(nv, nv), margin=0.001, max_vertices=256)
         got = len(s.physics_shape_info(sid)["verts"])
@@ -128,6 +152,9 @@ def main():
         cell("bars", 1, *crossed_states(bar, n, seed=n))
     for n in (1, 64, 256, 1024):
         cell("ell", 1, *ellipsoid_states(e256, e200, n, seed=n))
+    plate = s.physics_add_shape(R.box_points(0.10, 0.02, 0.001), margin=0.001)
+    for n in (1, 64, 256, 1024):
+        cell("plate", 1, *plate_states(plate, n, seed=n))
 
 
 if __name__ == "__main__":
