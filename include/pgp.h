@@ -1484,6 +1484,71 @@ int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_ob
                     int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
                     int trace_cap, int* n_trace);
 
+/* ---- trimmed-ICP refinement of MCTS child states: UCTState::performTrICP --------------------------------------------
+ * Replaces UCTState::performTrICP (UCTState.cpp:137-139, 142-174, 194; called at UCTSearch.cpp:98, 157, 225 between
+ * updateNewObject and correctPhysics).  One launch refines n states, ONE workgroup per state from the unexplained
+ * filter to the final pose (csrc/tricp_states.hip, restated by tests/_tricp_restate.py).  Per state:
+ *   1. unexplained filter: a point of the object's segment is dropped when any point of any static's model, placed at
+ *      that static's pose, lies strictly within removal_radius (pgp_unexplained_segment's arithmetic; every static
+ *      with its OWN model); skipped without statics or with removal_radius <= 0.  The kept points keep their order.
+ *   2. guess G = rigid inverse of T (camera -> object), float64, rounded once;
+ *   3. TrimmedICP of the kept points onto the object's model (pgp_icp_refine's definition, trimmed form):
+ *      k = (int)|trim_fraction * (float)n_kept| clamped to [1, n_kept], exhaustive nearest neighbours, the k smallest
+ *      distances (ties: lowest source index), Horn's closed form, while E / E_old < energy_ratio;
+ *   4. T <- rigid inverse of G.
+ * The library's own rules: k < 3 (n_kept == 0 included) leaves the state exactly as it came (T bit for bit, iters 0,
+ * energy 0); a non-finite pose, an unknown object index or more than 16 statics gives a NaN T and iters = -1 in the
+ * device call (the host call refuses them); a model of one or two points leaves the rotation about it undetermined: the
+ * result is then some proper rigid pose that puts the selected points' centroid on their targets' (n_kept, iters and
+ * energy are what they are for any such pose).  Exhaustive search: no index of the target yet.
+ * With trim_fraction 0.5 on a segment that overlaps its model completely TrimmedICP can stall some degrees from the
+ * optimum (the half it keeps is already at rest); 0.9 recovers 5 mm / 5 degree offsets. */
+#define PGP_TRICP_MAX_SEGMENT 4096   /* points of one object's segment */
+#define PGP_TRICP_MAX_STATICS 16     /* placed objects of one state */
+#define PGP_TRICP_MAX_MODEL 65535    /* points of one object's model */
+typedef struct {
+  float trim_fraction;    /* 0.5 = trimICPthreshold (UCTSearch.cpp:9); (0, 1] */
+  float removal_radius;   /* 0.008 = pointRemovalThreshold (UCTState.cpp:9); <= 0: no filter */
+  float energy_ratio;     /* 1.0 (UCTState.cpp:139) */
+  int max_iterations;     /* <= 0: 100; at most 1000 */
+} pgp_tricp_options;
+typedef struct {
+  const float* model_xyz;     /* n_model x 3 floats, object frame; host */
+  int n_model;                /* 1 .. PGP_TRICP_MAX_MODEL */
+  const float* segment_xyz;   /* n_segment x 3 floats, camera frame; host */
+  int n_segment;              /* 0 .. PGP_TRICP_MAX_SEGMENT */
+} pgp_tricp_object;
+int pgp_tricp_default_options(pgp_tricp_options* opt);
+/* Copies the clouds of n_obj objects to the device; replaces an earlier set; n_obj == 0 frees them.  The call drains the
+ * device first (launches of pgp_tricp_states_device still queued on a caller's stream read the set that is replaced);
+ * it must not be made while a stream is capturing.  Coordinates are not checked for being finite: a segment point with a
+ * NaN, an infinite or a huge coordinate (its squared distances are NaN or overflow) is never explained by a static, finds
+ * no neighbour (d2 = FLT_MAX), is ranked last by the trim and never enters a sum; a model point of that kind explains
+ * nothing and is nobody's nearest neighbour.  PGP_EINVAL: an empty or oversized model, a segment over the limit,
+ * a NULL cloud (the earlier set stays). */
+int pgp_tricp_set_objects(pgp_ctx* ctx, const pgp_tricp_object* objs, int n_obj);
+/* Refines n_states states: state i is object obj[i] at T[i] (16 floats column-major, object -> camera, in/out) among
+ * the statics (static_obj[j], static_T[j]), j in [static_offsets[i], static_offsets[i + 1]).  energy (the last
+ * iteration's mean squared distance of the selected pairs), iters and n_kept are nullable.  opt NULL: the defaults.
+ * Host pointers, synchronous.  PGP_ESTATE: no object set.  PGP_EINVAL with a message: an object index out of range,
+ * more than 16 statics, a non-finite pose, non-finite or out-of-range options. */
+int pgp_tricp_states(pgp_ctx* ctx, const pgp_tricp_options* opt, int n_states, const int* obj, float* T,
+                     const int* static_offsets, const int* static_obj, const float* static_T, float* energy, int* iters,
+                     int* n_kept);
+/* The same with DEVICE arrays, enqueued on `stream`: no synchronisation, no allocation.  The states are checked on the
+ * device: a bad one gets a NaN T, iters = -1, energy = 0 and n_kept = 0.  d_static_obj and d_static_T may be NULL only
+ * together and only when NO state of the batch has statics (the ranges are on the device, the host cannot look): then a
+ * state whose range is not empty is a bad state. */
+int pgp_tricp_states_device(pgp_ctx* ctx, const pgp_tricp_options* opt, int n_states, const int* d_obj, float* d_T,
+                            const int* d_static_offsets, const int* d_static_obj, const float* d_static_T,
+                            float* d_energy, int* d_iters, int* d_n_kept, void* stream);
+/* The switch, in the style of pgp_physics_set_edge_contacts: every later pgp_mcts_search of the context runs
+ * pgp_tricp_states' kernel on each state that adds an object, before it is settled (object l of the search is object
+ * l of the set, its statics the objects 0 .. l-1 at their settled poses).  opt NULL: the defaults; on == 0: off (the
+ * default): the search's launches are exactly those without this call.  While on, pgp_mcts_search returns PGP_EINVAL
+ * when the context holds no object set or one whose count differs from n_obj. */
+int pgp_mcts_set_tricp(pgp_ctx* ctx, int on, const pgp_tricp_options* opt);
+
 /* ---- several GPUs of one node (north_star; SceneCfg.cpp:376-406 and
  * HypothesisSelection.cpp:248-257 are the consumers) -----------------------------------------------
  * A pgp_multi is a group of devices in ONE process: one pgp_ctx, one host thread and one stream per

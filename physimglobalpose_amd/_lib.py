@@ -126,6 +126,20 @@ class PhysicsInfo(C.Structure):
     _fields_ = [("n_contacts", C.c_int), ("min_depth", C.c_float), ("lin_speed", C.c_float), ("ang_speed", C.c_float)]
 
 
+class TricpOptions(C.Structure):
+    _fields_ = [("trim_fraction", C.c_float), ("removal_radius", C.c_float), ("energy_ratio", C.c_float),
+                ("max_iterations", C.c_int)]
+
+
+class TricpObject(C.Structure):
+    _fields_ = [("model_xyz", C.POINTER(C.c_float)), ("n_model", C.c_int), ("segment_xyz", C.POINTER(C.c_float)),
+                ("n_segment", C.c_int)]
+
+
+PGP_TRICP_MAX_SEGMENT = 4096
+PGP_TRICP_MAX_STATICS = 16
+PGP_TRICP_MAX_MODEL = 65535
+
 PGP_MCTS_ROLLOUT_RANDOM = 0
 PGP_MCTS_ROLLOUT_LCP = 1
 PGP_MCTS_MAX_OBJECTS = 17
@@ -395,6 +409,12 @@ SIGNATURES = {
     "pgp_mcts_default_options": (C.c_int, [C.c_void_p]),
     "pgp_mcts_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _f, _f, C.POINTER(Camera), _f, _i, _f, _f,
                                   C.c_void_p, C.c_void_p, C.c_int, _i]),
+    "pgp_tricp_default_options": (C.c_int, [C.POINTER(TricpOptions)]),
+    "pgp_tricp_set_objects": (C.c_int, [C.c_void_p, C.POINTER(TricpObject), C.c_int]),
+    "pgp_tricp_states": (C.c_int, [C.c_void_p, C.POINTER(TricpOptions), C.c_int, _i, _f, _i, _i, _f, _f, _i, _i]),
+    "pgp_tricp_states_device": (C.c_int, [C.c_void_p, C.POINTER(TricpOptions), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgp_mcts_set_tricp": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TricpOptions)]),
     "pgp_sample_mesh": (C.c_int, [C.c_void_p, _f, C.c_int, C.c_int, _i, C.c_int, C.c_int, C.c_ulonglong, _f, _f, _i]),
     "pgp_sample_mesh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_ulonglong,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

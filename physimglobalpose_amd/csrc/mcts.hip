@@ -41,6 +41,8 @@
 // Device side of a step, for levels l = 0 .. n_obj-1 (each slot = one evaluated descent, one full leaf state):
 //   mcts_gather   builds the settle inputs of the states that ADD object l this step (expanded children of depth
 //                 l + 1 and rollout levels): the hypothesis pose from HBM, the statics = the slot's poses of levels < l.
+//   tricp_states  only with pgp_mcts_set_tricp on: one launch refines the gathered poses in place against the slot's
+//                 placed objects (tricp_states.hip: performTrICP, UCTSearch.cpp:98, 157, 225); off: not launched.
 //   settle_kernel one launch for all of them (physics.hip).
 //   mcts_scatter  writes each slot's pose of level l (settled now, or an ancestor's from the node-pose arena) into the
 //                 slot's pose table and the render batch, and new nodes' settled poses into the arena.
@@ -209,6 +211,13 @@ int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_o
     n_hyp[l] = o.n_hyp;
     hyp_off[l + 1] = hyp_off[l] + o.n_hyp;
     shape[l] = o.shape_id;
+  }
+  // pgp_mcts_set_tricp: object l of the search is object l of the resident set
+  const bool tricp = ctx->mcts_tricp;
+  if (tricp && ctx->tricp_n_obj != n_obj) {
+    set_error("%s: trimmed ICP is switched on and the context holds %d objects (pgp_tricp_set_objects), the search %d", who,
+              ctx->tricp_n_obj, n_obj);
+    return PGP_EINVAL;
   }
   // stop limits: the reference's sum_{i=0..n_obj} 25^i, clamped; the tree's node count (saturating)
   long long max_exp = opt->max_expansions;
@@ -467,6 +476,11 @@ int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_o
           hipLaunchKernelGGL(mcts_gather, dim3(ns), dim3(64), 0, st, l, n_obj, (const int*)d_shape, d_list, ns,
                              (const float*)d_hypT, (const float*)d_slot_pose, d_dyn, d_T, d_off, d_ss, d_sT);
           PGP_HIP(hipGetLastError());
+          // performTrICP (UCTSearch.cpp:98, 157, 225: expand, defaultPolicy, LCPPolicy): every state the level settles is
+          // refined first, in place, against its slot's placed objects 0 .. l-1
+          if (tricp && (rc = launch_tricp_states(ctx, ctx->mcts_tricp_opt, ns, nullptr, l, d_T, d_off, nullptr, d_sT, nullptr,
+                                                 nullptr, nullptr, st)) != PGP_OK)
+            return rc;
           P.n_states = ns;
           if ((rc = launch_settle(ctx, P, d_dyn, d_T, d_off, d_ss, d_sT, d_out, nullptr, nullptr, nullptr, nullptr, st)) != PGP_OK)
             return rc;

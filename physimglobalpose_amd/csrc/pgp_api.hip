@@ -263,6 +263,7 @@ int pgp_destroy(pgp_ctx* ctx) {
                     &ctx->d_scores, &ctx->d_counts, &ctx->d_best, &ctx->d_rec_ws, &ctx->d_hits, &ctx->d_seq, &ctx->d_Qs, &ctx->d_ids,
                     &ctx->d_rig, &ctx->d_icp_src, &ctx->d_icp_tgt, &ctx->d_icp_tgt_n, &ctx->d_icp_grid, &ctx->d_icp_T, &ctx->d_icp_out, &ctx->d_icp_ws, &ctx->d_icp_x, &ctx->d_Qs_unit, &ctx->d_cs_cnt, &ctx->d_cs_entries, &ctx->d_cs_keys,
                     &ctx->d_cs_pairs, &ctx->d_cs_out, &ctx->d_ppf_keys, &ctx->d_ppf_val, &ctx->d_ppf_off, &ctx->d_ppf_pairs, &ctx->d_prob_cdf, &ctx->d_sel_ws, &ctx->d_csb, &ctx->d_csb_picks, &ctx->d_pre_ws, &ctx->d_vg_ws, &ctx->d_mls_ws, &ctx->d_plane_ws, &ctx->d_plane_io, &ctx->d_cc_ws, &ctx->d_cc_io, &ctx->d_crease_ws, &ctx->d_ppf_model, &ctx->d_ppf_alpha, &ctx->d_ppf_ws, &ctx->d_ppf_io, &ctx->d_phys_shapes, &ctx->d_phys_verts, &ctx->d_phys_planes, &ctx->d_phys_io, &ctx->d_mcts_ws, &ctx->d_mcts_img, &ctx->d_pre_io, &ctx->d_depth, &ctx->d_render_ws, &ctx->d_render_io, &ctx->d_cl_keys, &ctx->d_cl_ws, &ctx->d_cl_io, &ctx->d_bp, &ctx->d_top_ws, &ctx->d_pub_ticket,
+                    &ctx->d_tricp_clouds, &ctx->d_tricp_objs, &ctx->d_tricp_io,
                     &ctx->d_v4_sel, &ctx->d_v4_mat, &ctx->d_v4_ws, &ctx->d_v4_quads, &ctx->d_v4_picks, &ctx->d_v4_io,
                     &ctx->d_s4_sel, &ctx->d_s4_ws, &ctx->d_s4_pairs, &ctx->d_s4_io, &ctx->d_Prgb, &ctx->d_Qs_nrm, &ctx->d_Qs_rgb,
                     &ctx->d_prep_ws, &ctx->d_fps_ws, &ctx->d_prep_io,
@@ -4045,6 +4046,198 @@ int pgp_mcts_search(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_ob
   CtxGuard guard(ctx);
   return mcts_search_impl(ctx, opt, objs, n_obj, table_params, cam_pose, cam, observed, best_hyp, best_T, best_score,
                           info, trace, trace_cap, n_trace);
+}
+
+}  // extern "C"
+
+// ---- trimmed ICP of MCTS states (tricp_states.hip) ------------------------------------------------------------------
+extern "C" {
+
+int pgp_tricp_default_options(pgp_tricp_options* opt) {
+  if (!opt) {
+    set_error("pgp_tricp_default_options: null");
+    return PGP_EINVAL;
+  }
+  opt->trim_fraction = 0.5f;     // trimICPthreshold (UCTSearch.cpp:9)
+  opt->removal_radius = 0.008f;  // pointRemovalThreshold (UCTState.cpp:9)
+  opt->energy_ratio = 1.0f;      // UCTState.cpp:139
+  opt->max_iterations = 100;
+  return PGP_OK;
+}
+
+int pgp_tricp_set_objects(pgp_ctx* ctx, const pgp_tricp_object* objs, int n_obj) {
+  const char* who = "pgp_tricp_set_objects";
+  if (!ctx || n_obj < 0 || (n_obj > 0 && !objs)) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  size_t n_pts = 0;
+  int max_seg = 0;
+  for (int l = 0; l < n_obj; ++l) {
+    const pgp_tricp_object& o = objs[l];
+    if (o.n_model < 1 || o.n_model > PGP_TRICP_MAX_MODEL || !o.model_xyz) {
+      set_error("%s: object %d has a model of %d points (1 .. %d expected)", who, l, o.n_model, PGP_TRICP_MAX_MODEL);
+      return PGP_EINVAL;
+    }
+    if (o.n_segment < 0 || o.n_segment > PGP_TRICP_MAX_SEGMENT || (o.n_segment > 0 && !o.segment_xyz)) {
+      set_error("%s: object %d has a segment of %d points (0 .. %d expected)", who, l, o.n_segment, PGP_TRICP_MAX_SEGMENT);
+      return PGP_EINVAL;
+    }
+    n_pts += (size_t)o.n_model + (size_t)o.n_segment;
+    max_seg = std::max(max_seg, o.n_segment);
+  }
+  CtxGuard guard(ctx);
+  hipStream_t st = ctx->stream;
+  // nothing may still read the set that is replaced: a pgp_tricp_states_device launch queued on a caller's stream reads
+  // the clouds through the resident table, so the whole device is drained, not the context's stream alone
+  PGP_HIP(hipDeviceSynchronize());
+  ctx->device_work_pending = false;
+  ctx->tricp_n_obj = 0;
+  ctx->tricp_max_seg = 0;
+  if (n_obj == 0) {
+    ctx->d_tricp_clouds.release();
+    ctx->d_tricp_objs.release();
+    return PGP_OK;
+  }
+  int rc;
+  if ((rc = ctx->d_tricp_clouds.ensure(n_pts * sizeof(float4))) != PGP_OK) return rc;
+  if ((rc = ctx->d_tricp_objs.ensure((size_t)n_obj * sizeof(TricpObject))) != PGP_OK) return rc;
+  std::vector<float4> h(n_pts);
+  std::vector<TricpObject> tab((size_t)n_obj);
+  float4* d = ctx->d_tricp_clouds.as<float4>();
+  size_t at = 0;
+  for (int l = 0; l < n_obj; ++l) {
+    const pgp_tricp_object& o = objs[l];
+    tab[l].model = d + at;
+    tab[l].n_model = o.n_model;
+    for (int i = 0; i < o.n_model; ++i) h[at++] = make_float4(o.model_xyz[3 * i], o.model_xyz[3 * i + 1], o.model_xyz[3 * i + 2], 0.f);
+    tab[l].seg = d + at;
+    tab[l].n_seg = o.n_segment;
+    for (int i = 0; i < o.n_segment; ++i)
+      h[at++] = make_float4(o.segment_xyz[3 * i], o.segment_xyz[3 * i + 1], o.segment_xyz[3 * i + 2], 0.f);
+  }
+  PGP_HIP(hipMemcpyAsync(d, h.data(), n_pts * sizeof(float4), hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(ctx->d_tricp_objs.p, tab.data(), (size_t)n_obj * sizeof(TricpObject), hipMemcpyHostToDevice, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  ctx->tricp_n_obj = n_obj;
+  ctx->tricp_max_seg = max_seg;
+  return PGP_OK;
+}
+
+int pgp_tricp_states(pgp_ctx* ctx, const pgp_tricp_options* opt, int n_states, const int* obj, float* T,
+                     const int* static_offsets, const int* static_obj, const float* static_T, float* energy, int* iters,
+                     int* n_kept) {
+  const char* who = "pgp_tricp_states";
+  if (!ctx || n_states < 0 || (n_states > 0 && (!obj || !T || !static_offsets))) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  pgp_tricp_options o;
+  int rc = check_tricp_options(opt, who, o);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx);
+  if (ctx->tricp_n_obj <= 0) {
+    set_error("%s: no object set (pgp_tricp_set_objects)", who);
+    return PGP_ESTATE;
+  }
+  if (n_states == 0) return PGP_OK;
+  if (static_offsets[0] != 0) {
+    set_error("%s: static_offsets[0] must be 0", who);
+    return PGP_EINVAL;
+  }
+  for (int i = 0; i < n_states; ++i) {
+    const int ns = static_offsets[i + 1] - static_offsets[i];
+    if (obj[i] < 0 || obj[i] >= ctx->tricp_n_obj) {
+      set_error("%s: state %d names object %d of %d", who, i, obj[i], ctx->tricp_n_obj);
+      return PGP_EINVAL;
+    }
+    if (ns < 0 || ns > PGP_TRICP_MAX_STATICS) {
+      set_error("%s: state %d has %d statics (0 .. %d expected)", who, i, ns, PGP_TRICP_MAX_STATICS);
+      return PGP_EINVAL;
+    }
+    if (ns > 0 && (!static_obj || !static_T)) {
+      set_error("%s: bad argument", who);
+      return PGP_EINVAL;
+    }
+    for (int q = 0; q < 16; ++q)
+      if (!std::isfinite(T[16 * (size_t)i + q])) {
+        set_error("%s: state %d has a non-finite pose", who, i);
+        return PGP_EINVAL;
+      }
+    for (int j = static_offsets[i]; j < static_offsets[i + 1]; ++j)
+      if (static_obj[j] < 0 || static_obj[j] >= ctx->tricp_n_obj) {
+        set_error("%s: state %d names static object %d of %d", who, i, static_obj[j], ctx->tricp_n_obj);
+        return PGP_EINVAL;
+      }
+  }
+  const size_t n = (size_t)n_states, m = (size_t)static_offsets[n_states];
+  Carve cv;
+  const auto p_obj = cv.add<int>(n, 256);
+  const auto p_T = cv.add<float>(n * 16, 256);
+  const auto p_off = cv.add<int>(n + 1, 256);
+  const auto p_so = cv.add<int>(std::max<size_t>(m, 1), 256);
+  const auto p_sT = cv.add<float>(std::max<size_t>(m, 1) * 16, 256);
+  const auto p_e = cv.add<float>(n, 256);
+  const auto p_it = cv.add<int>(n, 256);
+  const auto p_nk = cv.add<int>(n, 256);
+  if ((rc = cv.ensure(ctx->d_tricp_io)) != PGP_OK) return rc;
+  hipStream_t st = ctx->stream;
+  PGP_HIP(hipMemcpyAsync(cv.at(p_obj), obj, n * 4, hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(cv.at(p_T), T, n * 64, hipMemcpyHostToDevice, st));
+  PGP_HIP(hipMemcpyAsync(cv.at(p_off), static_offsets, (n + 1) * 4, hipMemcpyHostToDevice, st));
+  if (m > 0) {
+    PGP_HIP(hipMemcpyAsync(cv.at(p_so), static_obj, m * 4, hipMemcpyHostToDevice, st));
+    PGP_HIP(hipMemcpyAsync(cv.at(p_sT), static_T, m * 64, hipMemcpyHostToDevice, st));
+  }
+  if ((rc = launch_tricp_states(ctx, o, n_states, cv.at(p_obj), 0, cv.at(p_T), cv.at(p_off), cv.at(p_so), cv.at(p_sT),
+                                cv.at(p_e), cv.at(p_it), cv.at(p_nk), st)) != PGP_OK)
+    return rc;
+  PGP_HIP(hipMemcpyAsync(T, cv.at(p_T), n * 64, hipMemcpyDeviceToHost, st));
+  if (energy) PGP_HIP(hipMemcpyAsync(energy, cv.at(p_e), n * 4, hipMemcpyDeviceToHost, st));
+  if (iters) PGP_HIP(hipMemcpyAsync(iters, cv.at(p_it), n * 4, hipMemcpyDeviceToHost, st));
+  if (n_kept) PGP_HIP(hipMemcpyAsync(n_kept, cv.at(p_nk), n * 4, hipMemcpyDeviceToHost, st));
+  PGP_HIP(hipStreamSynchronize(st));
+  return PGP_OK;
+}
+
+int pgp_tricp_states_device(pgp_ctx* ctx, const pgp_tricp_options* opt, int n_states, const int* d_obj, float* d_T,
+                            const int* d_static_offsets, const int* d_static_obj, const float* d_static_T,
+                            float* d_energy, int* d_iters, int* d_n_kept, void* stream) {
+  const char* who = "pgp_tricp_states_device";
+  // no static arrays at all: a batch without statics (the kernel then refuses a state whose range is not empty)
+  if (!ctx || n_states < 0 || (n_states > 0 && (!d_obj || !d_T || !d_static_offsets || (!d_static_obj) != (!d_static_T)))) {
+    set_error("%s: bad argument", who);
+    return PGP_EINVAL;
+  }
+  pgp_tricp_options o;
+  int rc = check_tricp_options(opt, who, o);
+  if (rc != PGP_OK) return rc;
+  CtxGuard guard(ctx, false);
+  if (ctx->tricp_n_obj <= 0) {
+    set_error("%s: no object set (pgp_tricp_set_objects)", who);
+    return PGP_ESTATE;
+  }
+  if (n_states == 0) return PGP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = launch_tricp_states(ctx, o, n_states, d_obj, 0, d_T, d_static_offsets, d_static_obj, d_static_T, d_energy, d_iters,
+                           d_n_kept, st);
+  note_device_work(ctx, st);
+  return rc;
+}
+
+int pgp_mcts_set_tricp(pgp_ctx* ctx, int on, const pgp_tricp_options* opt) {
+  const char* who = "pgp_mcts_set_tricp";
+  if (!ctx) {
+    set_error("%s: ctx is NULL", who);
+    return PGP_EINVAL;
+  }
+  pgp_tricp_options o;
+  const int rc = check_tricp_options(opt, who, o);
+  if (rc != PGP_OK) return rc;   // nothing changes
+  CtxGuard guard(ctx);
+  ctx->mcts_tricp = on != 0;
+  ctx->mcts_tricp_opt = o;
+  return PGP_OK;
 }
 
 }  // extern "C"

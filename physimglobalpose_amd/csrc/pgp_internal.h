@@ -397,6 +397,15 @@ struct pgp_ctx {
   // MCTS search (mcts.hip): step workspace (pose tables, settle inputs, descriptors, scores); two images per slot
   pgp::DevBuf d_mcts_ws, d_mcts_img;
 
+  // trimmed ICP of MCTS states (tricp_states.hip): the object set of pgp_tricp_set_objects -- every cloud as float4 in
+  // one buffer, the table of pgp::TricpObject behind it -- and the staging of the host-pointer call
+  pgp::DevBuf d_tricp_clouds, d_tricp_objs, d_tricp_io;
+  int tricp_n_obj = 0;
+  int tricp_max_seg = 0;            // the largest segment of the set: sizes the kernel's LDS
+  bool tricp_attr_set = false;      // the kernel's dynamic LDS limit has been raised
+  bool mcts_tricp = false;          // pgp_mcts_set_tricp: mcts_search_impl refines every state it settles
+  pgp_tricp_options mcts_tricp_opt = {0.5f, 0.008f, 1.0f, 100};
+
   // model preparation (model_prep.hip): sampling scratch (areas, weights, prefix sums, scan scratch); the multi-launch
   // farthest-point form's d and partial keys; host-API staging and the dense sample of pgp_model_from_mesh
   pgp::DevBuf d_prep_ws, d_fps_ws, d_prep_io;
@@ -705,6 +714,21 @@ int mcts_search_impl(pgp_ctx* ctx, const pgp_mcts_options* opt, const pgp_mcts_o
                      const float* table_params, const float* cam_pose, const pgp_camera* cam, const float* observed,
                      int* best_hyp, float* best_T, float* best_score, pgp_mcts_info* info, pgp_mcts_record* trace,
                      int trace_cap, int* n_trace);
+
+// tricp_states.hip.  One object of the resident set: device clouds as float4 {x, y, z, 0}.
+struct TricpObject {
+  const float4* model;
+  const float4* seg;
+  int n_model, n_seg;
+};
+// who: the caller's name for the message; fills `out` with the options as the kernel takes them (max_iterations resolved)
+int check_tricp_options(const pgp_tricp_options* o, const char* who, pgp_tricp_options& out);
+// One workgroup per state, enqueued on st: no synchronisation, no allocation.  d_obj NULL: every state is object
+// obj_uniform; d_sobj NULL: static j of a state is object j - d_soff[state] (the MCTS level's layout); d_sT NULL: a state with statics is a bad state.  The outputs
+// d_energy, d_iters, d_n_kept are nullable.
+int launch_tricp_states(pgp_ctx* ctx, const pgp_tricp_options& o, int n_states, const int* d_obj, int obj_uniform, float* d_T,
+                        const int* d_soff, const int* d_sobj, const float* d_sT, float* d_energy, int* d_iters,
+                        int* d_n_kept, hipStream_t st);
 
 // model_prep.hip.  launch_sample_mesh synchronises `st` once (the error flag); d_nrm, d_tri_out and d_xyz4 (the positions
 // again as float4, what launch_farthest_points reads) are nullable.

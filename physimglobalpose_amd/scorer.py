@@ -1799,6 +1799,66 @@ class LcpScorer:
         return dict(best_hyp=best_hyp[:n_obj].copy(), best_T=best_T[:n_obj].copy(), best_score=np.float32(best_score.value),
                     info={k: getattr(info, k) for k, _ in info._fields_}, trace=tr, n_trace=n_trace.value)
 
+    # ---- trimmed ICP of MCTS states: UCTState::performTrICP (csrc/tricp_states.hip) ------------------------------------
+    @staticmethod
+    def tricp_options(**kw):
+        """pgp_tricp_default_options with keyword overrides (trim_fraction, removal_radius, energy_ratio, max_iterations)."""
+        o = _lib.TricpOptions()
+        _lib.check(_lib.load().pgp_tricp_default_options(C.byref(o)))
+        for k, v in kw.items():
+            assert hasattr(o, k), k
+            setattr(o, k, v)
+        return o
+
+    def tricp_set_objects(self, objects):
+        """pgp_tricp_set_objects.  objects: per object a (model (n,3) object frame, segment (m,3) camera frame) pair; an
+        empty list frees the resident set."""
+        n = len(objects)
+        keep = []
+        objs = (_lib.TricpObject * max(n, 1))()
+        for i, (model, seg) in enumerate(objects):
+            m = _f32(model, 3)
+            s = _f32(seg, 3)
+            keep += [m, s]
+            objs[i] = _lib.TricpObject(_fp(m), len(m), _fp(s), len(s))
+        _lib.check(self._lib.pgp_tricp_set_objects(self._h, objs, n))
+
+    def tricp_states(self, obj, T, statics=None, **opt):
+        """pgp_tricp_states: obj (n,) object indices into the resident set, T (n,16) column-major camera-frame poses,
+        statics: per state a list of (object index, T (16,)) -> (T_out (n,16), energy (n,), iters (n,), n_kept (n,))."""
+        o = opt.pop("options", None) or self.tricp_options(**opt)
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        T = _f32(T, 16).copy()
+        off, so, sT = self._statics(statics, n)
+        energy = np.zeros(max(n, 1), np.float32)
+        iters = np.zeros(max(n, 1), np.int32)
+        kept = np.zeros(max(n, 1), np.int32)
+        _lib.check(self._lib.pgp_tricp_states(self._h, C.byref(o), n, ob.ctypes.data_as(_i), _fp(T), off.ctypes.data_as(_i),
+                                              so.ctypes.data_as(_i), _fp(sT), _fp(energy), iters.ctypes.data_as(_i),
+                                              kept.ctypes.data_as(_i)))
+        return T[:n], energy[:n], iters[:n], kept[:n]
+
+    def tricp_states_device(self, d_obj, d_T, d_static_offsets, d_static_obj, d_static_T, d_energy=None, d_iters=None,
+                            d_n_kept=None, stream=None, **opt):
+        """pgp_tricp_states_device on torch tensors (int32 / float32), queued on `stream` (default: the current stream),
+        no synchronisation; d_T is refined in place.  Returns d_T."""
+        import torch
+        o = opt.pop("options", None) or self.tricp_options(**opt)
+        n = int(d_obj.numel())
+        st = (stream or torch.cuda.current_stream(d_T.device)).cuda_stream
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.pgp_tricp_states_device(self._h, C.byref(o), n, p(d_obj), p(d_T), p(d_static_offsets),
+                                                     p(d_static_obj), p(d_static_T), p(d_energy), p(d_iters), p(d_n_kept),
+                                                     C.c_void_p(st)))
+        return d_T
+
+    def mcts_set_tricp(self, on=True, **opt):
+        """pgp_mcts_set_tricp: every later mcts_search of this context refines each state that adds an object with
+        tricp_states' kernel before it is settled (off by default); options as tricp_options."""
+        o = opt.pop("options", None) or self.tricp_options(**opt)
+        _lib.check(self._lib.pgp_mcts_set_tricp(self._h, int(bool(on)), C.byref(o)))
+
 
 class MultiGpuScorer:
     """One (scene, model) pair replicated on several GPUs of the node, hypotheses block-partitioned,
